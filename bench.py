@@ -25,6 +25,18 @@ is BASELINE C4's 16,777,216 photon slots at any N) and reports "scaling":
 "strong". At N > 1 `stages_ms.exchange` is the per-pass exchange (RCCL
 all-reduce + reduce-scatter, or the slot all-gather) timed to completion in
 the stage-timed passes after the timed region.
+
+A plain run sets up, warms up, times the steps and prints the headline line.
+`--full` adds everything else the line can carry, each from runs of its own
+after the timed steps: the per-stage split (`stages_ms`, `kernel_rates`), the
+counting launches behind `roofline` / `trace_roofline`, the exchange timing
+and the other exchange at N > 1, and the CPU baseline.
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32
+`DIR/<name>.npy`: `radiance` (PassRunner.final_gather over all records, record
+order) and, on one GPU, the PPM state the pass left in the records (`flux`,
+`radius2`, `photon_count`). Above 60 MB in all, the per-record arrays keep the
+same fixed, seeded sample of records, listed in `record_index` (float64).
 """
 import argparse
 import json
@@ -90,6 +102,13 @@ def parse():
                     help="N > 1: skip timing the other exchange (reduce <-> allgather) after the headline steps")
     ap.add_argument("--pipeline", type=int, default=int(os.environ.get("PM_BENCH_PIPELINE", "0")),
                     help="1: each timed pass's gather overlaps the next pass's trace (second stream; one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: per-stage split "
+                         "passes, counting launches (roofline), exchange timing and the other exchange (N > 1), "
+                         "the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float32; a fixed, seeded "
+                         "sample of the records above 60 MB in all)")
     return ap.parse_args()
 
 
@@ -209,6 +228,27 @@ def cpu_baseline(scene, params, threads, cfg):
                   f"{dt * threads:.1f} thread-s",
         "mgather_samples_per_s": round(len(recs0) * passes / dt / 1e6, 4),
     }
+
+
+DUMP_BUDGET_BYTES = 60_000_000
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, arrays):
+    """Write per-record arrays (all of one length) as path/<name>.npy, float32.
+    Over DUMP_BUDGET_BYTES in all, every array keeps the same seeded sample of
+    records, whose indices go to record_index.npy (float64: exact below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[:1].astype(np.float32).nbytes for a in arrays.values())
+    keep = None
+    if n * row_bytes > DUMP_BUDGET_BYTES:
+        m = DUMP_BUDGET_BYTES // (row_bytes + 8)
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+        np.save(os.path.join(path, "record_index.npy"), keep.astype(np.float64))
+    for name, a in arrays.items():
+        a = a if keep is None else a[keep]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def self_launch(n):
@@ -342,6 +382,19 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         gather_launches, gather_ms_total = ctx.timing_total("gather")
+        if args.dump_outputs:
+            # the state the last timed step left, before any later pass touches it
+            passes_run = args.warmup + args.steps if progressive else 1     # since the last reset
+            radiance = torch.empty((ctx.num_records(), 3), dtype=torch.float32, device="cuda")
+            runner.final_gather(float(runner.emitted_per_pass * passes_run), radiance)
+            torch.cuda.synchronize()
+            dump = {"radiance": radiance.cpu().numpy()}
+            if world == 1:
+                state = ctx.download_records()
+                dump.update(flux=state["flux"], radius2=state["radius2"], photon_count=state["photon_count"])
+            if rank == 0:
+                dump_outputs(args.dump_outputs, dump)
+            del radiance, dump
         gather_ms = gather_ms_total / max(gather_launches, 1)
         # per-stage split: a few more passes after the timed region, every stage timed
         ctx.set_stage_timing("all")
@@ -350,7 +403,7 @@ def main():
         # once (in the timed steps it overlaps the next pass's trace + build)
         runner.time_exchange = world > 1
         runner.pipeline = False            # stage times of passes run one after another
-        split_passes = min(args.steps, 10)
+        split_passes = min(args.steps, 10) if args.full else 0
         for _ in range(split_passes):
             step()
         runner.flush()
@@ -369,7 +422,7 @@ def main():
 
         census = canonical = tcensus = None
         n_valid = None
-        if not args.no_census:
+        if args.full and not args.no_census:
             # untimed counting launch of the same step: algorithmic-byte units
             ctx.set_counting(True)
             step()
@@ -395,7 +448,7 @@ def main():
         # max over ranks), so the line carries both designs: reduce (default)
         # and the all-gather of photon slots that north_star names
         alt = None
-        if world > 1 and not args.no_alt_exchange and not knn:
+        if args.full and world > 1 and not args.no_alt_exchange and not knn:
             alt_x = "allgather" if args.exchange == "reduce" else "reduce"
             if args.exchange == "reduce":
                 ctx.set_record_view(False)             # band gathers address records, not the active view
@@ -473,7 +526,7 @@ def main():
     kernel_name = ("k_gather_knn_ss" if knn else "k_gather_tile" if structure == PM_GATHER_GRID else "k_gather_kd")
     if n_valid is None:
         n_valid = ctx.map_info()["valid"]
-    if gather_pass_ms > 0:
+    if args.full and gather_pass_ms > 0:
         # The timed step starts from the initial PPM state (a deferred reset):
         # the gather reads only each active record's position and normal
         # (32 B; flux, N and r^2 are the initial constants, pm_gather.hip
@@ -579,7 +632,7 @@ def main():
                         "so this exceeds what the kernel moves"}
 
     exchange = None
-    if world > 1:
+    if args.full and world > 1:
         # bytes this rank sends into the collectives per pass
         if args.exchange == "reduce":
             xb = 4 * runner.v_per * world + 24 * runner.v_per * world
@@ -675,7 +728,7 @@ def main():
         out["exchange"] = exchange
     if alt is not None:
         out["alt_exchange"] = alt
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(scene, RenderParams.defaults(paths_per_pass=args.paths, **est),
                                                args.cpu_threads or default_cpu_threads(), args.config)

@@ -10,7 +10,7 @@ CFG=$2; REPS=$3; EA=$4; EB=$5; shift 5
 for i in $(seq 1 $REPS); do
   for v in a b; do
     if [ $v = a ]; then E=$EA; else E=$EB; fi
-    env $E timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-census "$@" \
+    env $E timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --full --no-cpu-baseline --no-census "$@" \
       > $O/${v}_$i.json 2> $O/${v}_$i.err || exit $?
   done
 done

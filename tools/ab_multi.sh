@@ -18,7 +18,7 @@ for i in $(seq 1 $REPS); do
     E=()
     [ -n "$lib" ] && [ "$lib" != "-" ] && E+=("PMHIP_LIB=$R/cuda-raytrace_amd/lib/variants/libpmhip_$lib.so")
     [ -n "${envs:-}" ] && IFS=, read -r -a EV <<< "$envs" && E+=("${EV[@]}")
-    env "${E[@]}" timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-census "$@" \
+    env "${E[@]}" timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --full --no-cpu-baseline --no-census "$@" \
       > $O/${label}_$i.json 2> $O/${label}_$i.err || exit $?
   done
 done

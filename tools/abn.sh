@@ -9,7 +9,7 @@ CFG=$2; REPS=$3; VS=$4; shift 4
 for i in $(seq 1 $REPS); do
   for v in $VS; do
     L=""; [ $v != base ] && L="PMHIP_LIB=$R/cuda-raytrace_amd/lib/variants/libpmhip_$v.so"
-    env $L timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-census "$@" \
+    env $L timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --full --no-cpu-baseline --no-census "$@" \
       > $O/${v}_$i.json 2> $O/${v}_$i.err || exit $?
   done
 done

@@ -6,7 +6,7 @@ CFG=$2; REPS=$3; NAMES=$4
 for i in $(seq 1 $REPS); do
   for v in $NAMES; do
     if [ $v = base ]; then E=""; else E="PMHIP_LIB=cuda-raytrace_amd/lib/variants/libpmhip_$v.so"; fi
-    env $E timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-census \
+    env $E timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --full --no-cpu-baseline --no-census \
       > $O/${v}_$i.json 2> $O/${v}_$i.err || exit $?
   done
 done

@@ -7,7 +7,7 @@ CFG=$2; REPS=$3; VAR=$4; VALS=$5; shift 5
 export TMPDIR=/tmp
 for i in $(seq 1 $REPS); do
   for v in $VALS; do
-    env $VAR=$v timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-census "$@" \
+    env $VAR=$v timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --full --no-cpu-baseline --no-census "$@" \
       > $O/${v}_$i.json 2> $O/${v}_$i.err || exit $?
   done
 done

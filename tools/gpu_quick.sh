@@ -16,7 +16,7 @@ fi
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  env $envs timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > "$O/bench$i.json" 2> "$O/bench$i.err"
+  env $envs timeout -k 10 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline ${BENCH_ARGS:-} > "$O/bench$i.json" 2> "$O/bench$i.err"
   rc=$?; echo "[bench$i $envs] rc=$rc" | tee -a "$O/steps.log"
   [ $rc -ne 0 ] && exit $rc
   python3 -c "import json;d=json.load(open('$O/bench$i.json'));print('$envs', d['value'], d['ms_per_step'], d['stages_ms'], d['roofline']['avg_launch_ms'] if d.get('roofline') else None)"

@@ -23,7 +23,7 @@ if [ "${PM_TESTS:-0}" = "1" ]; then
   timeout -k 10 900 python -u -m pytest tests -q -m gpu -p no:cacheprovider --timeout 300 --timeout-method thread > "$O/pytest_gpu.log" 2>&1; ok $? pytest
 fi
 B="--config $CFG $*"
-timeout -k 10 900 python bench.py --steps 20 --warmup 3 $B > "$O/bench_$N.json" 2> "$O/bench_$N.err"; ok $? bench
+timeout -k 10 900 python bench.py --steps 20 --warmup 3 --full $B > "$O/bench_$N.json" 2> "$O/bench_$N.err"; ok $? bench
 cd /tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof_$N" -o run --output-format csv -- python3 "$R/bench.py" --steps 20 --warmup 3 --no-cpu-baseline $B > "$O/prof_$N.log" 2>&1; ok $? rocprof_stats
 find "$O/prof_$N" -name '*kernel_stats.csv' -exec cp {} "$O/kernel_stats_$N.csv" \;

@@ -7,12 +7,12 @@ rc=$?
 echo "pytest rc=$rc" | tee -a $O/steps.log
 case $rc in 0|1) ;; *) exit $rc ;; esac   # a crash or time limit: nothing more on the GPU
 for c in c2 c3 c5; do
-  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err || exit $?
+  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --full --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err || exit $?
 done
 V=$R/cuda-raytrace_amd/lib/variants/libpmhip_nocoop.so
 if [ -f $V ]; then
   for c in c3 c5; do
-    PMHIP_LIB=$V timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_${c}_nocoop.json 2> $O/bench_${c}_nocoop.err || exit $?
+    PMHIP_LIB=$V timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --full --no-cpu-baseline > $O/bench_${c}_nocoop.json 2> $O/bench_${c}_nocoop.err || exit $?
   done
 fi
-timeout -k 10 300 python bench.py --estimator knn --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_c2_knn.json 2> $O/bench_c2_knn.err
+timeout -k 10 300 python bench.py --estimator knn --steps 20 --warmup 3 --full --no-cpu-baseline > $O/bench_c2_knn.json 2> $O/bench_c2_knn.err

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/sort_$1; mkdir -p $O; cd $R
 CFG=$2; REPS=$3; shift 3
 for i in $(seq 1 $REPS); do
   for v in 1 0; do
-    PM_TILE_SORT=$v timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-census "$@" \
+    PM_TILE_SORT=$v timeout -k 10 300 python bench.py --config $CFG --steps 20 --warmup 3 --full --no-cpu-baseline --no-census "$@" \
       > $O/sort${v}_$i.json 2> $O/sort${v}_$i.err || exit $?
   done
 done
