@@ -173,7 +173,7 @@ struct PbrtFilm : pmcuda::Film {
 void CudaRender::Render(const Scene *scene) {
     if (!camera_ || !sampler_) Severe("CreateCudaRenderer must precede Render");
     /* lights (CudaLight::preLaunch, cudalight.cpp:105-120): point lights, and
-     * the disks of diffuse area lights, each with its 2D light samples
+     * the disks and triangle meshes of diffuse area lights, each with its 2D light samples
      * registered in sampler order (CudaSample::Add2D rounds the count) */
     std::vector<pmcuda::Light> lights;
     Sample proto(NULL, NULL, NULL, scene);
@@ -195,6 +195,18 @@ void CudaRender::Render(const Scene *scene) {
                     pmcuda::Light L;
                     L.kind = pmcuda::Light::AreaDisk;
                     toPm(disk, L.disk);
+                    L.Lemit = toPm(al->Lemit);
+                    L.n_samples = (int)samplePerShape;
+                    lights.push_back(L);
+                } else if (const TriangleMesh *tm = dynamic_cast<const TriangleMesh *>(s.GetPtr())) {
+                    /* beyond the reference: the mesh as one light, its samples registered like a disk's */
+                    samplePerShape = (uint32_t)sampler_->RoundSize((int)samplePerShape);
+                    proto.Add2D(samplePerShape);
+                    n2d += samplePerShape;
+                    pmcuda::Light L;
+                    L.kind = pmcuda::Light::AreaMesh;
+                    toPm(tm, L.mesh);
+                    L.reverse_orientation = tm->ReverseOrientation;
                     L.Lemit = toPm(al->Lemit);
                     L.n_samples = (int)samplePerShape;
                     lights.push_back(L);

@@ -228,6 +228,19 @@ public:
         for (int i = 0; i < nverts; ++i) p[i] = (*ObjectToWorld)(P[i]);
     }
     ~TriangleMesh() { delete[] vertexIndex; delete[] p; delete[] s; delete[] n; delete[] uvs; }
+    /* the summed triangle areas: what pbrt-v2's ShapeSet totals over the mesh
+     * refined into Triangles (DiffuseAreaLight's area) */
+    float Area() const {
+        float a = 0.f;
+        for (int t = 0; t < ntris; ++t) {
+            const Point &p0 = p[vertexIndex[3 * t]], &p1 = p[vertexIndex[3 * t + 1]], &p2 = p[vertexIndex[3 * t + 2]];
+            const float ax = p1.x - p0.x, ay = p1.y - p0.y, az = p1.z - p0.z, bx = p2.x - p0.x, by = p2.y - p0.y,
+                        bz = p2.z - p0.z;
+            const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+            a += 0.5f * std::sqrt(cx * cx + cy * cy + cz * cz);
+        }
+        return a;
+    }
     int ntris, nverts;
     int *vertexIndex;
     Point *p;

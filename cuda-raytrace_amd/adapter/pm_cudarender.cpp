@@ -249,6 +249,13 @@ void CudaRender::addLights(const std::vector<Light> &lights) {
         if (L.kind == Light::Point) {
             const float I[3] = {L.intensity.r, L.intensity.g, L.intensity.b};
             check(ctx_, pm_add_light_point(ctx_, L.pos, I), "pm_add_light_point");
+        } else if (L.kind == Light::AreaMesh) {
+            const float Le[3] = {L.Lemit.r, L.Lemit.g, L.Lemit.b};
+            int index = -1;
+            check(ctx_, pm_add_light_mesh(ctx_, L.mesh.P.data(), (int)(L.mesh.P.size() / 3), L.mesh.indices.data(),
+                                          (int)(L.mesh.indices.size() / 3), L.reverse_orientation ? 1 : 0, Le,
+                                          L.n_samples < 1 ? 1 : L.n_samples, &index),
+                  "pm_add_light_mesh");
         } else {
             const DiskFrame f = disk_frame(L.disk);
             float n[3] = {f.x[1] * f.y[2] - f.x[2] * f.y[1], f.x[2] * f.y[0] - f.x[0] * f.y[2],

@@ -81,12 +81,15 @@ struct Shape {
 };
 
 /* pbrt lights as CudaLight::setupLight flattens them (cudalight.cpp:16-59):
- * PointLight, or DiffuseAreaLight over disk shapes. */
+ * PointLight, or DiffuseAreaLight over disk shapes; and, beyond the
+ * reference, DiffuseAreaLight over a triangle mesh (pm_add_light_mesh). */
 struct Light {
-    enum Kind { Point, AreaDisk } kind = Point;
+    enum Kind { Point, AreaDisk, AreaMesh } kind = Point;
     float pos[3] = {0, 0, 0}; /* Point */
     RGB intensity = {0, 0, 0};
     Shape disk;               /* AreaDisk: the disk shape (radius, height, o2w) */
+    Shape mesh;               /* AreaMesh: the world-space triangle mesh (P, indices) */
+    bool reverse_orientation = false; /* AreaMesh: pbrt's ReverseOrientation — emit from the other side */
     RGB Lemit = {0, 0, 0};
     int n_samples = 1;
 };

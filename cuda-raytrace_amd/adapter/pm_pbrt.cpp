@@ -414,12 +414,18 @@ struct PbrtParser::Impl {
                 warn(lx, line, "area lights inside ObjectBegin are not supported (%s)", name);
             } else if (gs.area_light != "diffuse") {
                 warn(lx, line, "area light \"%s\" not supported", gs.area_light);
-            } else if (name != "disk") { /* cudalight.cpp:35-56: only disks emit */
-                warn(lx, line, "UnImplemented Cuda Area Light Source: %s (only disks)", name);
+            } else if (name != "disk" && name != "trianglemesh") { /* cudalight.cpp:35-56: only disks emit; meshes are ours */
+                warn(lx, line, "UnImplemented Cuda Area Light Source: %s (only disks and triangle meshes)", name);
             } else {
                 Light L;
-                L.kind = Light::AreaDisk;
-                L.disk = s;
+                if (name == "disk") {
+                    L.kind = Light::AreaDisk;
+                    L.disk = s;
+                } else {
+                    L.kind = Light::AreaMesh;
+                    L.mesh = s;
+                    L.reverse_orientation = gs.reverse;
+                }
                 const RGB Le = spectrum(lx, line, gs.area_params, "L", RGB{1.f, 1.f, 1.f});
                 const RGB sc = spectrum(lx, line, gs.area_params, "scale", RGB{1.f, 1.f, 1.f});
                 L.Lemit = RGB{Le.r * sc.r, Le.g * sc.g, Le.b * sc.b};

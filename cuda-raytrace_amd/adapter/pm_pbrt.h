@@ -11,7 +11,9 @@
  *   state        WorldBegin/End AttributeBegin/End ReverseOrientation
  *                Material MakeNamedMaterial NamedMaterial Texture (constant)
  *   lights       LightSource "point" (I, scale, from), AreaLightSource "diffuse"
- *                (L, scale, nsamples) on the following shapes
+ *                (L, scale, nsamples) on the following "disk" and
+ *                "trianglemesh" shapes (a mesh emits from the side of
+ *                cross(p1 - p0, p2 - p0); ReverseOrientation flips it)
  *   shapes       Shape "trianglemesh" (P in world space as pbrt's TriangleMesh
  *                stores it; N / uv raw), "sphere", "disk"; anything else goes
  *                to CreateCudaShape, which warns and skips it like

@@ -14,7 +14,8 @@
  * render the same inputs through the stage driver and compare bit for bit.
  *
  * usage: pm_pbrt_host --out f.bin [--width W --height H --paths N
- *        --photonmap grid|kdtree --renderer photonmap|simple --nsamples S --instanced]
+ *        --photonmap grid|kdtree --renderer photonmap|simple --nsamples S --instanced
+ *        --quad-light]   (the box's own 130 x 105 quad light, a trianglemesh, instead of the disk)
  */
 #include <cmath>
 #include <cstdio>
@@ -34,7 +35,7 @@ namespace {
 struct Opts {
     int W = 64, H = 48, paths = 16384, nsamples = 1;
     std::string photonmap = "grid", renderer = "photonmap", out;
-    bool instanced = false;
+    bool instanced = false, quad_light = false;
 };
 
 /* pixel centres in raster order, one sample per pixel; light 2D randoms:
@@ -175,12 +176,16 @@ int run(const Opts &o) {
     float mi[4][4] = {{1, 0, 0, -278.f}, {0, 0, 1, -279.5f}, {0, -1, 0, 548.7f}, {0, 0, 0, 1}};
     static const Transform light2world{Matrix4x4(m), Matrix4x4(mi)}, world2light{Matrix4x4(mi), Matrix4x4(m)};
     Reference<Shape> disk(new Disk(&light2world, &world2light, false, 0.f, 65.f, 0.f, 360.f));
+    /* --quad-light (scenes/cornell-quad-light.pbrt): AreaLightSource "diffuse" on
+     * Shape "trianglemesh", the quad wound to face down */
+    Reference<Shape> emitter = o.quad_light ? quads(&identity, {{343, 548.7f, 227, 343, 548.7f, 332, 213, 548.7f, 332, 213, 548.7f, 227}})
+                                            : disk;
     const float Le[3] = {17.f, 17.f, 17.f};
-    DiffuseAreaLight *area = new DiffuseAreaLight(light2world, RGBSpectrum::FromRGB(Le, SPECTRUM_ILLUMINANT),
-                                                  o.nsamples, disk);
+    DiffuseAreaLight *area = new DiffuseAreaLight(o.quad_light ? identity : light2world,
+                                                  RGBSpectrum::FromRGB(Le, SPECTRUM_ILLUMINANT), o.nsamples, emitter);
     Scene scene;
     scene.lights.push_back(area);
-    CreateCudaShape("disk", disk, NULL, black.GetPtr(), 0);
+    CreateCudaShape(o.quad_light ? "trianglemesh" : "disk", emitter, NULL, black.GetPtr(), 0);
     /* MakeRenderer: Renderer "cuda" */
     KeepFilm *film = new KeepFilm(o.W, o.H);
     RecordingCamera *camera = new RecordingCamera(film, o.W, o.H);
@@ -219,6 +224,7 @@ int main(int argc, char **argv) {
         else if (a == "--photonmap") o.photonmap = val();
         else if (a == "--renderer") o.renderer = val();
         else if (a == "--instanced") o.instanced = true;
+        else if (a == "--quad-light") o.quad_light = true;
         else if (a == "--out") o.out = val();
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }

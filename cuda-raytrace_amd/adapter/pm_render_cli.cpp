@@ -204,6 +204,17 @@ int dump(const std::string &path) {
             DumpSink::arr(lights, L.pos, 3);
             lights += ", \"I\": ";
             DumpSink::arr(lights, I, 3);
+        } else if (L.kind == Light::AreaMesh) {
+            const float Le[3] = {L.Lemit.r, L.Lemit.g, L.Lemit.b};
+            std::snprintf(b, sizeof b, "{\"kind\": \"mesh\", \"nsamples\": %d, \"reverse_orientation\": %d, \"Le\": ",
+                          L.n_samples, L.reverse_orientation ? 1 : 0);
+            lights += b;
+            DumpSink::arr(lights, Le, 3);
+            lights += ", \"P\": ";
+            DumpSink::arr(lights, L.mesh.P.data(), L.mesh.P.size());
+            lights += ", \"indices\": [";
+            for (size_t i = 0; i < L.mesh.indices.size(); ++i) lights += (i ? ", " : "") + std::to_string(L.mesh.indices[i]);
+            lights += "]";
         } else {
             const float Le[3] = {L.Lemit.r, L.Lemit.g, L.Lemit.b};
             std::snprintf(b, sizeof b, "{\"kind\": \"disk\", \"nsamples\": %d, \"Le\": ", L.n_samples);

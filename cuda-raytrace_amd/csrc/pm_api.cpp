@@ -87,6 +87,7 @@ struct Ctx {
     std::vector<float4> spheres; /* 4 per sphere */
     std::vector<float> sphere_o2w;
     std::vector<LightDev> lights;
+    std::vector<LightTri> light_tris; /* the mesh lights' emitting triangles, light after light (SceneDev::light_tris) */
     int rand2d_total = 0;
     int pinhole = 0, W = 0, H = 0;
     float eye[3] = {0}, fwd[3] = {0}, right[3] = {0}, up[3] = {0};
@@ -96,6 +97,7 @@ struct Ctx {
     bool committed = false;
     /* device scene */
     DevBuf d_scene, d_rays, d_rand2d; /* d_scene: the scene blob (SceneDev) */
+    DevBuf d_light_tris;              /* SceneDev::light_tris (kept out of the blob: never LDS-resident) */
     DevBuf d_tripairs;                /* brute-force scenes: triangle pairs interleaved (SceneDev::tri_pairs_g) */
     SceneDev S{};
     float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};
@@ -852,7 +854,7 @@ void pm_destroy(void *ptr) {
                       &c->d_dl, &c->d_slots, &c->d_count, &c->d_scratch, &c->d_vflags, &c->d_vrank, &c->d_vlist, &c->d_vsums,
                       &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times, &c->d_tile_cost, &c->d_tiles2,
                       &c->d_kd, &c->d_out, &c->d_counters, &c->d_tiles, &c->d_tile_flags, &c->d_tile_count,
-                      &c->d_r2hist, &c->d_spill};
+                      &c->d_r2hist, &c->d_spill, &c->d_light_tris};
     for (DevBuf *b : bufs) b->release();
     if (c->tile_event) (void)hipEventDestroy(c->tile_event);
     if (c->r2_event) (void)hipEventDestroy(c->r2_event);
@@ -1029,6 +1031,54 @@ int pm_add_light_disk(void *ptr, const float o[3], const float p1[3], const floa
     L.le = f4(Le[0], Le[1], Le[2], 0);
     c->rand2d_total += ns;
     c->lights.push_back(L);
+    c->committed = false;
+    return PM_OK;
+}
+
+/* the emission table of a mesh light, as pm_api.h states it (tests restate it) */
+int pm_add_light_mesh(void *ptr, const float *P, int nverts, const int *idx, int ntris, int reverse,
+                      const float Le[3], int nsamples, int *out_light) {
+    GROUP_FWD(ptr, pm_add_light_mesh(sub, P, nverts, idx, ntris, reverse, Le, nsamples, out_light));
+    GETCTX(ptr);
+    if (!P || !idx || !Le || !out_light) FAIL(c, PM_ERR_INVALID, "null mesh light argument");
+    if (nverts <= 0 || ntris <= 0) FAIL(c, PM_ERR_INVALID, "empty mesh light");
+    for (int64_t i = 0; i < 3 * (int64_t)ntris; ++i)
+        if (idx[i] < 0 || idx[i] >= nverts) FAIL(c, PM_ERR_INVALID, "vertex index %d out of range", idx[i]);
+    if (c->light_tris.size() + (size_t)ntris >= ((size_t)1 << 31)) FAIL(c, PM_ERR_INVALID, "too many emitting triangles");
+    std::vector<LightTri> tris((size_t)ntris);
+    std::vector<double> sum((size_t)ntris);
+    double total = 0.0;
+    for (int t = 0; t < ntris; ++t) {
+        const float *p0 = P + 3 * (size_t)idx[3 * t], *p1 = P + 3 * (size_t)idx[3 * t + 1], *p2 = P + 3 * (size_t)idx[3 * t + 2];
+        const double a[3] = {(double)p1[0] - p0[0], (double)p1[1] - p0[1], (double)p1[2] - p0[2]};
+        const double b[3] = {(double)p2[0] - p0[0], (double)p2[1] - p0[1], (double)p2[2] - p0[2]};
+        const double n[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+        const double len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        total += 0.5 * len;
+        sum[t] = total;
+        /* a zero-area triangle is never sampled: its normal is left zero */
+        const double inv = len > 0.0 ? (reverse ? -1.0 : 1.0) / len : 0.0;
+        LightTri &T = tris[t];
+        T.p0_cdf = f4(p0[0], p0[1], p0[2], 0.f);
+        T.e1 = f4(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2], 0.f);
+        T.e2 = f4(p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2], 0.f);
+        T.n = f4((float)(n[0] * inv), (float)(n[1] * inv), (float)(n[2] * inv), 0.f);
+    }
+    if (!(total > 0.0) || !std::isfinite(total) || !std::isfinite((float)total))
+        FAIL(c, PM_ERR_INVALID, "mesh light area %g is zero or not finite", total);
+    for (int t = 0; t < ntris; ++t) tris[t].p0_cdf.w = (float)(sum[t] / total);
+    tris[ntris - 1].p0_cdf.w = 1.0f;
+    const int ns = std::max(1, nsamples);
+    LightDev L{};
+    L.o_type = f4(ibits((int)c->light_tris.size()), ibits(ntris), ibits(reverse ? 1 : 0), ibits(PM_LIGHT_AREA_MESH));
+    L.p1_ns = f4(0, 0, 0, ibits(ns));
+    L.p2_r2d = f4(0, 0, 0, ibits(c->rand2d_total)); /* CudaSample::Add2D offset, as the disk light */
+    L.n_area = f4(0, 0, 0, (float)total);
+    L.le = f4(Le[0], Le[1], Le[2], 0);
+    c->rand2d_total += ns;
+    c->light_tris.insert(c->light_tris.end(), tris.begin(), tris.end());
+    c->lights.push_back(L);
+    *out_light = (int)c->lights.size() - 1;
     c->committed = false;
     return PM_OK;
 }
@@ -1465,6 +1515,8 @@ int pm_commit(void *ptr) {
     S.n_tris = (int)L.n_tris; S.n_disks = (int)nd; S.n_spheres = (int)ns;
     S.tri_geo_g = S.tri_geo; S.tri_id_g = S.tri_id;
     S.tri_pairs_g = L.id_order ? c->d_tripairs.as<float>() : nullptr;
+    if ((rc = upload(c, c->d_light_tris, c->light_tris))) return rc;
+    S.light_tris = c->d_light_tris.as<LightTri>();
     S.n_inst = (int)ni;
     S.insts = ni ? (const float4 *)(base + L.o_insts) : nullptr;
     S.obj_v = ni ? (const float4 *)(base + L.o_objv) : nullptr;
@@ -1487,7 +1539,14 @@ int pm_commit(void *ptr) {
     double em = 0.0, kd = 1.0;
     for (const LightDev &L : c->lights) {
         double le = std::max({std::fabs(L.le.x), std::fabs(L.le.y), std::fabs(L.le.z)});
-        em = std::max(em, fbits_h(L.o_type.w) == PM_LIGHT_POINT ? le * 4.0 * M_PI : le * L.n_area.w * 2.0 * M_PI);
+        /* emitted power bound (sample_le's Le / pdf): a point light's 4 pi I; a
+         * disk's Le area 2 pi; a mesh's the same with its total area */
+        switch (fbits_h(L.o_type.w)) {
+        case PM_LIGHT_POINT: em = std::max(em, le * 4.0 * M_PI); break;
+        case PM_LIGHT_AREA_DISK: em = std::max(em, le * L.n_area.w * 2.0 * M_PI); break;
+        case PM_LIGHT_AREA_MESH: em = std::max(em, le * L.n_area.w * 2.0 * M_PI); break; /* n_area.w: the total area */
+        default: FAIL(c, PM_ERR_INVALID, "light type %d has no emitted-power bound", fbits_h(L.o_type.w));
+        }
     }
     for (const float4 &m : c->materials)
         if (fbits_h(m.w) == PM_MATTE) kd = std::max({kd, (double)m.x, (double)m.y, (double)m.z});
@@ -2641,6 +2700,7 @@ int pm_scene_section(void *ptr, int section, void *out, int64_t max_bytes, int64
     case PM_SCENE_BVH4: src = S.wnodes; n = S.wide ? (S.wide == 2 ? 64 : 128) * c->bvh4_nodes : 0; break; /* 3: 8-wide, 128 B */
     case PM_SCENE_INSTANCES: src = S.insts; n = 128 * (int64_t)S.n_inst; break;
     case PM_SCENE_OBJ_TRIS: src = S.obj_v; n = S.n_inst ? 48 * c->obj_tris_stored : 0; break;
+    case PM_SCENE_LIGHT_TRIS: src = S.light_tris; n = (int64_t)(c->light_tris.size() * sizeof(LightTri)); break;
     default: FAIL(c, PM_ERR_INVALID, "unknown scene section %d", section);
     }
     if (bytes) *bytes = n;

@@ -68,6 +68,18 @@ struct LightDev {      /* CudaLightDevice (common.cu.h:47-59), 80 B */
     float4 p2_r2d;     /* p2.xyz, random2DStart (int bits) */
     float4 n_area;     /* normal.xyz, area */
     float4 le;         /* intensity.xyz, 0 */
+    /* PM_LIGHT_AREA_MESH (ours) has no o / p1 / p2 / normal: o_type.x, .y
+     * hold (int bits) the first entry and the entry count of its triangles
+     * in SceneDev::light_tris, o_type.z its reverse_orientation flag;
+     * n_area.w is the mesh's total area, the other lanes as above */
+};
+
+/* one emitting triangle of a mesh light, 64 B (four 16-B loads per lane) */
+struct LightTri {
+    float4 p0_cdf;     /* p0.xyz, cdf[k] of the light's area distribution */
+    float4 e1;         /* p1 - p0, 0 */
+    float4 e2;         /* p2 - p0, 0 */
+    float4 n;          /* unit normal of the emitting side, 0 */
 };
 
 struct SceneDev {
@@ -125,7 +137,13 @@ struct SceneDev {
     const float4 *obj_uv; /* object vertex uvs (xy) */
     const int4 *obj_mesh; /* per object mesh: material, light, has_n, has_uv */
     int n_inst;
-    /* all arrays above are 16-B aligned sections of one blob in HBM */
+    /* the emitting triangles of the mesh lights (PM_LIGHT_AREA_MESH), light
+     * after light; a buffer of its own in HBM, never part of the blob: the LDS
+     * modes budget their LDS for the scene, and a lane's search through a
+     * light's cdf diverges, so it is read with plain vector loads (L2 / TCP
+     * keep the small read-only table) */
+    const LightTri *light_tris;
+    /* all arrays above but light_tris are 16-B aligned sections of one blob in HBM */
     const char *blob;
     uint32_t blob_bytes;
     uint32_t lds_bytes; /* = blob_bytes when the blob fits LDS_SCENE_MAX (LDS-resident mode), else 0 */
@@ -1181,7 +1199,10 @@ PMD bool traverse(const SceneDev &S, const Ray &ray, Hit &best, int *stack, int 
 }
 
 /* ------------------------------------------------------------- shading */
-struct Geo { v3 ns, dpdu; int material, light; };
+/* ng: the unit geometric normal of the hit primitive — for a triangle the
+ * direction of cross(p1 - p0, p2 - p0), whatever its vertex normals say;
+ * read by light_le for mesh lights only (dead code elsewhere) */
+struct Geo { v3 ns, dpdu, ng; int material, light; };
 
 /* hit attributes (cudatrianglemesh.cu:20-78, cudadisk.cu:36-47,
  * cudasphere.cu:35-48), transformed and normalized as the closest-hit
@@ -1226,7 +1247,8 @@ PMD Geo shade(const SceneDev &S, const Ray &ray, const Hit &h) {
                    (dv2 * dp1.z - dv1 * dp2.z) * invdet);
         }
         g.dpdu = normalize(d);
-        if (!mi.z) { g.ns = normalize(n); return g; }
+        g.ng = normalize(n);
+        if (!mi.z) { g.ns = g.ng; return g; }
         /* vertex normals through pbrt's Transform::operator()(Normal) (transpose
          * of mInv), then interpolated per hit as for a flattened mesh */
         const float4 *W = I + 3;
@@ -1241,6 +1263,7 @@ PMD Geo shade(const SceneDev &S, const Ray &ray, const Hit &h) {
         const int mb = fbits(s0.w);
         g.material = mb & 0x7fffffff; g.light = fbits(s1.w);
         g.dpdu = xyz(s1);
+        g.ng = xyz(s0);
         if (mb >= 0) { g.ns = xyz(s0); return g; }
         const int4 ti = S.tri_info[idx]; /* shading normals: interpolated per hit */
         v3 n0 = xyz(S.norms[ti.x]), n1 = xyz(S.norms[ti.y]), n2 = xyz(S.norms[ti.z]);
@@ -1271,6 +1294,7 @@ PMD Geo shade(const SceneDev &S, const Ray &ray, const Hit &h) {
         g.material = fbits(s[3].y); g.light = fbits(s[3].z);
     }
     g.ns = normalize(nsw);
+    g.ng = g.ns;
     g.dpdu = normalize(dpduw);
     return g;
 }
@@ -1317,14 +1341,52 @@ PMD v3 sample_f(v3 kd, const Geo &g, v3 wow, float u1, float u2, v3 *wiw, float 
 }
 
 /* ------------------------------------------------------------- lights */
+/* A point of a mesh light (PM_LIGHT_AREA_MESH, ours: the reference emits from
+ * disks only) for the 2-D sample (u1, u2), uniform over its area; *n = the
+ * emitting side's unit normal there. u1 picks triangle k, the first with
+ * cdf[k] > u1 (pm_add_light_mesh builds the table): a binary search whose
+ * trip count depends on the light's triangle count alone, so the lanes of a
+ * wave stay together and only their addresses differ; an empty bin (a
+ * zero-area triangle) is never picked. u1 is held below 1 first (host rays
+ * may carry a 2-D sample of exactly 1): the bin found is then never empty,
+ * whatever the last triangles' areas, and the remap never divides 0 by 0.
+ * u1 is then stretched over the bin, and pbrt's UniformSampleTriangle
+ * (su = sqrt(u1), b0 = 1 - su, b1 = u2 su) places the point at
+ * b0 p0 + b1 p1 + b2 p2, b2 = 1 - b0 - b1, evaluated as p0 + b1 e1 + b2 e2. */
+PMD v3 sample_light_mesh(const LightDev &L, const LightTri *tris, float u1, float u2, v3 *n) {
+    u1 = fminf(u1, 0x1.fffffep-1f);
+    const LightTri *T = tris + fbits(L.o_type.x);
+    int lo = 0, len = fbits(L.o_type.y);
+    while (len > 1) {
+        const int half = len >> 1;
+        lo = T[lo + half - 1].p0_cdf.w > u1 ? lo : lo + half;
+        len -= half;
+    }
+    const float4 a = T[lo].p0_cdf, e1 = T[lo].e1, e2 = T[lo].e2, nn = T[lo].n;
+    const float cprev = lo > 0 ? T[lo - 1].p0_cdf.w : 0.f;
+    const float su = sqrtf((u1 - cprev) / (a.w - cprev));
+    const float b0 = 1.f - su, b1 = u2 * su;
+    *n = xyz(nn);
+    return xyz(a) + b1 * xyz(e1) + (1.f - b0 - b1) * xyz(e2);
+}
+
 /* cudalight.cu.h:18-64 */
-PMD v3 sample_l_shading(const LightDev &L, v3 point, float u1, float u2, v3 *uwi, float *pdf) {
+PMD v3 sample_l_shading(const LightDev &L, const LightTri *tris, v3 point, float u1, float u2, v3 *uwi, float *pdf) {
     int type = fbits(L.o_type.w);
     if (type == PM_LIGHT_POINT) {
         *uwi = xyz(L.o_type) - point;
         float invlength2 = rcp_exact(dot(*uwi, *uwi));
         *pdf = 1.f;
         return xyz(L.le) * invlength2;
+    }
+    if (type == PM_LIGHT_AREA_MESH) { /* the disk's estimator below, with the sampled triangle's normal */
+        v3 n;
+        *uwi = sample_light_mesh(L, tris, u1, u2, &n) - point;
+        v3 wi = normalize(*uwi);
+        float distanceSquared = dot(*uwi, *uwi);
+        float costha = -dot(n, wi);
+        *pdf = distanceSquared / (costha * L.n_area.w);
+        return costha > 0.0f ? xyz(L.le) : mk(0.f, 0.f, 0.f);
     }
     float x, y;
     concentric_sample_disk(u1, u2, &x, &y);
@@ -1337,8 +1399,8 @@ PMD v3 sample_l_shading(const LightDev &L, v3 point, float u1, float u2, v3 *uwi
 }
 
 /* cudalight.cu.h:78-124 — emission */
-PMD v3 sample_le(const LightDev &L, float lu1, float lu2, float u1, float u2, float eps, Ray *ray, v3 *Ns,
-                 float *pdf) {
+PMD v3 sample_le(const LightDev &L, const LightTri *tris, float lu1, float lu2, float u1, float u2, float eps,
+                 Ray *ray, v3 *Ns, float *pdf) {
     int type = fbits(L.o_type.w);
     if (type == PM_LIGHT_POINT) {
         ray->o = xyz(L.o_type);
@@ -1347,6 +1409,14 @@ PMD v3 sample_le(const LightDev &L, float lu1, float lu2, float u1, float u2, fl
         *Ns = ray->d;
         *pdf = (float)(1.f / (4.f * M_PI));
         return xyz(L.le);
+    }
+    if (type == PM_LIGHT_AREA_MESH) { /* the disk's emission below from a point of the mesh */
+        v3 org = sample_light_mesh(L, tris, lu1, lu2, Ns);
+        v3 dir = uniform_sample_sphere(u1, u2);
+        if (dot(dir, *Ns) < 0.f) dir = dir * -1.f;
+        ray->o = org; ray->d = dir; ray->tmin = 1e-2f;
+        *pdf = INV_TWOPI;
+        return xyz(L.le) * L.n_area.w;
     }
     float x, y;
     concentric_sample_disk(lu1, lu2, &x, &y);
@@ -1359,8 +1429,15 @@ PMD v3 sample_le(const LightDev &L, float lu1, float lu2, float u1, float u2, fl
     return xyz(L.le) * L.n_area.w;
 }
 
-/* cudalight.cu.h:128-138 */
-PMD v3 light_le(const LightDev &L, v3 wow) {
+/* cudalight.cu.h:128-138; ng: the geometric normal of the primitive that was
+ * hit (Geo::ng). A mesh light has no normal of its own: it emits from the
+ * side of the hit triangle's cross(p1 - p0, p2 - p0), the other side when
+ * its reverse_orientation flag is set (the sign its light_tris normals carry) */
+PMD v3 light_le(const LightDev &L, v3 wow, v3 ng) {
+    if (fbits(L.o_type.w) == PM_LIGHT_AREA_MESH) {
+        const float c = dot(ng, wow);
+        return (fbits(L.o_type.z) ? -c : c) > 0.f ? xyz(L.le) : mk(0.f, 0.f, 0.f);
+    }
     if (dot(xyz(L.n_area), wow) > 0.f) return xyz(L.le);
     return mk(0.f, 0.f, 0.f);
 }

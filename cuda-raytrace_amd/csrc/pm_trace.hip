@@ -87,7 +87,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
     v3 L = mk(0.f, 0.f, 0.f);
     const int total = S.n_lights;
     if (g.light < total) {
-        if (g.light >= 0) L = L + light_le(S.lights[g.light], -dir);
+        if (g.light >= 0) L = L + light_le(S.lights[g.light], -dir, g.ng);
         float4 m = S.materials[g.material];
         v3 fv = fbits(m.w) == PM_MATTE ? xyz(m) * INV_PI : mk(0.f, 0.f, 0.f);
         for (int i = 0; i < total; ++i) {
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
             const int ltype = fbits(Lt.o_type.w);
             for (int s = 0; s < nS; ++s) {
                 float u1 = 0.f, u2 = 0.f;
-                if (ltype == PM_LIGHT_AREA_DISK) {
+                if (ltype == PM_LIGHT_AREA_DISK || ltype == PM_LIGHT_AREA_MESH) {
                     int slot = fbits(Lt.p2_r2d.w) + s;
                     if (P.pinhole) {
                         uint32_t o4[4];
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
                     }
                 }
                 v3 uwi; float pdf;
-                v3 li = sample_l_shading(Lt, point, u1, u2, &uwi, &pdf);
+                v3 li = sample_l_shading(Lt, S.light_tris, point, u1, u2, &uwi, &pdf);
                 Ray sr;
                 sr.o = point; sr.d = uwi; sr.tmin = 0.001f; sr.tmax = 1.0f - 0.001f;
                 Hit sh;
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
         for (int i = 0; i < S.n_lights; ++i) {
             const LightDev Lt = S.lights[i];
             float u1 = 0.f, u2 = 0.f;
-            if (fbits(Lt.o_type.w) == PM_LIGHT_AREA_DISK) {
+            if (fbits(Lt.o_type.w) == PM_LIGHT_AREA_DISK || fbits(Lt.o_type.w) == PM_LIGHT_AREA_MESH) {
                 const int slot = fbits(Lt.p2_r2d.w); /* random2DStart + iSample 0 */
                 if (P.pinhole) {
                     uint32_t o4[4];
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
                 }
             }
             v3 uwi; float pdf;
-            const v3 li = sample_l_shading(Lt, point, u1, u2, &uwi, &pdf);
+            const v3 li = sample_l_shading(Lt, S.light_tris, point, u1, u2, &uwi, &pdf);
             Ray sr;
             sr.o = point; sr.d = uwi; sr.tmin = 0.001f; sr.tmax = 1.0f - 0.001f;
             Hit sh;
@@ -376,7 +376,7 @@ PMD bool emit_path(const TraceParams &P, const SceneDev &S, const uint32_t *perm
     permuted_halton4(pm_index, perm, P.perm_bits, smp);
     const LightDev Lt = S.lights[P.light_index];
     v3 N1; float pdf;
-    v3 Le = sample_le(Lt, smp[0], smp[1], smp[2], smp[3], P.eps, &st.ray, &N1, &pdf);
+    v3 Le = sample_le(Lt, S.light_tris, smp[0], smp[1], smp[2], smp[3], P.eps, &st.ray, &N1, &pdf);
     st.pid = pid; st.nI = 0; st.spec = 0; st.stored = 0; st.pslot = PSLOT_NONE;
     if (pdf == 0.0f || is_black(Le)) return false;
     st.ray.tmax = RT_DEFAULT_MAX;

@@ -12,6 +12,7 @@ PM_ERR_NOMEM = 4
 
 PM_MATTE, PM_MIRROR, PM_GLASS = 0, 1, 2
 PM_LIGHT_POINT, PM_LIGHT_AREA_DISK = 1, 3
+PM_LIGHT_AREA_MESH = 4  # ours: an emitting triangle mesh (pm_add_light_mesh)
 PM_REC_EXCEPTION, PM_REC_MISS, PM_REC_INVALID, PM_REC_BACKFACE = 0x1, 0x2, 0x4, 0x8
 PM_REC_INACTIVE = PM_REC_EXCEPTION | PM_REC_MISS | PM_REC_INVALID
 PM_GATHER_GRID, PM_GATHER_KDTREE = 0, 1
@@ -28,6 +29,9 @@ RECORD_DTYPE = np.dtype([
     ("flux", "<f4", 3), ("radius2", "<f4"), ("dl", "<f4", 3), ("photon_count", "<f4"),
 ])
 assert RECORD_DTYPE.itemsize == 64
+# one emitting triangle of a mesh light (PM_SCENE_LIGHT_TRIS; pm_device.h LightTri), 64 B
+LIGHT_TRI_DTYPE = np.dtype([("p0", "<f4", 3), ("cdf", "<f4"), ("e1", "<f4", 4), ("e2", "<f4", 4), ("n", "<f4", 4)])
+assert LIGHT_TRI_DTYPE.itemsize == 64
 
 
 class PMConfig(ctypes.Structure):

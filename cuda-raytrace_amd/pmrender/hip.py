@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .abi import (PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PMConfig, RenderParams, Stats, f32, fptr, iptr,
+from .abi import (LIGHT_TRI_DTYPE, PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PMConfig, RenderParams, Stats, f32, fptr, iptr,
                   record_pixels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,6 +53,7 @@ def load_library(path=None):
         "pm_add_disk": (c_int, [vp, P_f, P_f, P_f, P_f, c_float, c_float, c_int, c_int]),
         "pm_add_light_point": (c_int, [vp, P_f, P_f]),
         "pm_add_light_disk": (c_int, [vp, P_f, P_f, P_f, P_f, P_f, c_float, c_int]),
+        "pm_add_light_mesh": (c_int, [vp, P_f, c_int, P_i, c_int, c_int, P_f, c_int, P_i]),
         "pm_set_pinhole": (c_int, [vp, P_f, P_f, P_f, P_f, c_int, c_int]),
         "pm_set_eye_rays": (c_int, [vp, P_f, i64, P_f, c_int]),
         "pm_commit": (c_int, [vp]),
@@ -209,6 +210,17 @@ class Context:
     def add_light_disk(self, o, p1, p2, n, Le, area, nsamples):
         self._chk(self.lib.pm_add_light_disk(self.h, fptr(f32(o, 3)), fptr(f32(p1, 3)), fptr(f32(p2, 3)),
                                              fptr(f32(n, 3)), fptr(f32(Le, 3)), float(area), int(nsamples)))
+
+    def add_light_mesh(self, P, idx, Le, nsamples, reverse_orientation=False):
+        """A triangle-mesh area light (pm_add_light_mesh); returns its light index. The visible
+        geometry is the caller's: add_trimesh(P, idx, ..., light=<the index>)."""
+        P = f32(P)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        out = ctypes.c_int()
+        self._chk(self.lib.pm_add_light_mesh(self.h, fptr(P), P.size // 3, iptr(idx), idx.size // 3,
+                                             int(bool(reverse_orientation)), fptr(f32(Le, 3)), int(nsamples),
+                                             ctypes.byref(out)))
+        return out.value
 
     def set_pinhole(self, eye, fwd, right, up, W, H):
         self.width, self.height, self.pinhole = int(W), int(H), True
@@ -405,14 +417,15 @@ class Context:
 
     SCENE_SECTIONS = {"refs": (0, np.uint32), "tri_geo": (1, np.float32), "tri_shade": (2, np.float32),
                       "tri_id": (3, np.uint32), "tri_info": (4, np.int32), "bvh4": (5, np.uint32),
-                      "instances": (6, np.float32), "obj_tris": (7, np.float32)}
+                      "instances": (6, np.float32), "obj_tris": (7, np.float32),
+                      "light_tris": (8, LIGHT_TRI_DTYPE)}
 
     def scene_section(self, name):
         """One section of the committed scene blob as the kernels read it (pm_scene_section)."""
         sec, dt = self.SCENE_SECTIONS[name]
         n = ctypes.c_int64()
         self._chk(self.lib.pm_scene_section(self.h, sec, None, 0, ctypes.byref(n)))
-        out = np.zeros(n.value // 4, dtype=dt)
+        out = np.zeros(n.value // np.dtype(dt).itemsize, dtype=dt)
         if n.value:
             self._chk(self.lib.pm_scene_section(self.h, sec, out.ctypes.data, n.value, ctypes.byref(n)))
         return out

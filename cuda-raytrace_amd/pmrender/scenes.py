@@ -7,6 +7,8 @@ bit-identical inputs.
 * cornell_box: the classic 555-unit Cornell box (two blocks), ceiling disk
   area light r=65 at (278, 548.7, 279.5) facing -y, Lemit 17, pinhole
   camera at (278, 273, -800), fov 39.3 deg (C1, C2, C4).
+* cornell_quad: the same box lit by its own 130 x 105 quad light, a
+  triangle-mesh area light (scenes/cornell-box-quad.pbrt).
 * triangle_soup: Cornell enclosure + N random triangles, centres
   U[30,525]^3, edges U[-4,4]^3, Kd 0.5 (reference default matte,
   cudamaterial.cpp:40), numpy seed 1 (C3).
@@ -33,7 +35,8 @@ class Scene:
     meshes: list = field(default_factory=list)      # dict(P, idx, N, uv, material, light)
     spheres: list = field(default_factory=list)     # (r, o2w, w2o, material, light)
     disks: list = field(default_factory=list)       # (o, x, y, z, inner, phimax, material, light)
-    lights: list = field(default_factory=list)      # ("point", pos, I) | ("disk", o, p1, p2, n, Le, area, ns)
+    # ("point", pos, I) | ("disk", o, p1, p2, n, Le, area, ns) | ("mesh", P, idx, Le, ns, reverse_orientation)
+    lights: list = field(default_factory=list)
     objects: list = field(default_factory=list)     # object meshes (as meshes), placed by `instances` only
     instances: list = field(default_factory=list)   # (object index, o2w 4x4, w2o 4x4), affine
     camera: tuple = None                            # ("pinhole", eye, fwd, right, up, W, H) | ("rays", rays, rand2d, n2d)
@@ -41,6 +44,17 @@ class Scene:
     def material(self, mtype, rgb):
         self.materials.append((mtype, np.asarray(rgb, np.float32)))
         return len(self.materials) - 1
+
+    def add_mesh_light(self, P, idx, Le, nsamples=1, reverse_orientation=False, material=None):
+        """A triangle-mesh area light (pm_add_light_mesh) and its visible mesh; returns the light index.
+        It emits from the side of cross(p1 - p0, p2 - p0), the other one with reverse_orientation."""
+        if material is None:
+            material = self.material(PM_MATTE, (0.0, 0.0, 0.0))
+        P, idx = np.asarray(P, np.float32).reshape(-1, 3), np.asarray(idx, np.int32).reshape(-1, 3)
+        light_id = len(self.lights)
+        self.lights.append(("mesh", P, idx, np.asarray(Le, np.float32), int(nsamples), bool(reverse_orientation)))
+        self.meshes.append(dict(P=P, idx=idx, N=None, uv=None, material=material, light=light_id))
+        return light_id
 
     def add_quads(self, quads, material, light=-1):
         P, idx = [], []
@@ -79,6 +93,9 @@ class Scene:
         has them and `instancing`, else flattened (the CPU oracle; the A/B
         of the two-level trees) — after the meshes either way, so the global
         ids are the same."""
+        if any(L[0] == "mesh" for L in self.lights) and not hasattr(api, "add_light_mesh"):
+            raise NotImplementedError(f"{type(api).__name__} has no triangle-mesh area lights (pm_add_light_mesh); "
+                                      "only disks emit there, as in the reference")
         for mtype, rgb in self.materials:
             api.add_material(mtype, rgb)
         for m in self.meshes:
@@ -98,9 +115,12 @@ class Scene:
             api.add_sphere(r, o2w, w2o, mat, light)
         for o, x, y, z, inner, phimax, mat, light in self.disks:
             api.add_disk(o, x, y, z, inner, phimax, mat, light)
-        for L in self.lights:
+        for i, L in enumerate(self.lights):
             if L[0] == "point":
                 api.add_light_point(L[1], L[2])
+            elif L[0] == "mesh":
+                got = api.add_light_mesh(L[1], L[2], L[3], L[4], L[5])
+                assert got == i, "light indices follow the order of Scene.lights"
             else:
                 api.add_light_disk(*L[1:])
         cam = self.camera
@@ -186,6 +206,19 @@ def cornell_box(W=256, H=256, blocks=True, nsamples=1):
         ], white)
     _ceiling_light(s, nsamples=nsamples)
     s.camera = pinhole(W, H)
+    return s
+
+
+QUAD_LIGHT = [(343.0, 548.7, 227.0), (343.0, 548.7, 332.0), (213.0, 548.7, 332.0), (213.0, 548.7, 227.0)]
+
+
+def cornell_quad(W=256, H=256, blocks=True, nsamples=1, Le=17.0):
+    """The Cornell box with its own light: the 130 x 105 quad at y = 548.7 under
+    the ceiling, two triangles wound to face down (scenes/cornell-box-quad.pbrt)."""
+    s = cornell_box(W, H, blocks=blocks)
+    black = s.disks[0][6]  # the ceiling disk's black matte serves the quad
+    del s.lights[:], s.disks[:]
+    s.add_mesh_light(QUAD_LIGHT, [(0, 1, 2), (0, 2, 3)], (Le, Le, Le), nsamples, material=black)
     return s
 
 
@@ -355,6 +388,6 @@ def rays_from_pinhole(scene, jitter_seed=5):
     d = f[None, None, :] + sx[..., None] * r[None, None, :] + sy[..., None] * u[None, None, :]
     d /= np.linalg.norm(d, axis=-1, keepdims=True)
     rays = np.concatenate([np.broadcast_to(eye, d.shape), d], axis=-1).reshape(-1, 6).astype(np.float32)
-    n2d = sum(L[7] for L in scene.lights if L[0] == "disk")
+    n2d = sum(L[7] if L[0] == "disk" else L[4] for L in scene.lights if L[0] in ("disk", "mesh"))
     rand2d = rng.uniform(0, 1, size=(rays.shape[0], max(n2d, 1), 2)).astype(np.float32)
     return ("rays", rays, rand2d, max(n2d, 1))

@@ -20,6 +20,7 @@
  *   pm_add_disk                   CudaDisk::setupGeometry          util/shape/cudadisk.cpp:15-45
  *   pm_add_light_point            CudaLight::setupLight<PointLight>        util/light/cudalight.cpp:16-24
  *   pm_add_light_disk             CudaLight::setupLight<DiffuseAreaLight>  util/light/cudalight.cpp:26-59
+ *   pm_add_light_mesh             (new: the reference emits from disks only, cudalight.cpp:35-56)
  *   pm_set_eye_rays               PbrtCamera::preLaunch (bRays, bRandom2D) util/camera/pbrtcamera.cpp:57-122
  *   pm_set_pinhole                (on-device eye rays for synthetic benches)
  *   pm_commit                     CudaRender::Render → assembleNode (Sbvh build)  cudarender.cpp:38-75,112-123
@@ -56,6 +57,8 @@ extern "C" {
 /* CudaLightDevice::LightType, util/common.cu.h:48 */
 #define PM_LIGHT_POINT 1
 #define PM_LIGHT_AREA_DISK 3
+/* ours (the reference's enum ends at 3): a triangle mesh that emits, pm_add_light_mesh */
+#define PM_LIGHT_AREA_MESH 4
 /* RayTracingRecord flags, photon_mapping/photonmapping.h:25-26 (+ INVALID for padding) */
 #define PM_REC_EXCEPTION 0x01u
 #define PM_REC_MISS 0x02u
@@ -197,6 +200,22 @@ int pm_add_light_point(void *ctx, const float pos[3], const float intensity[3]);
  * n normal, Le emitted radiance, area, n_samples shadow samples. */
 int pm_add_light_disk(void *ctx, const float o[3], const float p1[3], const float p2[3],
                       const float n[3], const float Le[3], float area, int n_samples);
+/* Triangle-mesh area light (pbrt's DiffuseAreaLight over a trianglemesh; the
+ * reference has none). World-space vertices and indices as pm_add_trimesh;
+ * only the emitter is created here: the caller adds the visible geometry with
+ * pm_add_trimesh(..., light_index = *out_light) from the same arrays, as
+ * pm_add_disk pairs with pm_add_light_disk. Triangle k emits from the side of
+ * normalize(cross(p1 - p0, p2 - p0)), negated when reverse_orientation is set.
+ * A point is drawn by area: per-triangle areas 0.5 |cross(p1 - p0, p2 - p0)|
+ * in double from the float vertices, running sum in double in index order,
+ * cdf[k] = (float)(sum[k] / sum[n - 1]), cdf[n - 1] = 1; the sample picks the
+ * first k with cdf[k] > min(u, 1 - 2^-24) (a zero-area triangle is never picked), remaps u
+ * into the bin and places the point with pbrt's UniformSampleTriangle as
+ * p0 + b1 (p1 - p0) + (1 - b0 - b1) (p2 - p0). n_samples 2-D randoms are
+ * registered as for the disk light. PM_ERR_INVALID: a null pointer,
+ * ntris <= 0, an index out of range, a total area of 0 or not finite. */
+int pm_add_light_mesh(void *ctx, const float *P, int nverts, const int *indices, int ntris,
+                      int reverse_orientation, const float Le[3], int n_samples, int *out_light);
 
 /* Eye samples. Either a pinhole camera evaluated on the device (records in
  * 8x8-pixel tile order, output in raster order) ... */
@@ -348,6 +367,9 @@ int pm_scene_info(void *ctx, int64_t out[7]);
 #define PM_SCENE_BVH4 5
 #define PM_SCENE_INSTANCES 6 /* 128 B per instance (pm_device.h SceneDev::insts) */
 #define PM_SCENE_OBJ_TRIS 7  /* 48 B per stored object triangle (object-space p0, p1, p2) */
+/* 64 B per emitting triangle, mesh lights in light order: (p0, cdf[k]) (p1 - p0, 0)
+ * (p2 - p0, 0) (emitting-side unit normal, 0); pm_device.h SceneDev::light_tris */
+#define PM_SCENE_LIGHT_TRIS 8
 int pm_scene_section(void *ctx, int section, void *out, int64_t max_bytes, int64_t *bytes);
 /* the current photon map (pm_build_photon_map; the reference's
  * CreatePhotonMap, photonmappingrenderer.cpp:150-180): [0] structure
