@@ -1088,6 +1088,9 @@ int pm_set_pinhole(void *ptr, const float eye[3], const float fwd[3], const floa
     GROUP_FWD(ptr, pm_set_pinhole(sub, eye, fwd, right, up, W, H));
     GETCTX(ptr);
     if (W <= 0 || H <= 0 || !eye || !fwd || !right || !up) FAIL(c, PM_ERR_INVALID, "bad pinhole camera");
+    for (int a = 0; a < 3; ++a)
+        if (!(fabsf(eye[a]) <= PM_MAX_RAY_ORIGIN) || !std::isfinite(fwd[a]) || !std::isfinite(right[a]) || !std::isfinite(up[a]))
+            FAIL(c, PM_ERR_INVALID, "pinhole camera: eye beyond 2^20 or a non-finite vector");
     c->pinhole = 1; c->W = W; c->H = H;
     std::memcpy(c->eye, eye, 12); std::memcpy(c->fwd, fwd, 12);
     std::memcpy(c->right, right, 12); std::memcpy(c->up, up, 12);
@@ -1098,6 +1101,11 @@ int pm_set_eye_rays(void *ptr, const float *rays, int64_t nrays, const float *ra
     GROUP_FWD(ptr, pm_set_eye_rays(sub, rays, nrays, rand2d, n2d));
     GETCTX(ptr);
     if (!rays || nrays <= 0) FAIL(c, PM_ERR_INVALID, "no rays");
+    /* the traversal modes agree bit for bit for finite rays with |o| <= 2^20 (pm_device.h box_near) */
+    for (int64_t i = 0; i < nrays; ++i)
+        for (int a = 0; a < 3; ++a)
+            if (!(fabsf(rays[6 * i + a]) <= PM_MAX_RAY_ORIGIN) || !std::isfinite(rays[6 * i + 3 + a]))
+                FAIL(c, PM_ERR_INVALID, "ray %lld: origin beyond 2^20 or a non-finite component", (long long)i);
     c->pinhole = 0;
     c->nrays = nrays;
     c->rays.assign(rays, rays + 6 * nrays);

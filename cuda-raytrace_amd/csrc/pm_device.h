@@ -360,9 +360,18 @@ PMD bool isect_sphere(const float4 *s, const Ray &ray, float *thit) {
 /* ---------------------------------------------------------- traversal */
 /* Slab test of one child box; returns tnear (inf = miss). */
 /* t = (plane - o) / d as one FMA, plane * inv - o * inv (oinv precomputed per
- * ray). The slab test only culls: its error is about one ulp of the
- * coordinates, and every primitive box is padded by 1e-4 of its coordinate
- * magnitude at commit (thousands of ulps), so no box holding a hit is culled. */
+ * ray). The slab test only culls, and it must never cull a box holding a hit
+ * the triangle test accepts. Its error has two parts: a few ulps of the plane
+ * coordinate, which the commit pad of every primitive box (1e-4 max(1,
+ * |coordinate|), thousands of ulps of it) covers, and a few ulps of o * inv,
+ * i.e. of the ray's *origin*, which that pad does not scale with: from an
+ * origin 1e4 away an ulp of o is 1e-3, ten times the pad of a unit-sized
+ * scene. The second part is covered per ray: ray_oinv() / ray_oinv_hi() widen every box by
+ * pad = 2^-20 max|o| (16 ulps of the origin; the FMA, the product o * inv and
+ * the <= 1 ulp reciprocal together stay below 4) through the two offsets
+ * oinv = (o + pad) * inv for the low planes and oinvH = (o - pad) * inv for
+ * the high ones, at no cost per box. Tested for |o| <= 2^20, the bound
+ * pm_set_eye_rays and pm_set_pinhole hold eye rays to. */
 /* slab test; oinvH (default oinv) offsets the high planes: an instance tree
  * widens every box by a pad with oinv = (o' + pad) * inv, oinvH = (o' - pad)
  * * inv at no cost per box (blas_isect) */
@@ -385,10 +394,32 @@ PMD v3 safe_inv(v3 d) {
     float x = fabsf(d.x) < tiny ? copysignf(tiny, d.x) : d.x;
     float y = fabsf(d.y) < tiny ? copysignf(tiny, d.y) : d.y;
     float z = fabsf(d.z) < tiny ? copysignf(tiny, d.z) : d.z;
-    /* hardware reciprocal (<= 1 ulp): the slab test only culls, and every
-     * prim box is padded by 1e-4 relative at commit, so an ulp in 1/d never
+    /* hardware reciprocal (<= 1 ulp): the slab test only culls; an ulp in 1/d
+     * moves t = (plane - o) / d by an ulp of the plane and of the origin,
+     * which the commit pad and the per-ray pad (ray_pad2) cover, so it never
      * drops a box holding the closest hit (which is order-independent) */
     return mk(__builtin_amdgcn_rcpf(x), __builtin_amdgcn_rcpf(y), __builtin_amdgcn_rcpf(z));
+}
+/* the per-ray box pad (box_near's comment): 2 * 2^-20 max|o| */
+PMD float ray_pad2(v3 o) { return 0x1p-19f * fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z))); }
+/* oinv = (o + pad) * inv, the low planes' offset */
+PMD v3 ray_oinv(v3 o, v3 inv, float pad2) {
+    const float pad = 0.5f * pad2;
+    return mk((o.x + pad) * inv.x, (o.y + pad) * inv.y, (o.z + pad) * inv.z);
+}
+/* oinvH = (o - pad) * inv = oinv - 2 pad inv, the high planes' offset. Built
+ * anew at every node visit (a v_max3, a multiply and these three FMAs) and not
+ * kept: three more live registers across the walk cost k_eye a wave of
+ * occupancy and the pooled trace kernel scratch; the empty asm keeps the
+ * compiler from hoisting it out of the walk's loop again. What it protects
+ * (gfx950, `make resources`): k_trace_pool<0,0> / <0,1> 96 VGPRs with 28 /
+ * 108 B of scratch, k_trace_pool8<0,0> 102 VGPRs, k_eye<MODE_GLOBAL> 125
+ * VGPRs at 4 waves (kept hoisted: 129 at 3 waves; k_trace_pool<0,0> 52 B
+ * of scratch). If a compiler changes these, re-measure before keeping it. */
+PMD v3 ray_oinv_hi(v3 oinv, v3 inv, v3 o) {
+    float pad2 = ray_pad2(o);
+    asm volatile("" : "+v"(pad2));
+    return mk(__builtin_fmaf(-pad2, inv.x, oinv.x), __builtin_fmaf(-pad2, inv.y, oinv.y), __builtin_fmaf(-pad2, inv.z, oinv.z));
 }
 
 /* per-lane traversal census (bench roofline / DESIGN.md): nodes entered and
@@ -615,7 +646,7 @@ PMD bool traverse(const SceneDev &S, const Ray &ray, Hit &best, int *stack, int 
     best.gid = 0xffffffffu;
     best.ref = 0xffffffffu;
     const v3 inv = safe_inv(ray.d);
-    const v3 oinv = mk(ray.o.x * inv.x, ray.o.y * inv.y, ray.o.z * inv.z);
+    const v3 oinv = ray_oinv(ray.o, inv, ray_pad2(ray.o));
     int sp = 0;
     int cur = 0; /* next node to enter; -1: none left */
     /* Leaves found while descending are postponed (at most the two children of
@@ -643,8 +674,9 @@ PMD bool traverse(const SceneDev &S, const Ray &ray, Hit &best, int *stack, int 
             const float4 *nd = S.nodes + 4 * cur;
             float4 a = nd[0], b = nd[1], c = nd[2];
             int4 ch = *reinterpret_cast<const int4 *>(nd + 3);
-            float tl = box_near(a.x, a.y, a.z, a.w, b.x, b.y, oinv, inv, ray.tmin, best.t);
-            float tr = box_near(b.z, b.w, c.x, c.y, c.z, c.w, oinv, inv, ray.tmin, best.t);
+            const v3 oinvH = ray_oinv_hi(oinv, inv, ray.o);
+            float tl = box_near(a.x, a.y, a.z, a.w, b.x, b.y, oinv, inv, ray.tmin, best.t, oinvH);
+            float tr = box_near(b.z, b.w, c.x, c.y, c.z, c.w, oinv, inv, ray.tmin, best.t, oinvH);
             bool hl = tl != __int_as_float(0x7f800000) && ch.z >= 0;
             bool hr = tr != __int_as_float(0x7f800000) && ch.w >= 0;
             if (hl && ch.x < 0) { l0s = (uint32_t)~ch.x; l0n = (uint32_t)ch.z; hl = false; }
@@ -723,9 +755,10 @@ PMD void node4_decode(const uint4 w0, const uint4 w1, const uint4 w2, const uint
         /* the plane o + q 2^e and the slab (plane - O) / d folded: t = q a + b
          * with a = 2^e / d, b = o / d - O / d per node, one FMA per plane
          * instead of a decode FMA and a slab FMA. Not the decoded plane's t
-         * bit for bit, but within a few ulps of the coordinates, far inside
-         * the 1e-4 relative pad of every primitive box (culling stays
-         * conservative; closest hits do not depend on it) */
+         * bit for bit, but within a few ulps of the plane coordinate (inside
+         * the commit pad of every primitive box) and of the ray's origin
+         * (inside the per-ray pad carried by oinv / oinvH, see box_near):
+         * culling stays conservative; closest hits do not depend on it */
         const float ax = sx * inv.x, ay = sy * inv.y, az = sz * inv.z;
         const float bx = __builtin_fmaf(ox, inv.x, -oinv.x), by = __builtin_fmaf(oy, inv.y, -oinv.y),
                     bz = __builtin_fmaf(oz, inv.z, -oinv.z);
@@ -779,7 +812,7 @@ PMD bool traverse4(const SceneDev &S, const Ray &ray, Hit &best, int *stack, int
     best.gid = 0xffffffffu;
     best.ref = 0xffffffffu;
     const v3 inv = safe_inv(ray.d);
-    const v3 oinv = mk(ray.o.x * inv.x, ray.o.y * inv.y, ray.o.z * inv.z);
+    const v3 oinv = ray_oinv(ray.o, inv, ray_pad2(ray.o));
     int sp = 0;
     int cur = 0;
     uint32_t l0s = 0, l0n = 0, l1s = 0, l1n = 0, l2s = 0, l2n = 0, l3s = 0, l3n = 0;
@@ -791,7 +824,7 @@ PMD bool traverse4(const SceneDev &S, const Ray &ray, Hit &best, int *stack, int
             cen.node();
             float t[4];
             int c[4], n[4];
-            node4_test(S, cur, oinv, inv, ray.tmin, best.t, t, c, n);
+            node4_test(S, cur, oinv, inv, ray.tmin, best.t, t, c, n, ray_oinv_hi(oinv, inv, ray.o));
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (t[k] != INF && n[k] > 0) { /* leaf: postpone */
@@ -934,7 +967,7 @@ PMD bool blas_isect(const SceneDev &S, uint32_t inst, const Ray &ray, Hit &best,
  * trav_step advances by one node visit or one leaf; the result equals
  * traverse4's (same culling, same leaf tests, same tie-break). */
 struct TravState {
-    v3 inv, oinv;
+    v3 inv, oinv; /* oinv: the low planes' offset (ray_oinv); the high planes' is rebuilt per visit */
     Hit best;
     int cur, sp, guard;
     uint32_t l0s, l0n, l1s, l1n, l2s, l2n, l3s, l3n;
@@ -945,7 +978,7 @@ PMD void trav_begin(const Ray &ray, TravState &t) {
     t.best.ref = 0xffffffffu;
     t.best.beta = t.best.gamma = 0.f;
     t.inv = safe_inv(ray.d);
-    t.oinv = mk(ray.o.x * t.inv.x, ray.o.y * t.inv.y, ray.o.z * t.inv.z);
+    t.oinv = ray_oinv(ray.o, t.inv, ray_pad2(ray.o));
     t.cur = 0; t.sp = 0; t.guard = 0;
     t.l0n = t.l1n = t.l2n = t.l3n = 0;
     t.l0s = t.l1s = t.l2s = t.l3s = 0;
@@ -998,7 +1031,7 @@ PMD bool trav_step(const SceneDev &S, const Ray &ray, TravState &T, const SpillS
     const float INF = __int_as_float(0x7f800000);
     float t[4];
     int c[4], n[4];
-    node4_test(S, T.cur, T.oinv, T.inv, ray.tmin, T.best.t, t, c, n);
+    node4_test(S, T.cur, T.oinv, T.inv, ray.tmin, T.best.t, t, c, n, ray_oinv_hi(T.oinv, T.inv, ray.o));
 #if PM_LEAFQ_SHIFT
     /* the pending-leaf queue is empty here (a visit follows the last pending
      * leaf's test): the hit leaves, in child order, enter it by shifting from
@@ -1051,7 +1084,7 @@ PMD bool trav_step(const SceneDev &S, const Ray &ray, TravState &T, const SpillS
  * C3's soup (tools/bvh_width_sim.cpp: 30.1 -> 20.1), each a dependent fetch. */
 constexpr int BVH8_EMPTY = (int)0x80000000;
 PMD void node8_test(const SceneDev &S, int cur, const v3 &oinv, const v3 &inv, float tmin, float tmax, float t[8],
-                    int c[8]) {
+                    int c[8], const v3 &oinvH) {
     const uint4 *nd = reinterpret_cast<const uint4 *>(S.wnodes) + 8 * cur;
     const uint4 w0 = nd[0], w1 = nd[1], w2 = nd[2], w3 = nd[3], w4 = nd[4], w5 = nd[5];
     const float ox = __uint_as_float(w0.x), oy = __uint_as_float(w0.y), oz = __uint_as_float(w0.z);
@@ -1062,6 +1095,8 @@ PMD void node8_test(const SceneDev &S, int cur, const v3 &oinv, const v3 &inv, f
     const float ax = sx * inv.x, ay = sy * inv.y, az = sz * inv.z;
     const float bx = __builtin_fmaf(ox, inv.x, -oinv.x), by = __builtin_fmaf(oy, inv.y, -oinv.y),
                 bz = __builtin_fmaf(oz, inv.z, -oinv.z);
+    const float bxH = __builtin_fmaf(ox, inv.x, -oinvH.x), byH = __builtin_fmaf(oy, inv.y, -oinvH.y),
+                bzH = __builtin_fmaf(oz, inv.z, -oinvH.z);
     /* byte planes: lo x (w1.x, w1.y), lo y (w1.z, w1.w), lo z (w2.x, w2.y),
      * hi x (w2.z, w2.w), hi y (w3.x, w3.y), hi z (w3.z, w3.w) */
     const uint32_t LX[2] = {w1.x, w1.y}, LY[2] = {w1.z, w1.w}, LZ[2] = {w2.x, w2.y};
@@ -1075,9 +1110,9 @@ PMD void node8_test(const SceneDev &S, int cur, const v3 &oinv, const v3 &inv, f
         const float t0x = __builtin_fmaf((float)((LX[h] >> sh) & 0xffu), ax, bx);
         const float t0y = __builtin_fmaf((float)((LY[h] >> sh) & 0xffu), ay, by);
         const float t0z = __builtin_fmaf((float)((LZ[h] >> sh) & 0xffu), az, bz);
-        const float t1x = __builtin_fmaf((float)((HX[h] >> sh) & 0xffu), ax, bx);
-        const float t1y = __builtin_fmaf((float)((HY[h] >> sh) & 0xffu), ay, by);
-        const float t1z = __builtin_fmaf((float)((HZ[h] >> sh) & 0xffu), az, bz);
+        const float t1x = __builtin_fmaf((float)((HX[h] >> sh) & 0xffu), ax, bxH);
+        const float t1y = __builtin_fmaf((float)((HY[h] >> sh) & 0xffu), ay, byH);
+        const float t1z = __builtin_fmaf((float)((HZ[h] >> sh) & 0xffu), az, bzH);
         const float tn = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fmaxf(fminf(t0z, t1z), tmin));
         const float tf = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fminf(fmaxf(t0z, t1z), tmax));
         t[k] = tn <= tf && c[k] != BVH8_EMPTY ? tn : __int_as_float(0x7f800000);
@@ -1113,11 +1148,11 @@ PMD int child8(const int c[8], uint32_t slot) { /* c[slot & 7] by selects (no dy
  * lane's, in one pass of the wave), the hit internal children sorted, the
  * nearest returned in `next` (-1: none) and the others pushed far to near */
 template <bool ANY, class C, class Put>
-PMD bool visit8(const SceneDev &S, int node, const Ray &ray, const v3 &oinv, const v3 &inv, Hit &best, C &cen, int &next,
-                Put &&stack_put) {
+PMD bool visit8(const SceneDev &S, int node, const Ray &ray, const v3 &oinv, const v3 &inv, const v3 &oinvH, Hit &best,
+                C &cen, int &next, Put &&stack_put) {
     float t[8];
     int c[8];
-    node8_test(S, node, oinv, inv, ray.tmin, best.t, t, c);
+    node8_test(S, node, oinv, inv, ray.tmin, best.t, t, c, oinvH);
     const float INF = __int_as_float(0x7f800000);
     uint32_t key[8], lm = 0u;
 #pragma unroll
@@ -1148,13 +1183,13 @@ PMD bool traverse8(const SceneDev &S, const Ray &ray, Hit &best, int *stack, int
     best.gid = 0xffffffffu;
     best.ref = 0xffffffffu;
     const v3 inv = safe_inv(ray.d);
-    const v3 oinv = mk(ray.o.x * inv.x, ray.o.y * inv.y, ray.o.z * inv.z);
+    const v3 oinv = ray_oinv(ray.o, inv, ray_pad2(ray.o));
     int sp = 0, cur = 0, guard = 0;
     while (cur >= 0 && guard <= S.n_nodes) {
         ++guard;
         cen.node();
         int next = -1;
-        if (visit8<ANY>(S, cur, ray, oinv, inv, best, cen, next, [&](int v) { stack[sp * stride] = v; ++sp; }))
+        if (visit8<ANY>(S, cur, ray, oinv, inv, ray_oinv_hi(oinv, inv, ray.o), best, cen, next, [&](int v) { stack[sp * stride] = v; ++sp; }))
             return true;
         if (next >= 0) cur = next;
         else if (sp > 0) { --sp; cur = stack[sp * stride]; }
@@ -1176,7 +1211,7 @@ PMD void trav_begin(const Ray &ray, TravState8 &t) {
     t.best.ref = 0xffffffffu;
     t.best.beta = t.best.gamma = 0.f;
     t.inv = safe_inv(ray.d);
-    t.oinv = mk(ray.o.x * t.inv.x, ray.o.y * t.inv.y, ray.o.z * t.inv.z);
+    t.oinv = ray_oinv(ray.o, t.inv, ray_pad2(ray.o));
     t.cur = 0; t.sp = 0; t.guard = 0;
 }
 template <class C>
@@ -1185,7 +1220,8 @@ PMD bool trav_step(const SceneDev &S, const Ray &ray, TravState8 &T, const Spill
     ++T.guard;
     cen.node();
     int next = -1;
-    visit8<false>(S, T.cur, ray, T.oinv, T.inv, T.best, cen, next, [&](int v) { stk.put(T.sp, v); ++T.sp; });
+    visit8<false>(S, T.cur, ray, T.oinv, T.inv, ray_oinv_hi(T.oinv, T.inv, ray.o), T.best, cen, next,
+                  [&](int v) { stk.put(T.sp, v); ++T.sp; });
     if (next >= 0) T.cur = next;
     else if (T.sp > 0) { --T.sp; T.cur = stk.get(T.sp); }
     else T.cur = -1;

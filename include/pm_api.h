@@ -217,6 +217,18 @@ int pm_add_light_disk(void *ctx, const float o[3], const float p1[3], const floa
 int pm_add_light_mesh(void *ctx, const float *P, int nverts, const int *indices, int ntris,
                       int reverse_orientation, const float Le[3], int n_samples, int *out_light);
 
+/* The largest |component| of an eye-ray origin (2^20). Up to it every
+ * traversal mode returns the same hit bit for bit for any finite eye ray
+ * (tested to that bound, tests/test_ray_query_gpu.py); far beyond it an ulp
+ * of the origin exceeds the triangles and the triangle test itself accepts
+ * hits that lie in no box. Both calls below return PM_ERR_INVALID for an
+ * origin beyond it and for a non-finite origin or direction. The guarantee
+ * covers eye rays only, in scenes that themselves lie within the bound:
+ * light positions (the origins of photon and shadow rays) and geometry are
+ * not checked, and rays that start on surfaces or lights beyond 2^20 are
+ * outside what was tested. */
+#define PM_MAX_RAY_ORIGIN 1048576.0f
+
 /* Eye samples. Either a pinhole camera evaluated on the device (records in
  * 8x8-pixel tile order, output in raster order) ... */
 int pm_set_pinhole(void *ctx, const float eye[3], const float fwd[3], const float right[3],
