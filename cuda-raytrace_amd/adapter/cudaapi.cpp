@@ -142,6 +142,8 @@ void CudaRender::createSubRenderer(Sampler *sampler, Camera *camera, const Param
     s.params.paths_per_pass = params.FindOneInt("photonpaths", (int)s.params.paths_per_pass);
     s.params.passes = params.FindOneInt("passes", s.params.passes);
     if (params.FindOneString("photonmap", "grid") == "kdtree") s.params.gather_structure = PM_GATHER_KDTREE;
+    /* the light the photon paths start on; -1 (PM_ALL_LIGHTS): every light, picked per path by power */
+    s.params.light_source_index = params.FindOneInt("lightsource", s.params.light_source_index);
     impl_.createSubRenderer(s, rendername);
 }
 

@@ -268,6 +268,17 @@ struct PbrtParser::Impl {
     bool have_camera = false;
     ParamSet camera_params;
     int xres = 640, yres = 480; /* pbrt-v2 ImageFilm defaults */
+    int lightsource_line = 0;   /* where the Renderer directive set "lightsource" (0: it did not) */
+    std::string lightsource_file;
+
+    /* after the whole scene: "lightsource" must name one of its lights (or every light) */
+    void check_lightsource() const {
+        const int k = opts->settings.params.light_source_index;
+        if (lightsource_line == 0 || k == PM_ALL_LIGHTS || (k >= 0 && (size_t)k < opts->lights.size())) return;
+        throw Error(lightsource_file + ":" + std::to_string(lightsource_line) + ": Renderer \"lightsource\" " +
+                    std::to_string(k) + " out of range: the scene has " + std::to_string(opts->lights.size()) +
+                    " lights (valid: -1 for every light, or 0 .. " + std::to_string((long long)opts->lights.size() - 1) + ")");
+    }
 
     Impl() {
         materials.push_back(Material{Material::Matte, {0.5f, 0.5f, 0.5f}}); /* pbrt default "matte" Kd 0.5 */
@@ -541,6 +552,23 @@ struct PbrtParser::Impl {
                 p.passes = ps.oneInt("passes", p.passes);
                 const std::string g = ps.oneString("gather", "grid");
                 p.gather_structure = g == "kdtree" || g == "kd" ? PM_GATHER_KDTREE : PM_GATHER_GRID;
+                /* the light the photon paths start on: "integer lightsource" [k],
+                 * -1 (PM_ALL_LIGHTS) or "string lightsource" "all" for every
+                 * light; checked against the scene's lights once it is parsed */
+                if (const Param *ls = ps.find("lightsource")) {
+                    if (!ls->strs.empty()) {
+                        if (ls->strs[0] != "all")
+                            lx.fail(line, "Renderer \"lightsource\": \"%s\" is not \"all\" or a light index", ls->strs[0].c_str());
+                        p.light_source_index = PM_ALL_LIGHTS;
+                    } else if (!ls->nums.empty()) {
+                        const double v = ls->nums[0];
+                        if (!(v >= -1.0 && v <= 2147483647.0) || v != std::floor(v))
+                            lx.fail(line, "Renderer \"lightsource\" %g: expected a light index >= 0, or -1 for every light", v);
+                        p.light_source_index = (int)v;
+                    }
+                    lightsource_line = line;
+                    lightsource_file = lx.file();
+                }
             } else if (d == "Sampler" || d == "PixelFilter" || d == "SurfaceIntegrator" || d == "VolumeIntegrator" ||
                        d == "Accelerator" || d == "Volume") {
                 str(lx);
@@ -647,6 +675,7 @@ void PbrtParser::parseFile(const std::string &path, PbrtSink &sink, PbrtOptions 
     impl_->sink = &sink;
     impl_->opts = &opts;
     impl_->parse_file(path);
+    impl_->check_lightsource();
 }
 
 void PbrtParser::parseString(const std::string &text, PbrtSink &sink, PbrtOptions &opts, const std::string &dir) {
@@ -654,6 +683,7 @@ void PbrtParser::parseString(const std::string &text, PbrtSink &sink, PbrtOption
     impl_->opts = &opts;
     Lexer lx(text, "<string>");
     impl_->parse(lx, dir);
+    impl_->check_lightsource();
 }
 
 } // namespace pmcuda

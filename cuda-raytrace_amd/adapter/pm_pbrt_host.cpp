@@ -16,6 +16,10 @@
  * usage: pm_pbrt_host --out f.bin [--width W --height H --paths N
  *        --photonmap grid|kdtree --renderer photonmap|simple --nsamples S --instanced
  *        --quad-light]   (the box's own 130 x 105 quad light, a trianglemesh, instead of the disk)
+ *        [--two-lights]  (scenes/cornell-two-lights.pbrt: the disk, then a blue quad light on the green wall)
+ *        [--lightsource K]  (Renderer "cuda" "integer lightsource" [K]; -1: photons from every light)
+ * The header's third word is the number of light 2D samples per ray
+ * (nsamples per area light).
  */
 #include <cmath>
 #include <cstdio>
@@ -35,7 +39,9 @@ namespace {
 struct Opts {
     int W = 64, H = 48, paths = 16384, nsamples = 1;
     std::string photonmap = "grid", renderer = "photonmap", out;
-    bool instanced = false, quad_light = false;
+    bool instanced = false, quad_light = false, two_lights = false;
+    int lightsource = 0;
+    bool lightsource_set = false;
 };
 
 /* pixel centres in raster order, one sample per pixel; light 2D randoms:
@@ -186,19 +192,30 @@ int run(const Opts &o) {
     Scene scene;
     scene.lights.push_back(area);
     CreateCudaShape(o.quad_light ? "trianglemesh" : "disk", emitter, NULL, black.GetPtr(), 0);
+    /* --two-lights (scenes/cornell-two-lights.pbrt): AreaLightSource "diffuse"
+     * "rgb L" [4 8 20] on a quad just off the green wall, wound to face +x */
+    DiffuseAreaLight *area2 = NULL;
+    if (o.two_lights) {
+        Reference<Shape> wallq = quads(&identity, {{1, 200, 230, 1, 300, 230, 1, 300, 330, 1, 200, 330}});
+        const float Le2[3] = {4.f, 8.f, 20.f};
+        area2 = new DiffuseAreaLight(identity, RGBSpectrum::FromRGB(Le2, SPECTRUM_ILLUMINANT), o.nsamples, wallq);
+        scene.lights.push_back(area2);
+        CreateCudaShape("trianglemesh", wallq, NULL, black.GetPtr(), 1);
+    }
     /* MakeRenderer: Renderer "cuda" */
     KeepFilm *film = new KeepFilm(o.W, o.H);
     RecordingCamera *camera = new RecordingCamera(film, o.W, o.H);
     ParamSet params; /* Renderer "cuda" "integer photonpaths" [N] "string photonmap" [...] */
     params.AddInt("photonpaths", &o.paths, 1);
     params.AddString("photonmap", &o.photonmap, 1);
+    if (o.lightsource_set) params.AddInt("lightsource", &o.lightsource, 1);
     CentreSampler *sampler = new CentreSampler(o.W, o.H);
     Renderer *renderer = CreateCudaRenderer(sampler, camera, params, o.renderer == "simple" ? "simple" : "photonmap");
     /* pbrtWorldEnd */
     renderer->Render(&scene);
     FILE *f = std::fopen(o.out.c_str(), "wb");
     if (!f) { std::perror("fopen"); return 2; }
-    const int hdr[4] = {o.W, o.H, o.nsamples, (int)film->written};
+    const int hdr[4] = {o.W, o.H, o.nsamples * (o.two_lights ? 2 : 1), (int)film->written};
     std::fwrite(hdr, sizeof hdr, 1, f);
     std::fwrite(camera->rays.data(), sizeof(float), camera->rays.size(), f);
     std::fwrite(sampler->rand2d.data(), sizeof(float), sampler->rand2d.size(), f);
@@ -207,6 +224,7 @@ int run(const Opts &o) {
     std::printf("pm_pbrt_host: %ld samples added, image written %d time(s)\n", film->added, film->written);
     delete renderer; /* pbrt deletes its Renderer */
     delete area;
+    delete area2;
     return 0;
 }
 
@@ -225,6 +243,8 @@ int main(int argc, char **argv) {
         else if (a == "--renderer") o.renderer = val();
         else if (a == "--instanced") o.instanced = true;
         else if (a == "--quad-light") o.quad_light = true;
+        else if (a == "--two-lights") o.two_lights = true;
+        else if (a == "--lightsource") { o.lightsource = std::stoi(val()); o.lightsource_set = true; }
         else if (a == "--out") o.out = val();
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }

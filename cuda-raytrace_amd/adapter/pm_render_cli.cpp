@@ -8,10 +8,14 @@
  *
  *   pm_render_cli --scene cornell --width W --height H --camera e0 e1 e2 f0 f1 f2 r0 r1 r2 u0 u1 u2
  *                 [--paths N] [--passes P] [--structure grid|kd] [--instanced]
- *                 [--renderer photonmapping|simple] --out img.pfm
+ *                 [--renderer photonmapping|simple] [--light N|all] --out img.pfm
  *   pm_render_cli --pbrt scene.pbrt [--out img.pfm] [--renderer R] [--paths N] [--passes P] [--structure S]
+ *                 [--light N|all]
  *                 (a pbrt-v2 scene file through pm_pbrt.h; command-line options override the file)
- *   pm_render_cli --pbrt scene.pbrt --dump   (parse only, no device: the plugin calls as JSON)
+ *   pm_render_cli --pbrt scene.pbrt --dump   (parse only, no device: the plugin calls as JSON, with the
+ *                 renderer's light_source_index and the scene's light selection table)
+ * --light: the light the photon paths start on; "all" (or -1) starts them on
+ * every light, picked per path by emitted power (PM_ALL_LIGHTS).
  *   pm_render_cli --selftest      (host-only checks, no device needed)
  */
 #include <cmath>
@@ -189,6 +193,27 @@ struct DumpSink : PbrtSink {
     }
 };
 
+/* the area pm_commit's selection table sees for an area light: the disk's as
+ * CudaRender::addLights passes it (pbrt Disk::Area), the mesh's as
+ * pm_add_light_mesh sums it (per-triangle areas in double, in index order) */
+float lightArea(const Light &L) {
+    if (L.kind != Light::AreaMesh) {
+        const float r = L.disk.radius, ri = L.disk.inner_radius;
+        return L.disk.phi_max * 0.5f * (r * r - ri * ri);
+    }
+    double total = 0.0;
+    const std::vector<float> &P = L.mesh.P;
+    for (size_t t = 0; t + 2 < L.mesh.indices.size(); t += 3) {
+        const float *p0 = &P[3 * (size_t)L.mesh.indices[t]], *p1 = &P[3 * (size_t)L.mesh.indices[t + 1]],
+                    *p2 = &P[3 * (size_t)L.mesh.indices[t + 2]];
+        const double a[3] = {(double)p1[0] - p0[0], (double)p1[1] - p0[1], (double)p1[2] - p0[2]};
+        const double b[3] = {(double)p2[0] - p0[0], (double)p2[1] - p0[1], (double)p2[2] - p0[2]};
+        const double n[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+        total += 0.5 * std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    }
+    return (float)total;
+}
+
 int dump(const std::string &path) {
     DumpSink sink;
     PbrtOptions o;
@@ -237,16 +262,48 @@ int dump(const std::string &path) {
     DumpSink::arr(cam, c.right, 3); cam += ", \"up\": ";
     DumpSink::arr(cam, c.up, 3);
     const pm_render_params &p = o.settings.params;
+    /* the light selection table of PM_ALL_LIGHTS as pm_commit would build it
+     * (host only); [] for a scene that emits nothing */
+    std::string cdf = "[";
+    {
+        std::vector<int> types;
+        std::vector<float> rgb, areas, table(o.lights.size());
+        for (const Light &L : o.lights) {
+            const RGB c = L.kind == Light::Point ? L.intensity : L.Lemit;
+            types.push_back(L.kind == Light::Point ? PM_LIGHT_POINT : L.kind == Light::AreaMesh ? PM_LIGHT_AREA_MESH : PM_LIGHT_AREA_DISK);
+            rgb.push_back(c.r); rgb.push_back(c.g); rgb.push_back(c.b);
+            areas.push_back(L.kind == Light::Point ? 0.f : lightArea(L));
+        }
+        if (!o.lights.empty() &&
+            pm_light_selection_cdf(types.data(), rgb.data(), areas.data(), (int)types.size(), table.data()) == PM_OK) {
+            cdf.clear();
+            DumpSink::arr(cdf, table.data(), table.size());
+            cdf.pop_back();
+        }
+    }
     std::printf("%s},\n\"renderer\": \"%s\", \"paths\": %lld, \"passes\": %d, \"gather\": %d, \"film\": \"%s\", "
-                "\"warnings\": %d}\n",
+                "\"light_source_index\": %d, \"light_cdf\": %s], \"warnings\": %d}\n",
                 cam.c_str(), o.renderer.c_str(), (long long)p.paths_per_pass, p.passes, p.gather_structure,
-                o.film_filename.c_str(), o.warnings);
+                o.film_filename.c_str(), p.light_source_index, cdf.c_str(), o.warnings);
     return 0;
 }
 
 /* a .pbrt scene through the plugin surface, as pbrt-v2 + the reference would run it */
+/* --light N|all: the light the photon paths start on (all: PM_ALL_LIGHTS) */
+int parse_light(const std::string &v) {
+    if (v == "all") return PM_ALL_LIGHTS;
+    char *end = nullptr;
+    const long k = std::strtol(v.c_str(), &end, 10);
+    if (v.empty() || *end || k < -1 || k > 2147483647L) throw Error("--light " + v + ": expected a light index, -1 or \"all\"");
+    return (int)k;
+}
+void check_light(int k, size_t n_lights) {
+    if (k != PM_ALL_LIGHTS && (k < 0 || (size_t)k >= n_lights))
+        throw Error("--light " + std::to_string(k) + " out of range: the scene has " + std::to_string(n_lights) + " lights");
+}
+
 int render_pbrt(const std::string &path, std::string out, const std::string &renderer, long long paths, int passes,
-                const std::string &structure) {
+                const std::string &structure, const std::string &light) {
     CudaRenderInit(0);
     PbrtOptions o;
     CudaApiSink sink;
@@ -257,6 +314,7 @@ int render_pbrt(const std::string &path, std::string out, const std::string &ren
     if (paths > 0) p.paths_per_pass = paths;
     if (passes > 0) p.passes = passes;
     if (!structure.empty()) p.gather_structure = structure == "kd" ? PM_GATHER_KDTREE : PM_GATHER_GRID;
+    if (!light.empty()) { p.light_source_index = parse_light(light); check_light(p.light_source_index, o.lights.size()); }
     if (out.empty()) out = o.film_filename;
     CudaRender *render = CreateCudaRenderer(o.settings, o.renderer);
     PixelFilm film(o.camera.width, o.camera.height, out);
@@ -277,7 +335,7 @@ int render_pbrt(const std::string &path, std::string out, const std::string &ren
 } // namespace
 
 int main(int argc, char **argv) {
-    std::string scene = "cornell", out, structure, renderer, pbrt;
+    std::string scene = "cornell", out, structure, renderer, pbrt, light;
     bool dump_only = false;
     int W = 64, H = 48;
     long long paths = 512 * 512;
@@ -297,6 +355,7 @@ int main(int argc, char **argv) {
         else if (a == "--paths") { paths = std::atoll(next()); paths_set = true; }
         else if (a == "--passes") { passes = std::atoi(next()); passes_set = true; }
         else if (a == "--structure") structure = next();
+        else if (a == "--light") light = next();
         else if (a == "--instanced") instanced = true;
         else if (a == "--renderer") renderer = next();
         else if (a == "--pbrt") pbrt = next();
@@ -310,7 +369,7 @@ int main(int argc, char **argv) {
     if (!pbrt.empty()) {
         try {
             if (dump_only) return dump(pbrt);
-            return render_pbrt(pbrt, out, renderer, paths_set ? paths : 0, passes_set ? passes : 0, structure);
+            return render_pbrt(pbrt, out, renderer, paths_set ? paths : 0, passes_set ? passes : 0, structure, light);
         } catch (const Error &e) {
             std::fprintf(stderr, "pm_render_cli: %s\n", e.what());
             return 1;
@@ -318,8 +377,8 @@ int main(int argc, char **argv) {
     }
     if (out.empty()) out = "out.pfm";
     if (scene != "cornell" || !have_cam) {
-        std::fprintf(stderr, "usage: %s --scene cornell --camera <12 floats> [--width W --height H] --out f.pfm\n",
-                     argv[0]);
+        std::fprintf(stderr, "usage: %s --scene cornell --camera <12 floats> [--width W --height H] [--light N|all] "
+                             "--out f.pfm\n", argv[0]);
         return 2;
     }
     try {
@@ -330,6 +389,7 @@ int main(int argc, char **argv) {
         settings.params.paths_per_pass = paths;
         settings.params.passes = passes;
         settings.params.gather_structure = structure == "kd" ? PM_GATHER_KDTREE : PM_GATHER_GRID;
+        if (!light.empty()) { settings.params.light_source_index = parse_light(light); check_light(settings.params.light_source_index, lights.size()); }
         CudaRender *render = CreateCudaRenderer(settings, renderer.empty() ? "photonmapping" : renderer);
         PixelFilm film(W, H, out);
         Camera camera;

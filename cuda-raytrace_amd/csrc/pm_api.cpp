@@ -98,10 +98,22 @@ struct Ctx {
     /* device scene */
     DevBuf d_scene, d_rays, d_rand2d; /* d_scene: the scene blob (SceneDev) */
     DevBuf d_light_tris;              /* SceneDev::light_tris (kept out of the blob: never LDS-resident) */
+    /* PM_ALL_LIGHTS: the light selection table (pm_light_selection_cdf over
+     * c->lights, made by pm_commit; all zero and light_cdf_ok false when the
+     * scene's total selection weight is 0 or not finite), its device copy
+     * (TraceParams::light_cdf: a buffer of its own like d_light_tris) */
+    std::vector<float> light_cdf;
+    bool light_cdf_ok = false;
+    DevBuf d_light_cdf;
     DevBuf d_tripairs;                /* brute-force scenes: triangle pairs interleaved (SceneDev::tri_pairs_g) */
     SceneDev S{};
     float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};
-    double emit_max = 1.0, kd_max = 1.0; /* bounds for the fixed-point flux scale */
+    /* bounds for the fixed-point flux scale: emit_max the largest single
+     * light's Le / pdf bound (a fixed light_source_index); emit_max_all the
+     * same under PM_ALL_LIGHTS, where the pick's probability divides the
+     * weight: max_l(bound_l / pmf_l) over the lights with pmf_l > 0 of the
+     * float table (emission_bound chooses per call) */
+    double emit_max = 1.0, emit_max_all = 1.0, kd_max = 1.0;
     bool scene_nonneg = true;  /* no negative emission / albedo component (fixed-point sums in double) */
     bool slots_nonneg = true;  /* the slot buffer holds no negative flux (uploaded slots are checked) */
     int bvh_depth = 0;
@@ -419,6 +431,11 @@ static int materialize_slots(Ctx *c, hipStream_t s) {
     return PM_OK;
 }
 
+/* the bound of a path's emitted weight for this call's light_source_index (Ctx::emit_max) */
+double emission_bound(const Ctx *c, const pm_render_params *p) {
+    return p->light_source_index == PM_ALL_LIGHTS ? c->emit_max_all : c->emit_max;
+}
+
 template <class T>
 int upload(Ctx *c, DevBuf &b, const std::vector<T> &v) {
     HIPCHK(c, b.ensure(std::max<size_t>(v.size() * sizeof(T), 16)));
@@ -486,7 +503,7 @@ GatherParams gather_params(Ctx *c, const pm_render_params *p) {
      * alpha_max * Kd_max / pi with alpha_max = emission * Kd_max^mpc (Lambert
      * weight ~Kd, specular weight 1); x4 headroom; 2^40 per contribution
      * leaves 2^23 contributions per record before int64 overflow */
-    double cmax = c->emit_max * std::pow(c->kd_max, (double)p->max_photon_count) * (c->kd_max / M_PI) * 4.0;
+    double cmax = emission_bound(c, p) * std::pow(c->kd_max, (double)p->max_photon_count) * (c->kd_max / M_PI) * 4.0;
     int S = (int)std::floor(std::log2(std::ldexp(1.0, 40) / std::max(cmax, 1e-30)));
     S = std::max(-60, std::min(60, S));
     G.fx_scale = (float)std::ldexp(1.0, S);
@@ -528,9 +545,13 @@ int check_params(Ctx *c, const pm_render_params *p) {
     if (!p) FAIL(c, PM_ERR_INVALID, "null params");
     if (!c->committed) FAIL(c, PM_ERR_INVALID, "scene not committed (call pm_commit)");
     if (p->max_photon_count < 1 || p->max_photon_count > 64) FAIL(c, PM_ERR_INVALID, "max_photon_count out of range");
-    if (p->light_source_index < 0 || p->light_source_index >= (int)c->lights.size())
-        FAIL(c, PM_ERR_INVALID, "light_source_index %d out of range (%zu lights)", p->light_source_index,
-             c->lights.size());
+    if (p->light_source_index == PM_ALL_LIGHTS) {
+        if (!c->light_cdf_ok)
+            FAIL(c, PM_ERR_INVALID, "PM_ALL_LIGHTS: the total selection weight of the scene's %zu lights is 0 or not "
+                                    "finite (no light to pick)", c->lights.size());
+    } else if (p->light_source_index < 0 || p->light_source_index >= (int)c->lights.size())
+        FAIL(c, PM_ERR_INVALID, "light_source_index %d out of range (%zu lights; PM_ALL_LIGHTS = -1 for every light)",
+             p->light_source_index, c->lights.size());
     if (!(p->initial_radius2 > 0.f)) FAIL(c, PM_ERR_INVALID, "initial_radius2 must be > 0");
     if (p->estimator != PM_ESTIMATOR_PPM && p->estimator != PM_ESTIMATOR_KNN)
         FAIL(c, PM_ERR_INVALID, "unknown estimator %d", p->estimator);
@@ -854,7 +875,7 @@ void pm_destroy(void *ptr) {
                       &c->d_dl, &c->d_slots, &c->d_count, &c->d_scratch, &c->d_vflags, &c->d_vrank, &c->d_vlist, &c->d_vsums,
                       &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times, &c->d_tile_cost, &c->d_tiles2,
                       &c->d_kd, &c->d_out, &c->d_counters, &c->d_tiles, &c->d_tile_flags, &c->d_tile_count,
-                      &c->d_r2hist, &c->d_spill, &c->d_light_tris};
+                      &c->d_r2hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf};
     for (DevBuf *b : bufs) b->release();
     if (c->tile_event) (void)hipEventDestroy(c->tile_event);
     if (c->r2_event) (void)hipEventDestroy(c->r2_event);
@@ -881,6 +902,34 @@ int64_t pm_kdtree_build_host(const pm_photon *slots, int64_t nslots, pm_photon *
 int pm_halton_permutation(uint32_t seed, uint32_t out[28]) {
     if (!out) return PM_ERR_INVALID;
     halton_perm(seed, out);
+    return PM_OK;
+}
+
+int pm_light_selection_cdf(const int *types, const float *le_rgb, const float *areas, int n, float *cdf_out) {
+    Ctx *const none = nullptr;
+    if (!types || !le_rgb || !areas || !cdf_out) FAIL(none, PM_ERR_INVALID, "pm_light_selection_cdf: null pointer");
+    if (n <= 0) FAIL(none, PM_ERR_INVALID, "pm_light_selection_cdf: no lights");
+    std::vector<double> sum((size_t)n);
+    double total = 0.0;
+    for (int l = 0; l < n; ++l) {
+        const double y = 0.212671 * (double)le_rgb[3 * l] + 0.715160 * (double)le_rgb[3 * l + 1] +
+                         0.072169 * (double)le_rgb[3 * l + 2];
+        double w;
+        switch (types[l]) {
+        case PM_LIGHT_POINT: w = y * (4.0 * M_PI); break;
+        case PM_LIGHT_AREA_DISK:
+        case PM_LIGHT_AREA_MESH: w = y * (M_PI * (double)areas[l]); break;
+        default: FAIL(none, PM_ERR_INVALID, "pm_light_selection_cdf: light %d has unknown type %d", l, types[l]);
+        }
+        if (w < 0.0) w = 0.0;
+        total += w;
+        sum[(size_t)l] = total;
+    }
+    if (!(total > 0.0) || !std::isfinite(total))
+        FAIL(none, PM_ERR_INVALID, "pm_light_selection_cdf: total selection weight %g of %d lights is 0 or not finite",
+             total, n);
+    for (int l = 0; l < n; ++l) cdf_out[l] = (float)(sum[(size_t)l] / total);
+    cdf_out[n - 1] = 1.0f;
     return PM_OK;
 }
 
@@ -1560,6 +1609,36 @@ int pm_commit(void *ptr) {
         if (fbits_h(m.w) == PM_MATTE) kd = std::max({kd, (double)m.x, (double)m.y, (double)m.z});
     c->emit_max = std::max(em, 1e-30);
     c->kd_max = kd;
+    /* PM_ALL_LIGHTS: the selection table, and the weight bound with the pick's
+     * probability divided out. A scene that emits nothing keeps a zero table:
+     * a fixed light_source_index still renders it, PM_ALL_LIGHTS is refused
+     * (check_params) */
+    {
+        const size_t nl = c->lights.size();
+        std::vector<int> types(nl);
+        std::vector<float> rgb(3 * nl), areas(nl);
+        for (size_t l = 0; l < nl; ++l) {
+            const LightDev &L = c->lights[l];
+            types[l] = fbits_h(L.o_type.w);
+            rgb[3 * l] = L.le.x; rgb[3 * l + 1] = L.le.y; rgb[3 * l + 2] = L.le.z;
+            areas[l] = L.n_area.w;
+        }
+        c->light_cdf.assign(nl, 0.f);
+        const std::string err_before = g_last_error;
+        c->light_cdf_ok = pm_light_selection_cdf(types.data(), rgb.data(), areas.data(), (int)nl, c->light_cdf.data()) == PM_OK;
+        if (!c->light_cdf_ok) { g_last_error = err_before; c->light_cdf.assign(nl, 0.f); }
+        if ((rc = upload(c, c->d_light_cdf, c->light_cdf))) return rc;
+        double em_all = 0.0;
+        for (size_t l = 0; l < nl && c->light_cdf_ok; ++l) {
+            const LightDev &L = c->lights[l];
+            const float pmf = c->light_cdf[l] - (l ? c->light_cdf[l - 1] : 0.f);
+            if (!(pmf > 0.f)) continue; /* never picked */
+            const double le = std::max({std::fabs(L.le.x), std::fabs(L.le.y), std::fabs(L.le.z)});
+            const double bound = fbits_h(L.o_type.w) == PM_LIGHT_POINT ? le * 4.0 * M_PI : le * L.n_area.w * 2.0 * M_PI;
+            em_all = std::max(em_all, bound / (double)pmf);
+        }
+        c->emit_max_all = std::max(em_all, 1e-30);
+    }
     bool nn = true;
     for (const LightDev &L : c->lights) nn = nn && L.le.x >= 0.f && L.le.y >= 0.f && L.le.z >= 0.f && L.n_area.w >= 0.f;
     for (const float4 &m : c->materials)
@@ -1799,6 +1878,7 @@ int pm_trace_photons(void *ptr, const pm_render_params *p, int pass, int64_t pat
     }
     T.pass = pass; T.mpc = (int)mpc; T.max_spec = p->max_specular_depth; T.light_index = p->light_source_index;
     T.eps = p->scene_epsilon; T.seed = p->rng_seed;
+    T.light_cdf = c->d_light_cdf.as<float>();
     T.counters = c->d_counters.as<unsigned long long>() + 4;
     T.prof = c->d_counters.as<unsigned long long>() + 8;
     if (c->counting) HIPCHK(c, hipMemsetAsync(T.counters, 0, 32, s));
@@ -2013,7 +2093,7 @@ static int gather_common(Ctx *c, const pm_render_params *p, long long *partial, 
          * the per-record scale per term (x4 headroom in amax), exact as a float
          * and as an int32, and <= PM_KNN_MAX = 2^6 terms sum below 2^28 —
          * exact in int32 */
-        const double amax = c->emit_max * std::pow(c->kd_max, (double)p->max_photon_count) * 4.0;
+        const double amax = emission_bound(c, p) * std::pow(c->kd_max, (double)p->max_photon_count) * 4.0;
         G.knn_fx = (float)(std::ldexp(1.0, 24) / std::max(amax, 1e-30));
         G.slots = c->d_slots.as<pm_photon>();
         if (c->knn_ss && !c->counting && c->gather_kernel == PM_GK_TILE) {
@@ -2709,6 +2789,7 @@ int pm_scene_section(void *ptr, int section, void *out, int64_t max_bytes, int64
     case PM_SCENE_INSTANCES: src = S.insts; n = 128 * (int64_t)S.n_inst; break;
     case PM_SCENE_OBJ_TRIS: src = S.obj_v; n = S.n_inst ? 48 * c->obj_tris_stored : 0; break;
     case PM_SCENE_LIGHT_TRIS: src = S.light_tris; n = (int64_t)(c->light_tris.size() * sizeof(LightTri)); break;
+    case PM_SCENE_LIGHT_CDF: src = c->d_light_cdf.p; n = 4 * (int64_t)c->light_cdf.size(); break;
     default: FAIL(c, PM_ERR_INVALID, "unknown scene section %d", section);
     }
     if (bytes) *bytes = n;

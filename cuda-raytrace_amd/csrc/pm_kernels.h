@@ -126,6 +126,12 @@ struct TraceParams {
      * keys say invalid; pm_api zeroes them with launch_zero_invalid_slots
      * before anything else reads the slot buffer) */
     int lazy_zero;
+    /* light_index == PM_ALL_LIGHTS: the light selection table, S.n_lights
+     * floats (pm_light_selection_cdf) in a buffer of its own in HBM like
+     * SceneDev::light_tris: no part of the scene blob, so it changes no
+     * scene's traversal mode and costs no LDS. Selects the ALL instantiations
+     * of the trace kernels (launch_trace); the fixed-light ones never read it */
+    const float *light_cdf;
 };
 
 struct GatherParams {

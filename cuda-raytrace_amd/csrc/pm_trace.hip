@@ -369,18 +369,51 @@ struct TProf {
 #endif
 };
 
-/* emission: Halton light sample -> first ray (photontracing.cu:88-117) */
+/* PM_ALL_LIGHTS: the light a path starts on, the first l with
+ * cdf[l] > min(u, 1 - 2^-24) of the light selection table (pm_api.h
+ * pm_light_selection_cdf; u held below 1 so that the bin found is never
+ * empty), and the probability of that pick as the float difference of its
+ * table entries. The search is sample_light_mesh's: its trip count depends
+ * on n alone, so the lanes of a wave stay together and only their addresses
+ * differ (a few floats that L2 / TCP keep). */
+PMD int pick_light(const float *cdf, int n, float u, float *pmf) {
+    u = fminf(u, 0x1.fffffep-1f);
+    int lo = 0, len = n;
+    while (len > 1) {
+        const int half = len >> 1;
+        lo = cdf[lo + half - 1] > u ? lo : lo + half;
+        len -= half;
+    }
+    *pmf = cdf[lo] - (lo > 0 ? cdf[lo - 1] : 0.f);
+    return lo;
+}
+
+/* emission: Halton light sample -> first ray (photontracing.cu:88-117).
+ * ALL (PM_ALL_LIGHTS, uniform per launch: a template argument, so the
+ * fixed-light kernels keep their code and registers): the light is picked per
+ * path with the sequence's fifth dimension — base 11, table perm + 17, at the
+ * same index; permuted_radical_inverse itself (its modulo and the n *= invBase
+ * quirk at every index: no floor shortcut to prove) — and the weight is
+ * divided by the pick's probability last, so a probability of 1 leaves it bit
+ * for bit. The other four dimensions and the bounce stream do not change: the
+ * path is otherwise the path pid of the picked light. */
+template <int ALL>
 PMD bool emit_path(const TraceParams &P, const SceneDev &S, const uint32_t *perm, uint32_t pid, PathState &st) {
     const uint32_t pm_index = pid * (uint32_t)P.mpc;
     float smp[4];
     permuted_halton4(pm_index, perm, P.perm_bits, smp);
-    const LightDev Lt = S.lights[P.light_index];
+    int light = P.light_index;
+    float pmf = 1.0f;
+    if (ALL) light = pick_light(P.light_cdf, S.n_lights, permuted_radical_inverse(pm_index, 11u, perm + 17), &pmf);
+    const LightDev Lt = S.lights[light];
     v3 N1; float pdf;
     v3 Le = sample_le(Lt, S.light_tris, smp[0], smp[1], smp[2], smp[3], P.eps, &st.ray, &N1, &pdf);
     st.pid = pid; st.nI = 0; st.spec = 0; st.stored = 0; st.pslot = PSLOT_NONE;
     if (pdf == 0.0f || is_black(Le)) return false;
     st.ray.tmax = RT_DEFAULT_MAX;
     st.alpha = (absdot(N1, st.ray.d) * Le) / pdf;
+    /* an IEEE division per component (v3 / float multiplies by the reciprocal: two roundings) */
+    if (ALL) st.alpha = mk(st.alpha.x / pmf, st.alpha.y / pmf, st.alpha.z / pmf);
     return true;
 }
 
@@ -486,7 +519,7 @@ PMD void finish_path(const TraceParams &P, PathState &st, const Held *held = nul
  * §5) and removed. HOLD: deposits held in LDS and written per path.
  * COUNT: census [rays traced, BVH nodes entered, primitive tests, photons
  * deposited], one atomic per wave (counting launches only, never timed). */
-template <int COUNT, int MODE, int HOLD>
+template <int COUNT, int MODE, int HOLD, int ALL = 0>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
     extern __shared__ __attribute__((aligned(16))) int stk[];
     __shared__ uint32_t perm[28];
@@ -507,7 +540,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
     prof.begin();
     if (path < P.path_count) {
         if (HOLD) held_clear(held);
-        bool alive = emit_path(P, S, perm, (uint32_t)(P.path_begin + path), st);
+        bool alive = emit_path<ALL>(P, S, perm, (uint32_t)(P.path_begin + path), st);
         prof.mark(0);
         while (alive) {
             ++rays;
@@ -544,8 +577,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
 constexpr int POOL_STEPS = PM_POOL_STEPS, POOL_SHADE_MIN = PM_POOL_SHADE_MIN;
 enum { PHASE_DEAD = 0, PHASE_TRAV = 1, PHASE_SHADE = 2 };
 
-/* W8: the 8-wide tree (S.wide == 3, TravState8) */
-template <int COUNT, int HOLD, int W8>
+/* W8: the 8-wide tree (S.wide == 3, TravState8); ALL: emit_path's */
+template <int COUNT, int HOLD, int W8, int ALL>
 /* 5 waves/SIMD: 96 VGPRs (102 unconstrained -> 4 waves), no scratch; with
  * the LDS stacks capped at 31 entries (PM_POOL_STACK, the rest spilled) five
  * 256-thread blocks fit a CU. C3 trace (same box): 4.59-4.61 ms at 4 waves,
@@ -611,7 +644,7 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
                 const int64_t mine = cursor + __popcll(dm & ((1ull << lane) - 1ull));
                 if (phase == PHASE_DEAD && mine < wend) {
                     if (HOLD) held_clear(held);
-                    if (emit_path(P, S, perm, (uint32_t)(P.path_begin + mine), st)) {
+                    if (emit_path<ALL>(P, S, perm, (uint32_t)(P.path_begin + mine), st)) {
                         trav_begin(st.ray, tr);
                         phase = PHASE_TRAV;
                     } else {
@@ -633,11 +666,11 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
     }
 }
 
-template <int COUNT, int HOLD>
-__global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool(TraceParams P) { trace_pool_body<COUNT, HOLD, 0>(P); }
-template <int COUNT, int HOLD>
+template <int COUNT, int HOLD, int ALL = 0>
+__global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool(TraceParams P) { trace_pool_body<COUNT, HOLD, 0, ALL>(P); }
+template <int COUNT, int HOLD, int ALL = 0>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
-void k_trace_pool8(TraceParams P) { trace_pool_body<COUNT, HOLD, 1>(P); }
+void k_trace_pool8(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL>(P); }
 
 /* resident waves of the pooled kernel per CU at this LDS size (0 if unknown) */
 int trace_pool_waves_per_cu(size_t lds, int hold, int w8) { /* lds: the stacks */
@@ -682,30 +715,47 @@ static bool trace_hold(const TraceParams &p) {
     return p.hold && p.mpc == HOLD_MPC && ((uintptr_t)p.slots & 15u) == 0u;
 }
 
-template <int HOLD>
+template <int HOLD, int ALL>
 static void launch_lane(const TraceParams &p, dim3 grid, size_t lds, int count, hipStream_t s) {
     switch (scene_mode(p.S)) {
     case MODE_BRUTE:
-        if (count) pm_launch((k_trace_lane<1, MODE_BRUTE, HOLD>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_BRUTE, HOLD>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((k_trace_lane<1, MODE_BRUTE, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((k_trace_lane<0, MODE_BRUTE, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     case MODE_LDS:
-        if (count) pm_launch((k_trace_lane<1, MODE_LDS, HOLD>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_LDS, HOLD>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((k_trace_lane<1, MODE_LDS, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((k_trace_lane<0, MODE_LDS, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     case MODE_INST: /* instances: the per-lane kernel (the pooled one walks only one level) */
-        if (count) pm_launch((k_trace_lane<1, MODE_INST, HOLD>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_INST, HOLD>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((k_trace_lane<1, MODE_INST, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((k_trace_lane<0, MODE_INST, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     default:
-        if (count) pm_launch((k_trace_lane<1, MODE_GLOBAL, HOLD>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_GLOBAL, HOLD>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((k_trace_lane<1, MODE_GLOBAL, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((k_trace_lane<0, MODE_GLOBAL, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     }
 }
 
+/* the pooled kernels (4-wide: k_trace_pool; 8-wide: k_trace_pool8) */
+template <int ALL>
+static void launch_pool(const TraceParams &p, dim3 grid, size_t lds, size_t lds_h, bool hold, int count, hipStream_t s) {
+    if (p.S.wide == 3) {
+        if (count && hold) pm_launch((k_trace_pool8<1, 1, ALL>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+        else if (count) pm_launch((k_trace_pool8<1, 0, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else if (hold) pm_launch((k_trace_pool8<0, 1, ALL>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+        else pm_launch((k_trace_pool8<0, 0, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+    } else if (count && hold) pm_launch((k_trace_pool<1, 1, ALL>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+    else if (count) pm_launch((k_trace_pool<1, 0, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+    else if (hold) pm_launch((k_trace_pool<0, 1, ALL>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+    else pm_launch((k_trace_pool<0, 0, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+}
+
 hipError_t launch_trace(const TraceParams &p, int count, hipStream_t s) {
     if (p.path_count <= 0) return hipSuccess;
+    /* PM_ALL_LIGHTS: the ALL instantiations; a fixed light is an index into S.lights */
+    const bool all = p.light_index == PM_ALL_LIGHTS;
+    if (all ? !p.light_cdf : p.light_index < 0 || p.light_index >= p.S.n_lights) return hipErrorInvalidValue;
     if (p.pool_paths > 0 && scene_mode(p.S) == MODE_GLOBAL && p.S.wide) {
         const int lstk = p.pool_stack > 0 && p.pool_stack < p.S.stack_depth ? p.pool_stack : p.S.stack_depth;
         if (lstk < p.S.stack_depth && !p.spill) return hipErrorInvalidValue;
@@ -714,24 +764,19 @@ hipError_t launch_trace(const TraceParams &p, int count, hipStream_t s) {
         const unsigned grid = (unsigned)((waves + TRACE_BLOCK / 64 - 1) / (TRACE_BLOCK / 64));
         const bool hold = trace_hold(p);
         const size_t lds_h = lds + (hold ? (size_t)HOLD_WORDS * TRACE_BLOCK * 4 : 0);
-        if (p.S.wide == 3) {
-            if (count && hold) pm_launch((k_trace_pool8<1, 1>), dim3(grid), dim3(TRACE_BLOCK), lds_h, s, p);
-            else if (count) pm_launch((k_trace_pool8<1, 0>), dim3(grid), dim3(TRACE_BLOCK), lds, s, p);
-            else if (hold) pm_launch((k_trace_pool8<0, 1>), dim3(grid), dim3(TRACE_BLOCK), lds_h, s, p);
-            else pm_launch((k_trace_pool8<0, 0>), dim3(grid), dim3(TRACE_BLOCK), lds, s, p);
-        } else if (count && hold) pm_launch((k_trace_pool<1, 1>), dim3(grid), dim3(TRACE_BLOCK), lds_h, s, p);
-        else if (count) pm_launch((k_trace_pool<1, 0>), dim3(grid), dim3(TRACE_BLOCK), lds, s, p);
-        else if (hold) pm_launch((k_trace_pool<0, 1>), dim3(grid), dim3(TRACE_BLOCK), lds_h, s, p);
-        else pm_launch((k_trace_pool<0, 0>), dim3(grid), dim3(TRACE_BLOCK), lds, s, p);
+        if (all) launch_pool<1>(p, dim3(grid), lds, lds_h, hold, count, s);
+        else launch_pool<0>(p, dim3(grid), lds, lds_h, hold, count, s);
         return hipGetLastError();
     }
     /* one path per lane */
     const size_t lds = (size_t)p.S.stack_depth * TRACE_BLOCK * 4 + p.S.lds_bytes;
     const unsigned grid = (unsigned)((p.path_count + TRACE_BLOCK - 1) / TRACE_BLOCK);
-    if (trace_hold(p))
-        launch_lane<1>(p, dim3(grid), lds + ((size_t)p.S.lds_bytes + 15u) / 16u * 16u - p.S.lds_bytes +
-                                          (size_t)HOLD_WORDS * TRACE_BLOCK * 4, count, s);
-    else launch_lane<0>(p, dim3(grid), lds, count, s);
+    const size_t lds_h = lds + ((size_t)p.S.lds_bytes + 15u) / 16u * 16u - p.S.lds_bytes + (size_t)HOLD_WORDS * TRACE_BLOCK * 4;
+    if (trace_hold(p)) {
+        if (all) launch_lane<1, 1>(p, dim3(grid), lds_h, count, s);
+        else launch_lane<1, 0>(p, dim3(grid), lds_h, count, s);
+    } else if (all) launch_lane<0, 1>(p, dim3(grid), lds, count, s);
+    else launch_lane<0, 0>(p, dim3(grid), lds, count, s);
     return hipGetLastError();
 }
 

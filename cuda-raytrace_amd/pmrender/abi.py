@@ -18,6 +18,7 @@ PM_REC_INACTIVE = PM_REC_EXCEPTION | PM_REC_MISS | PM_REC_INVALID
 PM_GATHER_GRID, PM_GATHER_KDTREE = 0, 1
 PM_ESTIMATOR_PPM, PM_ESTIMATOR_KNN = 0, 1
 PM_KNN_MAX = 64
+PM_ALL_LIGHTS = -1  # light_source_index: photon paths start on every light, picked by power
 PM_PHOTON_MAX_RIGHT_CHILD = (1 << 29) - 1
 
 # pm_photon == reference CudaPhoton (photon_mapping/photonmapping.h:32-41), 40 B
@@ -72,7 +73,7 @@ class RenderParams(ctypes.Structure):
         p.max_photon_count = 4       # photonmappingrenderer.cpp:183
         p.paths_per_pass = 512 * 512  # photonmappingrenderer.cpp:184-185
         p.passes = 1                 # photonmappingrenderer.cpp:38
-        p.light_source_index = 0     # photonmappingrenderer.cpp:211
+        p.light_source_index = 0     # photonmappingrenderer.cpp:211 (PM_ALL_LIGHTS: every light)
         p.max_specular_depth = 10    # raytracing.cu:98
         p.rng_seed = 777             # cudarandom.h:15
         p.light_rng_seed = 2047

@@ -94,6 +94,8 @@ def load_library(path=None):
         "pm_synchronize": (c_int, [vp]),
         "pm_last_kernel_ms": (c_int, [vp, ctypes.c_char_p, ctypes.POINTER(c_double)]),
         "pm_halton_permutation": (c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+        "pm_light_selection_cdf": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_float),
+                                           ctypes.POINTER(ctypes.c_float), c_int, ctypes.POINTER(ctypes.c_float)]),
         "pm_kdtree_build_host": (i64, [vp, i64, vp]),
         "pm_timing_reset": (c_int, [vp]),
         "pm_gather_range": (c_int, [vp, ctypes.POINTER(RenderParams), i64, i64, vp]),
@@ -117,6 +119,21 @@ def halton_permutation(seed):
     out = (ctypes.c_uint32 * 28)()
     lib.pm_halton_permutation(seed, out)
     return np.frombuffer(out, dtype=np.uint32).copy()
+
+
+def light_selection_cdf(types, le_rgb, areas):
+    """The light selection table of PM_ALL_LIGHTS (pm_light_selection_cdf; host
+    only, no device): float32 cdf per light. Raises ValueError where the call
+    returns PM_ERR_INVALID (no lights, unknown type, total weight 0 / not finite)."""
+    lib = load_library()
+    types = np.ascontiguousarray(np.asarray(types, dtype=np.int32))
+    n = int(types.size)
+    rgb, ar = f32(le_rgb, 3 * n), f32(areas, n)
+    out = np.zeros(max(n, 1), dtype=np.float32)
+    rc = lib.pm_light_selection_cdf(iptr(types), fptr(rgb), fptr(ar), n, fptr(out))
+    if rc != 0:
+        raise ValueError(f"pm_light_selection_cdf failed ({rc}): {lib.pm_last_error(None).decode()}")
+    return out[:n]
 
 
 def kdtree_build_host(slots):
@@ -418,7 +435,7 @@ class Context:
     SCENE_SECTIONS = {"refs": (0, np.uint32), "tri_geo": (1, np.float32), "tri_shade": (2, np.float32),
                       "tri_id": (3, np.uint32), "tri_info": (4, np.int32), "bvh4": (5, np.uint32),
                       "instances": (6, np.float32), "obj_tris": (7, np.float32),
-                      "light_tris": (8, LIGHT_TRI_DTYPE)}
+                      "light_tris": (8, LIGHT_TRI_DTYPE), "light_cdf": (9, np.float32)}
 
     def scene_section(self, name):
         """One section of the committed scene blob as the kernels read it (pm_scene_section)."""

@@ -9,6 +9,8 @@ bit-identical inputs.
   camera at (278, 273, -800), fov 39.3 deg (C1, C2, C4).
 * cornell_quad: the same box lit by its own 130 x 105 quad light, a
   triangle-mesh area light (scenes/cornell-box-quad.pbrt).
+* cornell_two_lights: the Cornell box with its disk and a blue quad light on
+  the green wall (scenes/cornell-two-lights.pbrt; PM_ALL_LIGHTS).
 * triangle_soup: Cornell enclosure + N random triangles, centres
   U[30,525]^3, edges U[-4,4]^3, Kd 0.5 (reference default matte,
   cudamaterial.cpp:40), numpy seed 1 (C3).
@@ -219,6 +221,21 @@ def cornell_quad(W=256, H=256, blocks=True, nsamples=1, Le=17.0):
     black = s.disks[0][6]  # the ceiling disk's black matte serves the quad
     del s.lights[:], s.disks[:]
     s.add_mesh_light(QUAD_LIGHT, [(0, 1, 2), (0, 2, 3)], (Le, Le, Le), nsamples, material=black)
+    return s
+
+
+WALL_LIGHT = [(1.0, 200.0, 230.0), (1.0, 300.0, 230.0), (1.0, 300.0, 330.0), (1.0, 200.0, 330.0)]
+WALL_LIGHT_LE = (4.0, 8.0, 20.0)
+
+
+def cornell_two_lights(W=256, H=256, blocks=True, nsamples=1):
+    """The Cornell box with two lights (scenes/cornell-two-lights.pbrt): the
+    white ceiling disk, then a blue 100 x 100 quad light just off the green wall
+    (x = 0), two triangles wound to face +x. Rendered with
+    light_source_index = PM_ALL_LIGHTS both lights cast indirect light."""
+    s = cornell_box(W, H, blocks=blocks, nsamples=nsamples)
+    black = s.disks[0][6]  # the ceiling disk's black matte serves the quad
+    s.add_mesh_light(WALL_LIGHT, [(0, 1, 2), (0, 2, 3)], WALL_LIGHT_LE, nsamples, material=black)
     return s
 
 

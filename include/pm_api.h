@@ -77,6 +77,11 @@ extern "C" {
 #define PM_ESTIMATOR_PPM 0 /* the reference's: fixed-radius query + progressive update (gathering.cu:17-146) */
 #define PM_ESTIMATOR_KNN 1 /* pbrt-v2 PhotonIntegrator::LPhoton: k nearest photons, Simpson kernel */
 #define PM_KNN_MAX 64      /* largest knn_lookup */
+/* pm_render_params::light_source_index: photon paths start on every light,
+ * each path on one light chosen by emitted power (the light selection table
+ * below, pm_light_selection_cdf); any value >= 0 is the reference's single
+ * light (photonmappingrenderer.cpp:211). Other negative values are invalid. */
+#define PM_ALL_LIGHTS (-1)
 
 /* ---- POD layouts shared with tests / other hosts ----------------------- */
 
@@ -131,7 +136,7 @@ typedef struct pm_render_params {
     int max_photon_count;    /* 4     photonmappingrenderer.cpp:183 (deposits per path) */
     int64_t paths_per_pass;  /* 262144 = 512*512, photonmappingrenderer.cpp:184-185,214 */
     int passes;              /* 1     photonmappingrenderer.cpp:38 */
-    int light_source_index;  /* 0     photonmappingrenderer.cpp:211 */
+    int light_source_index;  /* 0     photonmappingrenderer.cpp:211; PM_ALL_LIGHTS: every light */
     int max_specular_depth;  /* 10    raytracing.cu:98 (eye); build cap for photons (SURVEY App.B 5) */
     uint32_t rng_seed;       /* 777   util/random/cudarandom.h:15 */
     uint32_t light_rng_seed; /* 2047  (cudalight.cpp:530, commented-out light RNG seed) */
@@ -382,6 +387,10 @@ int pm_scene_info(void *ctx, int64_t out[7]);
 /* 64 B per emitting triangle, mesh lights in light order: (p0, cdf[k]) (p1 - p0, 0)
  * (p2 - p0, 0) (emitting-side unit normal, 0); pm_device.h SceneDev::light_tris */
 #define PM_SCENE_LIGHT_TRIS 8
+/* 4 B per light: the light selection table cdf[l] (float) of PM_ALL_LIGHTS,
+ * pm_light_selection_cdf over the scene's lights as pm_commit calls it (all
+ * zero when that call fails: the scene emits nothing) */
+#define PM_SCENE_LIGHT_CDF 9
 int pm_scene_section(void *ctx, int section, void *out, int64_t max_bytes, int64_t *bytes);
 /* the current photon map (pm_build_photon_map; the reference's
  * CreatePhotonMap, photonmappingrenderer.cpp:150-180): [0] structure
@@ -422,6 +431,33 @@ int64_t pm_kdtree_build_host(const pm_photon *slots, int64_t nslots, pm_photon *
 
 /* Halton permutation of PermutedHalton(5, RNG(seed)) (28 uints), exposed for tests. */
 int pm_halton_permutation(uint32_t seed, uint32_t out[28]);
+
+/* Host-only: the light selection table of PM_ALL_LIGHTS (pbrt-v2's photon
+ * shooter picks a light per path from a power cdf and divides the path weight
+ * by the probability of the pick; the reference emits from light 0 only).
+ * Light l has type types[l] (PM_LIGHT_*), colour le_rgb[3l .. 3l+2] (a point
+ * light's intensity, an area light's emitted radiance Le) and area areas[l]
+ * (disk: its area; mesh: its total area; ignored for a point light). All in
+ * double, from the float inputs:
+ *   y(c) = 0.212671 r + 0.715160 g + 0.072169 b     (pbrt's luminance, summed
+ *                                                    left to right)
+ *   w[l] = y(c) * (4 pi)         point light        (pbrt PointLight::Power)
+ *   w[l] = y(c) * (pi * area)    disk or mesh light (DiffuseAreaLight::Power;
+ *          also the mean of the path weight |cos| Le area / pdf that the
+ *          emission produces with its uniform-hemisphere direction)
+ * with pi = M_PI; a negative w[l] counts as 0. Running sum in double in light
+ * order, cdf[l] = (float)(sum[l] / sum[n - 1]), cdf[n - 1] = 1 (the
+ * pm_add_light_mesh convention). A path with selection sample u — dimension 5
+ * of the permuted Halton sequence (base 11, table entries 17..27 of
+ * pm_halton_permutation) at the path's first slot index, evaluated as the
+ * other four dimensions are — starts on the first light l with
+ * cdf[l] > min(u, 1 - 2^-24), so a light of weight 0 is never picked; its
+ * weight is the single light's, divided last by the float
+ * pmf[l] = cdf[l] - (l ? cdf[l - 1] : 0). Dimensions 1-4 and the bounce
+ * stream are the single light's, so path p is otherwise the path p of
+ * light_source_index = l. Returns PM_OK, or PM_ERR_INVALID for n <= 0, a null
+ * pointer, an unknown type, or a total weight that is 0 or not finite. */
+int pm_light_selection_cdf(const int *types, const float *le_rgb, const float *areas, int n, float *cdf_out);
 
 #ifdef __cplusplus
 }
