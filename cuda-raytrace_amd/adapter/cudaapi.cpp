@@ -144,6 +144,32 @@ void CudaRender::createSubRenderer(Sampler *sampler, Camera *camera, const Param
     if (params.FindOneString("photonmap", "grid") == "kdtree") s.params.gather_structure = PM_GATHER_KDTREE;
     /* the light the photon paths start on; -1 (PM_ALL_LIGHTS): every light, picked per path by power */
     s.params.light_source_index = params.FindOneInt("lightsource", s.params.light_source_index);
+    /* the device camera + film (pm_set_camera): "integer devicecamera" [1]
+     * hands the camera to the device (strata "integer xsamples" / "ysamples",
+     * "integer jitter" [0|1], "integer sampleseed"; thin lens "float
+     * lensradius" / "focaldistance"; "string pixelfilter" "box" | "triangle" |
+     * "gaussian" | "mitchell" with "float xwidth" / "ywidth" / "alpha" / "B" /
+     * "C", pbrt's defaults). Without it the sampler's rays are used as before. */
+    devcam_ = pmcuda::Camera();
+    devcam_.device_camera = params.FindOneInt("devicecamera", 0) != 0;
+    if (devcam_.device_camera) {
+        devcam_.xsamples = params.FindOneInt("xsamples", 1);
+        devcam_.ysamples = params.FindOneInt("ysamples", 1);
+        devcam_.jitter = params.FindOneInt("jitter", 1) != 0;
+        devcam_.sample_seed = (uint32_t)params.FindOneInt("sampleseed", 0);
+        devcam_.lens_radius = params.FindOneFloat("lensradius", 0.f);
+        devcam_.focal_distance = params.FindOneFloat("focaldistance", 0.f);
+        const std::string fn = params.FindOneString("pixelfilter", "box");
+        pm_filter f = {PM_FILTER_BOX, 0.5f, 0.5f, 0.f, 0.f};
+        if (fn == "triangle") f = pm_filter{PM_FILTER_TRIANGLE, 2.f, 2.f, 0.f, 0.f};
+        else if (fn == "gaussian") f = pm_filter{PM_FILTER_GAUSSIAN, 2.f, 2.f, params.FindOneFloat("alpha", 2.f), 0.f};
+        else if (fn == "mitchell")
+            f = pm_filter{PM_FILTER_MITCHELL, 2.f, 2.f, params.FindOneFloat("B", 1.f / 3.f), params.FindOneFloat("C", 1.f / 3.f)};
+        else if (fn != "box") Severe("Renderer \"cuda\": pixelfilter \"%s\" not supported", fn.c_str());
+        f.xwidth = params.FindOneFloat("xwidth", f.xwidth);
+        f.ywidth = params.FindOneFloat("ywidth", f.ywidth);
+        devcam_.filter = f;
+    }
     impl_.createSubRenderer(s, rendername);
 }
 
@@ -154,7 +180,7 @@ struct PbrtFilm : pmcuda::Film {
     ::Film *film;
     const std::vector<CameraSample> *samples;
     size_t next = 0;
-    void AddSample(const pmcuda::CameraSample &, const float rgb[3]) override {
+    void AddSample(const pmcuda::CameraSample &cs, const float rgb[3]) override {
         Spectrum result = RGBSpectrum::FromRGB(rgb);
         if (result.HasNaNs()) {
             Error("Not-a-number radiance value returned for image sample.  Setting to black.");
@@ -166,7 +192,11 @@ struct PbrtFilm : pmcuda::Film {
             Error("Infinite luminance value returned for image sample.  Setting to black.");
             result = Spectrum(0.f);
         }
-        film->AddSample((*samples)[next++], result);
+        if (samples) { film->AddSample((*samples)[next++], result); return; }
+        /* device camera: one filmed value per pixel at (x + 0.5, y + 0.5) */
+        CameraSample at = CameraSample();
+        at.imageX = cs.imageX; at.imageY = cs.imageY; at.lensU = at.lensV = 0.5f;
+        film->AddSample(at, result);
     }
     void WriteImage() override { film->WriteImage(); } /* PhotonMappingRenderer::postLaunch */
 };
@@ -223,6 +253,45 @@ void CudaRender::Render(const Scene *scene) {
     /* the eye samples (PbrtCamera::preLaunch, pbrtcamera.cpp:57-122): the
      * sampler's stream in its own order, rays with differentials scaled by
      * 1/sqrt(spp), the light 2D randoms of each sample */
+    if (devcam_.device_camera) {
+        /* The camera's world basis through pbrt's public interface: rays from
+         * the lens centre through the image centre, the middle of the right
+         * edge and the middle of the top edge. A perspective camera's
+         * direction is fwd + ndc_x right + ndc_y up up to length, so with
+         * fwd = the centre direction, right = dr / (dr . fwd) - fwd and up
+         * likewise. The 2D light samples are the device's own (Philox by
+         * sample index), so none are registered with the sampler. */
+        const int W = camera_->film->xResolution, H = camera_->film->yResolution;
+        auto probe = [&](float x, float y, Ray *r) {
+            CameraSample cs = CameraSample();
+            cs.imageX = x; cs.imageY = y; cs.lensU = cs.lensV = 0.5f; cs.time = 0.f;
+            camera_->GenerateRay(cs, r);
+            r->d = Normalize(r->d);
+        };
+        Ray c, r, u;
+        probe(0.5f * W, 0.5f * H, &c);
+        probe((float)W, 0.5f * H, &r);
+        probe(0.5f * W, 0.f, &u);
+        const float kr = 1.f / (r.d.x * c.d.x + r.d.y * c.d.y + r.d.z * c.d.z);
+        const float ku = 1.f / (u.d.x * c.d.x + u.d.y * c.d.y + u.d.z * c.d.z);
+        pmcuda::Camera cam = devcam_;
+        cam.pinhole = true;
+        cam.width = W; cam.height = H;
+        cam.eye[0] = c.o.x; cam.eye[1] = c.o.y; cam.eye[2] = c.o.z;
+        cam.fwd[0] = c.d.x; cam.fwd[1] = c.d.y; cam.fwd[2] = c.d.z;
+        cam.right[0] = r.d.x * kr - c.d.x; cam.right[1] = r.d.y * kr - c.d.y; cam.right[2] = r.d.z * kr - c.d.z;
+        cam.up[0] = u.d.x * ku - c.d.x; cam.up[1] = u.d.y * ku - c.d.y; cam.up[2] = u.d.z * ku - c.d.z;
+        PbrtFilm film;
+        film.film = camera_->film;
+        film.samples = NULL;
+        cam.film = &film;
+        try {
+            impl_.Render(lights, cam);
+        } catch (const pmcuda::Error &e) {
+            Severe("%s", e.what());
+        }
+        return;
+    }
     int xs, xe, ys, ye;
     camera_->film->GetSampleExtent(&xs, &xe, &ys, &ye);
     const int spp = sampler_->samplesPerPixel;

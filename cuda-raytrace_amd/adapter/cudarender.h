@@ -58,6 +58,10 @@ private:
     std::map<const Material *, pmcuda::Material> materials_; /* cudarender.h:74-76 */
     Sampler *sampler_;
     Camera *camera_;
+    /* the Renderer "cuda" ParamSet's device camera (createSubRenderer):
+     * device_camera set = the camera is evaluated on the device with its film
+     * (pm_set_camera) instead of through the sampler's host-generated rays */
+    pmcuda::Camera devcam_;
 };
 
 #endif // cudarender_h__

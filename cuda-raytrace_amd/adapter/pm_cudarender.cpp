@@ -286,6 +286,18 @@ void CudaRender::Render(const std::vector<Light> &lights, Camera &camera) {
 
 /* ------------------------------------------------------------ renderer */
 static int64_t set_camera(void *ctx, const Camera &camera) {
+    if (camera.pinhole && camera.device_camera) {
+        pm_camera c{};
+        std::memcpy(c.eye, camera.eye, 12); std::memcpy(c.fwd, camera.fwd, 12);
+        std::memcpy(c.right, camera.right, 12); std::memcpy(c.up, camera.up, 12);
+        c.width = camera.width; c.height = camera.height;
+        c.xsamples = camera.xsamples; c.ysamples = camera.ysamples; c.jitter = camera.jitter ? 1 : 0;
+        c.lens_radius = camera.lens_radius; c.focal_distance = camera.focal_distance;
+        c.sample_seed = camera.sample_seed; c.filter = camera.filter;
+        check(ctx, pm_set_camera(ctx, &c), "pm_set_camera");
+        const int64_t spp = camera.filter.type == PM_FILTER_NONE ? (int64_t)camera.xsamples * camera.ysamples : 1;
+        return (int64_t)camera.width * camera.height * spp;
+    }
     if (camera.pinhole) {
         check(ctx, pm_set_pinhole(ctx, camera.eye, camera.fwd, camera.right, camera.up, camera.width, camera.height),
               "pm_set_pinhole");
@@ -303,7 +315,12 @@ static void splat(Camera &camera, const std::vector<float> &rgb, int64_t n) {
     if (!camera.film) return;
     for (int64_t i = 0; i < n; ++i) {
         CameraSample cs;
-        if (camera.pinhole) {
+        if (camera.pinhole && camera.device_camera && camera.filter.type == PM_FILTER_NONE) {
+            /* the sample raster: each sample at its stratum centre */
+            const int64_t ws = (int64_t)camera.width * camera.xsamples;
+            cs.imageX = ((float)(i % ws) + 0.5f) / (float)camera.xsamples;
+            cs.imageY = ((float)(i / ws) + 0.5f) / (float)camera.ysamples;
+        } else if (camera.pinhole) {
             cs.imageX = (float)(i % camera.width) + 0.5f;
             cs.imageY = (float)(i / camera.width) + 0.5f;
         } else {

@@ -118,6 +118,17 @@ struct Camera {
     bool pinhole = true;
     float eye[3] = {0, 0, 0}, fwd[3] = {0, 0, 1}, right[3] = {1, 0, 0}, up[3] = {0, 1, 0};
     int width = 0, height = 0;
+    /* device_camera (pinhole only): the supersampled thin-lens camera with
+     * the on-device film (pm_set_camera) instead of pm_set_pinhole: strata per
+     * pixel, jitter, lens and pixel filter. With a real filter the film gets
+     * one AddSample per pixel at (x + 0.5, y + 0.5) with the filmed value;
+     * with PM_FILTER_NONE one per sample at its stratum centre. */
+    bool device_camera = false;
+    int xsamples = 1, ysamples = 1;
+    bool jitter = true;
+    float lens_radius = 0.f, focal_distance = 0.f;
+    uint32_t sample_seed = 0;
+    pm_filter filter = {PM_FILTER_NONE, 0.f, 0.f, 0.f, 0.f};
     std::vector<float> rays, rand2d;
     int n2d = 0;
     std::vector<CameraSample> samples;

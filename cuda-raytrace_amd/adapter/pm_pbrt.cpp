@@ -123,6 +123,10 @@ struct ParamSet {
         const Param *p = find(n);
         return p && !p->nums.empty() ? (int)p->nums[0] : d;
     }
+    bool oneBool(const std::string &n, bool d) const {
+        const Param *p = find(n);
+        return p && !p->strs.empty() ? p->strs[0] == "true" : d;
+    }
     std::string oneString(const std::string &n, const std::string &d) const {
         const Param *p = find(n);
         return p && !p->strs.empty() ? p->strs[0] : d;
@@ -448,7 +452,26 @@ struct PbrtParser::Impl {
         sink->shape(name, s, current_instance, gs.material, light);
     }
 
+    /* Sampler / PixelFilter / lens of the options block (defaults: one centre
+     * sample, no filter, pinhole: the device pinhole of pm_set_pinhole) */
+    int xsamples = 1, ysamples = 1;
+    bool jitter = true, have_filter = false;
+    pm_filter filter = {PM_FILTER_NONE, 0.f, 0.f, 0.f, 0.f};
+    float lens_radius = 0.f, focal_distance = 0.f;
+
     void camera_done() {
+        /* the device camera + film only where the scene asks for more than
+         * today's pinhole: several samples, a PixelFilter, or a lens */
+        {
+            Camera &cam = opts->camera;
+            cam.device_camera = xsamples * ysamples > 1 || have_filter || lens_radius > 0.f;
+            cam.xsamples = xsamples; cam.ysamples = ysamples;
+            cam.jitter = jitter; /* the Sampler's "bool jitter" (default true); unused by the pinhole */
+            cam.lens_radius = lens_radius;
+            cam.focal_distance = lens_radius > 0.f ? focal_distance : 0.f;
+            cam.filter = filter;
+            if (cam.device_camera && !have_filter) cam.filter = pm_filter{PM_FILTER_BOX, 0.5f, 0.5f, 0.f, 0.f};
+        }
         /* pinhole through the pixel centres: d = fwd + sx*right + sy*up,
          * sx, sy in [-1, 1] (pm_set_pinhole); the screen window folds into
          * the three vectors */
@@ -532,8 +555,12 @@ struct PbrtParser::Impl {
                 const std::string n = str(lx);
                 camera_params = params(lx);
                 if (n != "perspective") lx.fail(line, "camera \"%s\" not supported (perspective only)", n.c_str());
-                if (camera_params.oneFloat("lensradius", 0.f) > 0.f)
-                    warn(lx, line, "%s: depth of field not supported (pinhole)", n);
+                lens_radius = camera_params.oneFloat("lensradius", 0.f);
+                focal_distance = camera_params.oneFloat("focaldistance", 1e30f);
+                if (lens_radius < 0.f) lx.fail(line, "Camera \"lensradius\" %g: must be >= 0", lens_radius);
+                if (lens_radius > 0.f && !(focal_distance > 0.f && focal_distance < 1e30f))
+                    lx.fail(line, "Camera \"lensradius\" %g needs a \"float focaldistance\" (pbrt's default 1e30 "
+                                  "focuses at infinity: not supported)", lens_radius);
                 camera_to_world = inverse(ctm);
                 coord_sys["camera"] = camera_to_world;
                 have_camera = true;
@@ -569,7 +596,45 @@ struct PbrtParser::Impl {
                     lightsource_line = line;
                     lightsource_file = lx.file();
                 }
-            } else if (d == "Sampler" || d == "PixelFilter" || d == "SurfaceIntegrator" || d == "VolumeIntegrator" ||
+            } else if (d == "Sampler") {
+                const std::string n = str(lx);
+                const ParamSet ps = params(lx);
+                if (n == "stratified") {
+                    xsamples = ps.oneInt("xsamples", 2);
+                    ysamples = ps.oneInt("ysamples", 2);
+                    jitter = ps.oneBool("jitter", true);
+                } else if (n == "lowdiscrepancy" || n == "bestcandidate" || n == "random") {
+                    /* N rounded up to 2^k (64 at most), as 2^ceil(k/2) x 2^floor(k/2) strata */
+                    const int N = ps.oneInt("pixelsamples", 4);
+                    int k = 0;
+                    while (k < 6 && (1 << k) < N) ++k;
+                    xsamples = 1 << ((k + 1) / 2);
+                    ysamples = 1 << (k / 2);
+                    jitter = true;
+                    if (N > 1) warn(lx, line, "Sampler \"%s\": the pattern is stratified (jittered strata)", n);
+                } else {
+                    warn(lx, line, "Sampler \"%s\" not supported: one sample per pixel", n);
+                }
+                if (xsamples < 1 || xsamples > 8 || ysamples < 1 || ysamples > 8)
+                    lx.fail(line, "Sampler: %d x %d samples per pixel (1..8 each)", xsamples, ysamples);
+            } else if (d == "PixelFilter") {
+                std::string n = str(lx);
+                const ParamSet ps = params(lx);
+                if (n == "sinc") { warn(lx, line, "PixelFilter \"%s\" not supported: mitchell instead", n); n = "mitchell"; }
+                pm_filter f = {PM_FILTER_NONE, 0.f, 0.f, 0.f, 0.f};
+                float w = 2.f; /* pbrt-v2's default widths: box 0.5, the others 2 */
+                if (n == "box") { f.type = PM_FILTER_BOX; w = 0.5f; }
+                else if (n == "triangle") f.type = PM_FILTER_TRIANGLE;
+                else if (n == "gaussian") { f.type = PM_FILTER_GAUSSIAN; f.a = ps.oneFloat("alpha", 2.f); }
+                else if (n == "mitchell") { f.type = PM_FILTER_MITCHELL; f.a = ps.oneFloat("B", 1.f / 3.f); f.b = ps.oneFloat("C", 1.f / 3.f); }
+                else lx.fail(line, "PixelFilter \"%s\" not supported (box, triangle, gaussian, mitchell)", n.c_str());
+                f.xwidth = ps.oneFloat("xwidth", w);
+                f.ywidth = ps.oneFloat("ywidth", w);
+                if (!(f.xwidth > 0.f && f.xwidth <= 4.f) || !(f.ywidth > 0.f && f.ywidth <= 4.f))
+                    lx.fail(line, "PixelFilter widths (%g, %g) outside (0, 4]", f.xwidth, f.ywidth);
+                filter = f;
+                have_filter = true;
+            } else if (d == "SurfaceIntegrator" || d == "VolumeIntegrator" ||
                        d == "Accelerator" || d == "Volume") {
                 str(lx);
                 params(lx);

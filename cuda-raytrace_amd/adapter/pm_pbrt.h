@@ -24,7 +24,16 @@
  *                ("photonmapping" | "simple" | "cuda" + "string rendername";
  *                extension params "integer paths", "integer passes",
  *                "string gather" = "grid" | "kdtree")
- *                Sampler / PixelFilter / *Integrator / Accelerator: accepted, ignored
+ *                Camera "float lensradius" / "float focaldistance" (thin lens),
+ *                Sampler "stratified" (xsamples, ysamples, jitter) or
+ *                "lowdiscrepancy" | "bestcandidate" | "random" (pixelsamples N,
+ *                rounded up to 2^k <= 64 as 2^ceil(k/2) x 2^floor(k/2) jittered
+ *                strata), PixelFilter "box" | "triangle" | "gaussian" |
+ *                "mitchell" (xwidth, ywidth, alpha, B, C; "sinc" -> mitchell):
+ *                with more than one sample per pixel, a PixelFilter or a lens
+ *                the camera is the device camera with its film
+ *                (pm_set_camera), else today's pinhole
+ *                *Integrator / Accelerator: accepted, ignored
  *   Include      relative to the including file
  *
  * Semantics follow pbrt-v2: float transforms with pbrt's Rotate / LookAt

@@ -42,6 +42,10 @@ struct Opts {
     bool instanced = false, quad_light = false, two_lights = false;
     int lightsource = 0;
     bool lightsource_set = false;
+    /* --devicecamera: the Renderer "cuda" ParamSet's device camera + film */
+    int devicecamera = 0, xsamples = 1, ysamples = 1, jitter = 1;
+    float lensradius = 0.f, focaldistance = 0.f, xwidth = 0.f;
+    std::string pixelfilter;
 };
 
 /* pixel centres in raster order, one sample per pixel; light 2D randoms:
@@ -209,6 +213,16 @@ int run(const Opts &o) {
     params.AddInt("photonpaths", &o.paths, 1);
     params.AddString("photonmap", &o.photonmap, 1);
     if (o.lightsource_set) params.AddInt("lightsource", &o.lightsource, 1);
+    if (o.devicecamera) {
+        params.AddInt("devicecamera", &o.devicecamera, 1);
+        params.AddInt("xsamples", &o.xsamples, 1);
+        params.AddInt("ysamples", &o.ysamples, 1);
+        params.AddInt("jitter", &o.jitter, 1);
+        params.AddFloat("lensradius", &o.lensradius, 1);
+        params.AddFloat("focaldistance", &o.focaldistance, 1);
+        if (!o.pixelfilter.empty()) params.AddString("pixelfilter", &o.pixelfilter, 1);
+        if (o.xwidth > 0.f) { params.AddFloat("xwidth", &o.xwidth, 1); params.AddFloat("ywidth", &o.xwidth, 1); }
+    }
     CentreSampler *sampler = new CentreSampler(o.W, o.H);
     Renderer *renderer = CreateCudaRenderer(sampler, camera, params, o.renderer == "simple" ? "simple" : "photonmap");
     /* pbrtWorldEnd */
@@ -246,6 +260,14 @@ int main(int argc, char **argv) {
         else if (a == "--two-lights") o.two_lights = true;
         else if (a == "--lightsource") { o.lightsource = std::stoi(val()); o.lightsource_set = true; }
         else if (a == "--out") o.out = val();
+        else if (a == "--devicecamera") o.devicecamera = 1;
+        else if (a == "--xsamples") o.xsamples = std::stoi(val());
+        else if (a == "--ysamples") o.ysamples = std::stoi(val());
+        else if (a == "--no-jitter") o.jitter = 0;
+        else if (a == "--lensradius") o.lensradius = std::stof(val());
+        else if (a == "--focaldistance") o.focaldistance = std::stof(val());
+        else if (a == "--pixelfilter") o.pixelfilter = val();
+        else if (a == "--filterwidth") o.xwidth = std::stof(val());
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (o.out.empty()) { std::fprintf(stderr, "usage: %s --out f.bin [options]\n", argv[0]); return 2; }

@@ -12,6 +12,7 @@
  *   pm_render_cli --pbrt scene.pbrt [--out img.pfm] [--renderer R] [--paths N] [--passes P] [--structure S]
  *                 [--light N|all]
  *                 (a pbrt-v2 scene file through pm_pbrt.h; command-line options override the file)
+ *                 [--spp XxY] [--filter name[:xw[:yw[:a[:b]]]]] [--lens R:F] [--no-jitter]   (the device camera + film)
  *   pm_render_cli --pbrt scene.pbrt --dump   (parse only, no device: the plugin calls as JSON, with the
  *                 renderer's light_source_index and the scene's light selection table)
  * --light: the light the photon paths start on; "all" (or -1) starts them on
@@ -214,11 +215,79 @@ float lightArea(const Light &L) {
     return (float)total;
 }
 
-int dump(const std::string &path) {
+/* --spp XxY, --filter name[:xw[:yw[:a[:b]]]], --lens R:F, --no-jitter over the scene file's camera.
+ * Each flag replaces what the scene file says about the same thing and
+ * nothing else: jitter stays the Sampler's unless --no-jitter is given. The
+ * device camera is used by the scene file's own rule: more than one sample
+ * per pixel, a pixel filter, or a lens. */
+struct CameraFlags {
+    std::string spp, filter, lens;
+    bool no_jitter = false;
+    bool any() const { return !spp.empty() || !filter.empty() || !lens.empty() || no_jitter; }
+};
+float flag_float(const std::string &flag, const std::string &v) {
+    char *end = nullptr;
+    const float f = std::strtof(v.c_str(), &end);
+    if (v.empty() || *end || !std::isfinite(f)) throw Error(flag + ": \"" + v + "\" is not a number");
+    return f;
+}
+std::vector<std::string> split_colon(const std::string &v) {
+    std::vector<std::string> part;
+    size_t i = 0;
+    while (true) {
+        const size_t j = v.find(':', i);
+        part.push_back(v.substr(i, j == std::string::npos ? j : j - i));
+        if (j == std::string::npos) break;
+        i = j + 1;
+    }
+    return part;
+}
+void apply_camera_flags(const CameraFlags &f, Camera &c) {
+    if (!f.spp.empty()) {
+        int n = 0;
+        if (std::sscanf(f.spp.c_str(), "%dx%d%n", &c.xsamples, &c.ysamples, &n) != 2 || (size_t)n != f.spp.size() ||
+            c.xsamples < 1 || c.xsamples > 8 || c.ysamples < 1 || c.ysamples > 8)
+            throw Error("--spp " + f.spp + ": expected XxY with 1..8 each");
+    }
+    bool filter_given = c.device_camera && c.filter.type != PM_FILTER_NONE;
+    if (!f.filter.empty()) {
+        const std::vector<std::string> part = split_colon(f.filter);
+        pm_filter k = {PM_FILTER_NONE, 2.f, 2.f, 0.f, 0.f};
+        if (part[0] == "box") { k.type = PM_FILTER_BOX; k.xwidth = k.ywidth = 0.5f; }
+        else if (part[0] == "triangle") k.type = PM_FILTER_TRIANGLE;
+        else if (part[0] == "gaussian") { k.type = PM_FILTER_GAUSSIAN; k.a = 2.f; }
+        else if (part[0] == "mitchell") { k.type = PM_FILTER_MITCHELL; k.a = k.b = 1.f / 3.f; }
+        else throw Error("--filter " + f.filter + ": box, triangle, gaussian or mitchell");
+        if (part.size() > 5) throw Error("--filter " + f.filter + ": expected name[:xw[:yw[:a[:b]]]]");
+        if (part.size() > 1) k.xwidth = k.ywidth = flag_float("--filter", part[1]);
+        if (part.size() > 2) k.ywidth = flag_float("--filter", part[2]);
+        if (part.size() > 3) k.a = flag_float("--filter", part[3]);
+        if (part.size() > 4) k.b = flag_float("--filter", part[4]);
+        if (!(k.xwidth > 0.f && k.xwidth <= 4.f) || !(k.ywidth > 0.f && k.ywidth <= 4.f))
+            throw Error("--filter " + f.filter + ": widths outside (0, 4]");
+        c.filter = k;
+        filter_given = true;
+    }
+    if (!f.lens.empty()) {
+        const std::vector<std::string> part = split_colon(f.lens);
+        if (part.size() != 2) throw Error("--lens " + f.lens + ": expected R:F");
+        c.lens_radius = flag_float("--lens", part[0]);
+        c.focal_distance = flag_float("--lens", part[1]);
+        if (c.lens_radius < 0.f || (c.lens_radius > 0.f && !(c.focal_distance > 0.f)))
+            throw Error("--lens " + f.lens + ": R >= 0, and F > 0 with a lens");
+    }
+    if (f.no_jitter) c.jitter = false;
+    c.device_camera = c.xsamples * c.ysamples > 1 || filter_given || c.lens_radius > 0.f;
+    if (c.device_camera && !filter_given) c.filter = pm_filter{PM_FILTER_BOX, 0.5f, 0.5f, 0.f, 0.f};
+    if (!c.device_camera) c.filter = pm_filter{PM_FILTER_NONE, 0.f, 0.f, 0.f, 0.f};
+}
+
+int dump(const std::string &path, const CameraFlags &cflags) {
     DumpSink sink;
     PbrtOptions o;
     PbrtParser parser;
     parser.parseFile(path, sink, o);
+    apply_camera_flags(cflags, o.camera);
     std::string lights;
     for (const Light &L : o.lights) {
         if (!lights.empty()) lights += ",\n";
@@ -261,6 +330,16 @@ int dump(const std::string &path) {
     DumpSink::arr(cam, c.fwd, 3); cam += ", \"right\": ";
     DumpSink::arr(cam, c.right, 3); cam += ", \"up\": ";
     DumpSink::arr(cam, c.up, 3);
+    {
+        static const char *names[] = {"none", "box", "triangle", "gaussian", "mitchell"};
+        char b[512];
+        std::snprintf(b, sizeof b, ", \"device_camera\": %d, \"xsamples\": %d, \"ysamples\": %d, \"jitter\": %d, "
+                      "\"lens_radius\": %.9g, \"focal_distance\": %.9g, \"sample_seed\": %u, \"filter\": {\"type\": \"%s\", "
+                      "\"xwidth\": %.9g, \"ywidth\": %.9g, \"a\": %.9g, \"b\": %.9g}",
+                      c.device_camera ? 1 : 0, c.xsamples, c.ysamples, c.jitter ? 1 : 0, c.lens_radius, c.focal_distance,
+                      c.sample_seed, names[c.filter.type], c.filter.xwidth, c.filter.ywidth, c.filter.a, c.filter.b);
+        cam += b;
+    }
     const pm_render_params &p = o.settings.params;
     /* the light selection table of PM_ALL_LIGHTS as pm_commit would build it
      * (host only); [] for a scene that emits nothing */
@@ -303,7 +382,7 @@ void check_light(int k, size_t n_lights) {
 }
 
 int render_pbrt(const std::string &path, std::string out, const std::string &renderer, long long paths, int passes,
-                const std::string &structure, const std::string &light) {
+                const std::string &structure, const std::string &light, const CameraFlags &cflags = CameraFlags()) {
     CudaRenderInit(0);
     PbrtOptions o;
     CudaApiSink sink;
@@ -316,8 +395,9 @@ int render_pbrt(const std::string &path, std::string out, const std::string &ren
     if (!structure.empty()) p.gather_structure = structure == "kd" ? PM_GATHER_KDTREE : PM_GATHER_GRID;
     if (!light.empty()) { p.light_source_index = parse_light(light); check_light(p.light_source_index, o.lights.size()); }
     if (out.empty()) out = o.film_filename;
+    apply_camera_flags(cflags, o.camera);
     CudaRender *render = CreateCudaRenderer(o.settings, o.renderer);
-    PixelFilm film(o.camera.width, o.camera.height, out);
+    PixelFilm film(o.camera.width, o.camera.height, out); /* the device film writes one value per pixel */
     o.camera.film = &film;
     render->Render(o.lights, o.camera);
     if (auto *pm = dynamic_cast<PhotonMappingRenderer *>(render->subRenderer()))
@@ -342,6 +422,7 @@ int main(int argc, char **argv) {
     int passes = 1;
     bool instanced = false, have_cam = false, paths_set = false, passes_set = false;
     float cam[12] = {0};
+    CameraFlags cflags;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -361,6 +442,10 @@ int main(int argc, char **argv) {
         else if (a == "--pbrt") pbrt = next();
         else if (a == "--dump") dump_only = true;
         else if (a == "--out") out = next();
+        else if (a == "--spp") cflags.spp = next();
+        else if (a == "--filter") cflags.filter = next();
+        else if (a == "--lens") cflags.lens = next();
+        else if (a == "--no-jitter") cflags.no_jitter = true;
         else if (a == "--camera") {
             for (float &c : cam) c = std::strtof(next(), nullptr);
             have_cam = true;
@@ -368,12 +453,16 @@ int main(int argc, char **argv) {
     }
     if (!pbrt.empty()) {
         try {
-            if (dump_only) return dump(pbrt);
-            return render_pbrt(pbrt, out, renderer, paths_set ? paths : 0, passes_set ? passes : 0, structure, light);
+            if (dump_only) return dump(pbrt, cflags);
+            return render_pbrt(pbrt, out, renderer, paths_set ? paths : 0, passes_set ? passes : 0, structure, light, cflags);
         } catch (const Error &e) {
             std::fprintf(stderr, "pm_render_cli: %s\n", e.what());
             return 1;
         }
+    }
+    if (cflags.any()) {
+        std::fprintf(stderr, "--spp, --filter, --lens and --no-jitter need --pbrt scene.pbrt\n");
+        return 2;
     }
     if (out.empty()) out = "out.pfm";
     if (scene != "cornell" || !have_cam) {

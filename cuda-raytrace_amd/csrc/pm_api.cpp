@@ -90,6 +90,12 @@ struct Ctx {
     std::vector<LightTri> light_tris; /* the mesh lights' emitting triangles, light after light (SceneDev::light_tris) */
     int rand2d_total = 0;
     int pinhole = 0, W = 0, H = 0;
+    /* pm_set_camera: pinhole = 1 and W x H the sample raster (image * strata),
+     * so records, views and bands are the pinhole's; cam keeps the image size,
+     * the sampling state and the filter, film_table its weights */
+    int camera = 0;
+    pm_camera cam{};
+    DevBuf d_film_table, d_img;
     float eye[3] = {0}, fwd[3] = {0}, right[3] = {0}, up[3] = {0};
     std::vector<float> rays, rand2d;
     int64_t nrays = 0;
@@ -875,7 +881,7 @@ void pm_destroy(void *ptr) {
                       &c->d_dl, &c->d_slots, &c->d_count, &c->d_scratch, &c->d_vflags, &c->d_vrank, &c->d_vlist, &c->d_vsums,
                       &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times, &c->d_tile_cost, &c->d_tiles2,
                       &c->d_kd, &c->d_out, &c->d_counters, &c->d_tiles, &c->d_tile_flags, &c->d_tile_count,
-                      &c->d_r2hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf};
+                      &c->d_r2hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf, &c->d_film_table, &c->d_img};
     for (DevBuf *b : bufs) b->release();
     if (c->tile_event) (void)hipEventDestroy(c->tile_event);
     if (c->r2_event) (void)hipEventDestroy(c->r2_event);
@@ -1140,7 +1146,7 @@ int pm_set_pinhole(void *ptr, const float eye[3], const float fwd[3], const floa
     for (int a = 0; a < 3; ++a)
         if (!(fabsf(eye[a]) <= PM_MAX_RAY_ORIGIN) || !std::isfinite(fwd[a]) || !std::isfinite(right[a]) || !std::isfinite(up[a]))
             FAIL(c, PM_ERR_INVALID, "pinhole camera: eye beyond 2^20 or a non-finite vector");
-    c->pinhole = 1; c->W = W; c->H = H;
+    c->pinhole = 1; c->W = W; c->H = H; c->camera = 0;
     std::memcpy(c->eye, eye, 12); std::memcpy(c->fwd, fwd, 12);
     std::memcpy(c->right, right, 12); std::memcpy(c->up, up, 12);
     return PM_OK;
@@ -1155,7 +1161,7 @@ int pm_set_eye_rays(void *ptr, const float *rays, int64_t nrays, const float *ra
         for (int a = 0; a < 3; ++a)
             if (!(fabsf(rays[6 * i + a]) <= PM_MAX_RAY_ORIGIN) || !std::isfinite(rays[6 * i + 3 + a]))
                 FAIL(c, PM_ERR_INVALID, "ray %lld: origin beyond 2^20 or a non-finite component", (long long)i);
-    c->pinhole = 0;
+    c->pinhole = 0; c->camera = 0;
     c->nrays = nrays;
     c->rays.assign(rays, rays + 6 * nrays);
     c->n2d = (rand2d && n2d > 0) ? n2d : 0;
@@ -1168,6 +1174,146 @@ int pm_set_eye_rays(void *ptr, const float *rays, int64_t nrays, const float *ra
         HIPCHK(c, hipMemcpy(c->d_rand2d.p, c->rand2d.data(), c->rand2d.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     return PM_OK;
+}
+
+/* ---- camera + film (pm_api.h pm_set_camera) ------------------------------ */
+static bool real_filter(const pm_filter &f) { return f.type != PM_FILTER_NONE; }
+
+int pm_film_filter_table(const pm_filter *f, float out[PM_FILM_TABLE * PM_FILM_TABLE]) {
+    if (!f || !out) { g_last_error = "pm_film_filter_table: null pointer"; return PM_ERR_INVALID; }
+    if (f->type < PM_FILTER_BOX || f->type > PM_FILTER_MITCHELL || !(f->xwidth > 0.f && f->xwidth <= 4.f) ||
+        !(f->ywidth > 0.f && f->ywidth <= 4.f)) {
+        g_last_error = "pm_film_filter_table: unknown filter type or a width outside (0, 4]";
+        return PM_ERR_INVALID;
+    }
+    const double xw = f->xwidth, yw = f->ywidth, a = f->a, b = f->b;
+    auto gauss = [&](double t, double w) { return std::max(0.0, std::exp(-a * t * t) - std::exp(-a * w * w)); };
+    auto mitchell = [&](double x) { /* pbrt-v2 MitchellFilter::Mitchell1D, B = a, C = b */
+        const double t = std::fabs(2.0 * x);
+        if (t > 1.0)
+            return ((-a - 6 * b) * t * t * t + (6 * a + 30 * b) * t * t + (-12 * a - 48 * b) * t + (8 * a + 24 * b)) / 6.0;
+        return ((12 - 9 * a - 6 * b) * t * t * t + (-18 + 12 * a + 6 * b) * t * t + (6 - 2 * a)) / 6.0;
+    };
+    for (int j = 0; j < PM_FILM_TABLE; ++j)
+        for (int i = 0; i < PM_FILM_TABLE; ++i) {
+            const double x = (i + 0.5) / PM_FILM_TABLE * xw, y = (j + 0.5) / PM_FILM_TABLE * yw;
+            double v = 1.0;
+            switch (f->type) {
+            case PM_FILTER_TRIANGLE: v = std::max(0.0, xw - std::fabs(x)) * std::max(0.0, yw - std::fabs(y)); break;
+            case PM_FILTER_GAUSSIAN: v = gauss(x, xw) * gauss(y, yw); break;
+            case PM_FILTER_MITCHELL: v = mitchell(x / xw) * mitchell(y / yw); break;
+            default: break;
+            }
+            out[j * PM_FILM_TABLE + i] = (float)v;
+        }
+    return PM_OK;
+}
+
+int pm_set_camera(void *ptr, const pm_camera *cam) {
+    GROUP_FWD(ptr, pm_set_camera(sub, cam));
+    GETCTX(ptr);
+    if (!cam) FAIL(c, PM_ERR_INVALID, "null camera");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(cam->eye[a]) || !std::isfinite(cam->fwd[a]) || !std::isfinite(cam->right[a]) ||
+            !std::isfinite(cam->up[a]))
+            FAIL(c, PM_ERR_INVALID, "camera: a non-finite vector");
+    if (cam->width <= 0 || cam->height <= 0) FAIL(c, PM_ERR_INVALID, "camera: bad image size");
+    if (cam->xsamples < 1 || cam->xsamples > 8 || cam->ysamples < 1 || cam->ysamples > 8)
+        FAIL(c, PM_ERR_INVALID, "camera: %d x %d samples per pixel (1..8 each)", cam->xsamples, cam->ysamples);
+    const int64_t WS = (int64_t)cam->width * cam->xsamples, HS = (int64_t)cam->height * cam->ysamples;
+    if (WS >= (1ll << 31) || HS >= (1ll << 31) || WS * HS >= (1ll << 31))
+        FAIL(c, PM_ERR_INVALID, "camera: %lld x %lld samples (2^31 or more)", (long long)WS, (long long)HS);
+    if (!(cam->lens_radius >= 0.f) || !std::isfinite(cam->lens_radius))
+        FAIL(c, PM_ERR_INVALID, "camera: lens_radius must be >= 0");
+    if (cam->lens_radius > 0.f && !(cam->focal_distance > 0.f && std::isfinite(cam->focal_distance)))
+        FAIL(c, PM_ERR_INVALID, "camera: a lens needs a focal_distance > 0");
+    for (int a = 0; a < 3; ++a)
+        if (!(fabsf(cam->eye[a]) + cam->lens_radius <= PM_MAX_RAY_ORIGIN))
+            FAIL(c, PM_ERR_INVALID, "camera: eye + lens_radius beyond 2^20");
+    const pm_filter &f = cam->filter;
+    if (f.type < PM_FILTER_NONE || f.type > PM_FILTER_MITCHELL) FAIL(c, PM_ERR_INVALID, "camera: unknown filter type %d", f.type);
+    float table[PM_FILM_TABLE * PM_FILM_TABLE];
+    if (real_filter(f)) {
+        /* film positions are fp32 pixel coordinates: beyond 2^20 samples per
+         * axis they no longer resolve a stratum (and k_film's halo margin,
+         * pm_film.hip film_halo, is sized for this bound) */
+        if (WS > (1 << 20) || HS > (1 << 20))
+            FAIL(c, PM_ERR_INVALID, "camera: a filmed raster of %lld x %lld samples (2^20 per axis at most)", (long long)WS, (long long)HS);
+        if (!(f.xwidth > 0.f && f.xwidth <= 4.f) || !(f.ywidth > 0.f && f.ywidth <= 4.f))
+            FAIL(c, PM_ERR_INVALID, "camera: filter width (%g, %g) outside (0, 4]", f.xwidth, f.ywidth);
+        if (pm_film_filter_table(&f, table)) FAIL(c, PM_ERR_INVALID, "camera: bad filter");
+        HIPCHK(c, c->d_film_table.ensure(sizeof(table)));
+        HIPCHK(c, hipMemcpy(c->d_film_table.p, table, sizeof(table), hipMemcpyHostToDevice));
+    }
+    c->cam = *cam;
+    c->camera = 1; c->pinhole = 1; c->W = (int)WS; c->H = (int)HS;
+    std::memcpy(c->eye, cam->eye, 12); std::memcpy(c->fwd, cam->fwd, 12);
+    std::memcpy(c->right, cam->right, 12); std::memcpy(c->up, cam->up, 12);
+    return PM_OK;
+}
+
+/* the eye kernels' camera block (all of it the pinhole's when no camera is set) */
+static void eye_camera(const Ctx *c, EyeParams &E) {
+    E.pinhole = c->pinhole; E.W = c->W; E.H = c->H; E.n2d = c->n2d;
+    E.eye = make_float4(c->eye[0], c->eye[1], c->eye[2], 0); E.fwd = make_float4(c->fwd[0], c->fwd[1], c->fwd[2], 0);
+    E.right = make_float4(c->right[0], c->right[1], c->right[2], 0); E.up = make_float4(c->up[0], c->up[1], c->up[2], 0);
+    E.camera = c->camera;
+    if (c->camera) {
+        E.cam.xs = c->cam.xsamples; E.cam.ys = c->cam.ysamples; E.cam.jitter = c->cam.jitter != 0;
+        E.cam.lens_radius = c->cam.lens_radius; E.cam.focal = c->cam.focal_distance; E.cam.seed = c->cam.sample_seed;
+    }
+}
+
+static bool has_film(const Ctx *c) { return c->camera && real_filter(c->cam.filter); }
+
+int pm_film(void *ptr, const void *d_samples, void *d_image, void *stream) {
+    if (Group *g_ = group_of(ptr)) { /* the assembled raster is filmed on the first device */
+        (void)hipSetDevice(g_->subs[0]->device);
+        const int rc_ = pm_film(g_->subs[0], d_samples, d_image, stream);
+        return rc_ ? group_fail(ptr, g_->subs[0], rc_) : PM_OK;
+    }
+    GETCTX(ptr);
+    if (!has_film(c)) FAIL(c, PM_ERR_INVALID, "pm_film: no camera with a filter (pm_set_camera)");
+    if (!d_samples || !d_image) FAIL(c, PM_ERR_INVALID, "pm_film: null buffer");
+    hipStream_t s = pick(c, stream);
+    EyeParams E{};
+    eye_camera(c, E);
+    FilmParams F{};
+    F.samples = (const float *)d_samples; F.image = (float *)d_image; F.table = c->d_film_table.as<float>();
+    F.W = c->cam.width; F.H = c->cam.height; F.WS = c->W; F.HS = c->H;
+    F.cam = E.cam;
+    F.xw = c->cam.filter.xwidth; F.yw = c->cam.filter.ywidth;
+    F.inv_xw = 1.0f / F.xw; F.inv_yw = 1.0f / F.yw;
+    timer_begin(c, "film", s);
+    HIPCHK(c, launch_film(F, s));
+    timer_end(c, "film", s);
+    return PM_OK;
+}
+
+int pm_camera_rays(void *ptr, int64_t first, int64_t count, float *rays6, float *film_xy) {
+    if (Group *g_ = group_of(ptr)) {
+        (void)hipSetDevice(g_->subs[0]->device);
+        const int rc_ = pm_camera_rays(g_->subs[0], first, count, rays6, film_xy);
+        return rc_ ? group_fail(ptr, g_->subs[0], rc_) : PM_OK;
+    }
+    GETCTX(ptr);
+    if (!c->camera) FAIL(c, PM_ERR_INVALID, "pm_camera_rays: no camera (pm_set_camera)");
+    if (first < 0 || count < 0 || first + count > (int64_t)c->W * c->H) FAIL(c, PM_ERR_INVALID, "pm_camera_rays: bad sample range");
+    if (count == 0) return PM_OK;
+    EyeParams E{};
+    eye_camera(c, E);
+    DevBuf d_r, d_f;
+    int rc = PM_OK;
+    hipError_t e = hipSuccess;
+    if (rays6) e = d_r.ensure((size_t)count * 6 * sizeof(float));
+    if (e == hipSuccess && film_xy) e = d_f.ensure((size_t)count * 2 * sizeof(float));
+    if (e == hipSuccess) e = launch_camera_rays(E, first, count, d_r.as<float>(), d_f.as<float>(), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && rays6) e = hipMemcpy(rays6, d_r.p, (size_t)count * 6 * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && film_xy) e = hipMemcpy(film_xy, d_f.p, (size_t)count * 2 * sizeof(float), hipMemcpyDeviceToHost);
+    d_r.release(); d_f.release();
+    if (e != hipSuccess) { c->err = std::string("pm_camera_rays: ") + hipGetErrorString(e); g_last_error = c->err; rc = PM_ERR_HIP; }
+    return rc;
 }
 
 /* the object meshes of an instanced scene (two-level trees) */
@@ -1660,9 +1806,7 @@ int pm_eye_pass(void *ptr, const pm_render_params *p, void *stream) {
     EyeParams E{};
     E.S = c->S;
     E.R = recs(c);
-    E.pinhole = c->pinhole; E.W = c->W; E.H = c->H; E.n2d = c->n2d;
-    E.eye = f4(c->eye[0], c->eye[1], c->eye[2], 0); E.fwd = f4(c->fwd[0], c->fwd[1], c->fwd[2], 0);
-    E.right = f4(c->right[0], c->right[1], c->right[2], 0); E.up = f4(c->up[0], c->up[1], c->up[2], 0);
+    eye_camera(c, E);
     E.rays = c->d_rays.as<float>(); E.rand2d = c->d_rand2d.as<float>();
     E.eps = p->scene_epsilon; E.r2init = p->initial_radius2; E.max_spec = p->max_specular_depth;
     E.light_seed = p->light_rng_seed;
@@ -2460,6 +2604,12 @@ static int group_render(Ctx *gc, const pm_render_params *p, float *out_rgb, pm_s
     /* final radiance of each device's bands, straight into the host image */
     const double emitted = (double)P * p->passes;
     const int64_t nout = c0->pinhole ? (int64_t)c0->W * c0->H : nrec;
+    /* with a film the bands assemble the sample raster on the host first; it
+     * is filmed on the first device below */
+    const bool film = has_film(c0);
+    std::vector<float> raster;
+    float *const img_rgb = out_rgb;
+    if (film) { raster.resize((size_t)nout * 3); out_rgb = raster.data(); }
     for (int d = 0; d < n; ++d) {
         Ctx *c = G.subs[d];
         (void)hipSetDevice(c->device);
@@ -2485,6 +2635,15 @@ static int group_render(Ctx *gc, const pm_render_params *p, float *out_rgb, pm_s
         }
     }
     for (int d = 0; d < n; ++d) { (void)hipSetDevice(G.subs[d]->device); HIPCHK(gc, hipStreamSynchronize(G.subs[d]->stream)); }
+    if (film) {
+        (void)hipSetDevice(c0->device);
+        const int64_t nimg = (int64_t)c0->cam.width * c0->cam.height;
+        HIPCHK(gc, c0->d_img.ensure(nimg * 3 * sizeof(float)));
+        HIPCHK(gc, hipMemcpyAsync(c0->d_out.p, raster.data(), raster.size() * sizeof(float), hipMemcpyHostToDevice, c0->stream));
+        if ((rc = pm_film(c0, c0->d_out.p, c0->d_img.p, c0->stream))) return sub_fail(c0, rc);
+        HIPCHK(gc, hipMemcpyAsync(img_rgb, c0->d_img.p, nimg * 3 * sizeof(float), hipMemcpyDeviceToHost, c0->stream));
+        HIPCHK(gc, hipStreamSynchronize(c0->stream));
+    }
     if (st) {
         std::memset(st, 0, sizeof(*st));
         st->paths_emitted = (int64_t)emitted;
@@ -2546,7 +2705,14 @@ int pm_render(void *ptr, const pm_render_params *p, float *out_rgb, pm_stats *st
     timer_begin(c, "final", s);
     HIPCHK(c, launch_final(F, s));
     timer_end(c, "final", s);
-    HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_out.p, nout * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (has_film(c)) { /* sample raster -> image */
+        const int64_t nimg = (int64_t)c->cam.width * c->cam.height;
+        HIPCHK(c, c->d_img.ensure(nimg * 3 * sizeof(float)));
+        if ((rc = pm_film(c, c->d_out.p, c->d_img.p, s))) return rc;
+        HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_img.p, nimg * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_out.p, nout * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(c, hipStreamSynchronize(s));
     t_final = timer_ms(c, "final");
     if (st) {
@@ -2580,9 +2746,7 @@ int pm_simple_pass(void *ptr, const pm_render_params *p, void *d_out, void *stre
     EyeParams E{};
     E.S = c->S;
     E.R.count = n; /* the simple renderer keeps no records */
-    E.pinhole = c->pinhole; E.W = c->W; E.H = c->H; E.n2d = c->n2d;
-    E.eye = f4(c->eye[0], c->eye[1], c->eye[2], 0); E.fwd = f4(c->fwd[0], c->fwd[1], c->fwd[2], 0);
-    E.right = f4(c->right[0], c->right[1], c->right[2], 0); E.up = f4(c->up[0], c->up[1], c->up[2], 0);
+    eye_camera(c, E);
     E.rays = c->d_rays.as<float>(); E.rand2d = c->d_rand2d.as<float>();
     E.eps = p->scene_epsilon; E.light_seed = p->light_rng_seed;
     timer_begin(c, "simple", s);
@@ -2603,7 +2767,14 @@ int pm_render_simple(void *ptr, const pm_render_params *p, float *out_rgb, pm_st
     hipStream_t s = c->stream;
     int rc;
     if ((rc = pm_simple_pass(c, p, c->d_out.p, s))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_out.p, nout * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (has_film(c)) {
+        const int64_t nimg = (int64_t)c->cam.width * c->cam.height;
+        HIPCHK(c, c->d_img.ensure(nimg * 3 * sizeof(float)));
+        if ((rc = pm_film(c, c->d_out.p, c->d_img.p, s))) return rc;
+        HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_img.p, nimg * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_out.p, nout * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(c, hipStreamSynchronize(s));
     if (st) {
         std::memset(st, 0, sizeof(*st));

@@ -66,6 +66,14 @@ struct RecordsDev {
     int64_t count;
 };
 
+/* pm_set_camera's sampling state (pm_api.h pm_camera): the sample raster is
+ * EyeParams::W x H (= image * strata) */
+struct CameraDev {
+    int xs, ys, jitter;
+    float lens_radius, focal;
+    uint32_t seed;
+};
+
 struct EyeParams {
     SceneDev S;
     RecordsDev R;
@@ -76,6 +84,68 @@ struct EyeParams {
     float eps, r2init;
     int max_spec;
     uint32_t light_seed;
+    /* camera != 0 (pm_set_camera): the CAM instantiations of k_eye / k_simple;
+     * pinhole is 1 and W x H the sample raster, so everything but the ray
+     * itself is the pinhole's */
+    int camera;
+    CameraDev cam;
+};
+
+/* the jitter and lens randoms of sample q (pm_api.h pm_set_camera) */
+PMD void camera_randoms(const CameraDev &C, int64_t q, float *ju, float *jv, float *lu, float *lv) {
+    /* uniform per launch: stratum centres through a pinhole use none of the four */
+    if (!C.jitter && !(C.lens_radius > 0.0f)) { *ju = *jv = 0.5f; *lu = *lv = 0.0f; return; }
+    uint32_t o4[4];
+    pmdm_philox4x32_10((uint32_t)((uint64_t)q & 0xffffffffu), (uint32_t)((uint64_t)q >> 32), 1u, 0u, C.seed, 0u, o4);
+    *ju = C.jitter ? pmdm_u01(o4[0]) : 0.5f;
+    *jv = C.jitter ? pmdm_u01(o4[1]) : 0.5f;
+    *lu = pmdm_u01(o4[2]);
+    *lv = pmdm_u01(o4[3]);
+}
+/* film position of sample (ix, iy) with jitter (ju, jv), in pixels */
+PMD void camera_film_xy(const CameraDev &C, int ix, int iy, float ju, float jv, float *fx, float *fy) {
+    *fx = ((float)ix + ju) / (float)C.xs;
+    *fy = ((float)iy + jv) / (float)C.ys;
+}
+/* The camera ray of sample (ix, iy) of the WS x HS raster, in the order of
+ * operations pm_api.h pins: shared by k_eye, k_simple and k_camera_rays. */
+PMD void camera_ray(const CameraDev &C, float4 eye4, float4 fwd4, float4 right4, float4 up4, int WS, int HS, int ix,
+                    int iy, v3 *o, v3 *d, float *fx, float *fy) {
+    float ju, jv, lu, lv;
+    camera_randoms(C, (int64_t)iy * WS + ix, &ju, &jv, &lu, &lv);
+    camera_film_xy(C, ix, iy, ju, jv, fx, fy);
+    const v3 eye = xyz(eye4), fwd = xyz(fwd4), right = xyz(right4), up = xyz(up4);
+    const float sx = (2.0f * ((float)ix + ju)) / (float)WS - 1.0f;
+    const float sy = 1.0f - (2.0f * ((float)iy + jv)) / (float)HS;
+    const v3 d0 = fwd + sx * right + sy * up;
+    if (C.lens_radius > 0.0f) {
+        float cx, cy;
+        concentric_sample_disk(lu, lv, &cx, &cy);
+        const v3 ol = eye + C.lens_radius * (cx * normalize(right) + cy * normalize(up));
+        const float ft = C.focal / sqrtf(dot(fwd, fwd));
+        const v3 pf = eye + d0 * ft;
+        *o = ol;
+        *d = normalize(pf - ol);
+    } else {
+        *o = eye;
+        *d = normalize(d0);
+    }
+}
+
+/* the film (pm_film.hip k_film): one workgroup per FILM_TILE x FILM_TILE
+ * output pixels, the tile's sample footprint staged through LDS in bands of
+ * whole sample rows */
+constexpr int FILM_TILE = 16;
+constexpr int FILM_LDS_SAMPLES = 3072; /* band capacity: 5 planes x 4 B x 3072 = 60 KB, + 1 KB table */
+struct FilmParams {
+    const float *samples; /* float3 x WS * HS, raster order */
+    float *image;         /* float3 x W * H */
+    const float *table;   /* PM_FILM_TABLE^2 weights (pm_film_filter_table) */
+    int W, H, WS, HS;
+    CameraDev cam;
+    float xw, yw, inv_xw, inv_yw;
+    int hx, hy;           /* footprint halo in pixels per side (conservative) */
+    int row_w, band_rows; /* staged row width (samples) and rows per band */
 };
 
 constexpr int R2_BINS = 64, R2_COPIES = 256, R2_PER_OCTAVE = 8; /* radius histogram (adaptive grid) */
@@ -237,6 +307,12 @@ hipError_t launch_eye(const EyeParams &p, hipStream_t s);
 /* simple renderer (simplerender.cu): direct light per eye sample into out
  * (float3, raster / sample order); only p.R.count of the records is read */
 hipError_t launch_simple(const EyeParams &p, float *out, hipStream_t s);
+/* pm_camera_rays: rays6 (o.xyz, d.xyz) and film_xy (fx, fy) of samples
+ * [first, first + count) of p's camera (device buffers; either may be null) */
+hipError_t launch_camera_rays(const EyeParams &p, int64_t first, int64_t count, float *rays6, float *film_xy,
+                              hipStream_t s);
+/* the film (pm_film.hip): fills hx / hy / row_w / band_rows of p itself */
+hipError_t launch_film(FilmParams p, hipStream_t s);
 /* writes every slot of its paths (deposits, then zeros); count: census */
 /* resident waves of k_trace_pool per CU with `lds` bytes of dynamic LDS per block */
 int trace_pool_waves_per_cu(size_t lds, int hold, int w8 = 0);

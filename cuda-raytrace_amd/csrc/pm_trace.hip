@@ -20,7 +20,10 @@ namespace pm {
 /* ====================================================================== */
 /* eye pass                                                               */
 /* ====================================================================== */
-template <int MODE>
+/* CAM: the rays of pm_set_camera (camera_ray, pm_kernels.h) over the sample
+ * raster P.W x P.H; uniform per launch, so the pinhole / host-ray
+ * instantiations (CAM = false) carry none of it */
+template <int MODE, bool CAM = false>
 __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
     extern __shared__ __attribute__((aligned(16))) int stk[]; /* [stack_depth x EYE_BLOCK][scene blob (LDS)] */
     int *stack = stk + threadIdx.x;
@@ -33,7 +36,18 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
     Ray ray;
     int64_t pixel;
     float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (P.pinhole) {
+    if (CAM) {
+        int px, py;
+        rec_to_pixel(r, P.W, &px, &py);
+        if (px >= P.W || py >= P.H) {
+            P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float(PM_REC_INVALID));
+            P.R.nrm[r] = zero4; P.R.state[r] = zero4; P.R.n[r] = 0.f; P.R.dl[r] = zero4;
+            return;
+        }
+        pixel = (int64_t)py * P.W + px; /* the sample index q: keys the light samples below */
+        float fx, fy;
+        camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, px, py, &ray.o, &ray.d, &fx, &fy);
+    } else if (P.pinhole) {
         int px, py;
         rec_to_pixel(r, P.W, &px, &py);
         if (px >= P.W || py >= P.H) {
@@ -132,6 +146,15 @@ hipError_t launch_eye(const EyeParams &p, hipStream_t s) {
     if (p.R.count <= 0) return hipSuccess;
     unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
     const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
+    if (p.camera) {
+        switch (scene_mode(p.S)) {
+        case MODE_BRUTE: pm_launch(k_eye<MODE_BRUTE, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+        case MODE_LDS: pm_launch(k_eye<MODE_LDS, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+        case MODE_INST: pm_launch(k_eye<MODE_INST, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+        default: pm_launch(k_eye<MODE_GLOBAL, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+        }
+        return hipGetLastError();
+    }
     switch (scene_mode(p.S)) {
     case MODE_BRUTE: pm_launch(k_eye<MODE_BRUTE>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
     case MODE_LDS: pm_launch(k_eye<MODE_LDS>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
@@ -150,7 +173,7 @@ hipError_t launch_eye(const EyeParams &p, hipStream_t s) {
  * a miss is black (:75-79). The host's NaN / negative / infinite check
  * (simplerender.cpp:70-87) is fused into the store. Output: raster order
  * (pinhole) or sample order (host rays), float3 per sample. */
-template <int MODE>
+template <int MODE, bool CAM = false>
 __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
     extern __shared__ __attribute__((aligned(16))) int stk[];
     int *stack = stk + threadIdx.x;
@@ -162,7 +185,14 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
 
     Ray ray;
     int64_t pixel;
-    if (P.pinhole) {
+    if (CAM) {
+        int px, py;
+        rec_to_pixel(r, P.W, &px, &py);
+        if (px >= P.W || py >= P.H) return;
+        pixel = (int64_t)py * P.W + px;
+        float fx, fy;
+        camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, px, py, &ray.o, &ray.d, &fx, &fy);
+    } else if (P.pinhole) {
         int px, py;
         rec_to_pixel(r, P.W, &px, &py);
         if (px >= P.W || py >= P.H) return;
@@ -223,12 +253,46 @@ hipError_t launch_simple(const EyeParams &p, float *out, hipStream_t s) {
     if (p.R.count <= 0) return hipSuccess;
     unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
     const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
+    if (p.camera) {
+        switch (scene_mode(p.S)) {
+        case MODE_BRUTE: pm_launch(k_simple<MODE_BRUTE, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
+        case MODE_LDS: pm_launch(k_simple<MODE_LDS, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
+        case MODE_INST: pm_launch(k_simple<MODE_INST, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
+        default: pm_launch(k_simple<MODE_GLOBAL, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
+        }
+        return hipGetLastError();
+    }
     switch (scene_mode(p.S)) {
     case MODE_BRUTE: pm_launch(k_simple<MODE_BRUTE>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
     case MODE_LDS: pm_launch(k_simple<MODE_LDS>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
     case MODE_INST: pm_launch(k_simple<MODE_INST>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
     default: pm_launch(k_simple<MODE_GLOBAL>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
     }
+    return hipGetLastError();
+}
+
+/* pm_camera_rays: the rays and film positions of samples [first, first +
+ * count) in raster order, through camera_ray as the eye pass calls it */
+__global__ __launch_bounds__(256) void k_camera_rays(EyeParams P, int64_t first, int64_t count, float *rays6,
+                                                     float *film_xy) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int64_t q = first + i;
+    const int ix = (int)(q % P.W), iy = (int)(q / P.W);
+    v3 o, d;
+    float fx, fy;
+    camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, ix, iy, &o, &d, &fx, &fy);
+    if (rays6) {
+        float *r = rays6 + 6 * i;
+        r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
+    }
+    if (film_xy) { film_xy[2 * i] = fx; film_xy[2 * i + 1] = fy; }
+}
+
+hipError_t launch_camera_rays(const EyeParams &p, int64_t first, int64_t count, float *rays6, float *film_xy,
+                              hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    pm_launch(k_camera_rays, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, p, first, count, rays6, film_xy);
     return hipGetLastError();
 }
 

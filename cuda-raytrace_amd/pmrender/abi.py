@@ -20,6 +20,11 @@ PM_ESTIMATOR_PPM, PM_ESTIMATOR_KNN = 0, 1
 PM_KNN_MAX = 64
 PM_ALL_LIGHTS = -1  # light_source_index: photon paths start on every light, picked by power
 PM_PHOTON_MAX_RIGHT_CHILD = (1 << 29) - 1
+# pm_filter::type; PM_FILM_TABLE: the film's weight table is 16 x 16 (pbrt ImageFilm)
+PM_FILTER_NONE, PM_FILTER_BOX, PM_FILTER_TRIANGLE, PM_FILTER_GAUSSIAN, PM_FILTER_MITCHELL = 0, 1, 2, 3, 4
+PM_FILM_TABLE = 16
+FILTER_TYPES = {"none": PM_FILTER_NONE, "box": PM_FILTER_BOX, "triangle": PM_FILTER_TRIANGLE,
+                "gaussian": PM_FILTER_GAUSSIAN, "mitchell": PM_FILTER_MITCHELL}
 
 # pm_photon == reference CudaPhoton (photon_mapping/photonmapping.h:32-41), 40 B
 PHOTON_DTYPE = np.dtype([("bits", "<u4"), ("p", "<f4", 3), ("alpha", "<f4", 3), ("wi", "<f4", 3)])
@@ -41,6 +46,54 @@ class PMConfig(ctypes.Structure):
         ("device", ctypes.c_int),
         ("n_devices", ctypes.c_int),
         ("devices", ctypes.POINTER(ctypes.c_int)),
+        ("reserved", ctypes.c_int * 4),
+    ]
+
+
+class Filter(ctypes.Structure):
+    """include/pm_api.h pm_filter (20 B): a = gaussian alpha / mitchell B, b = mitchell C."""
+    _fields_ = [
+        ("type", ctypes.c_int),
+        ("xwidth", ctypes.c_float),
+        ("ywidth", ctypes.c_float),
+        ("a", ctypes.c_float),
+        ("b", ctypes.c_float),
+    ]
+
+    # pbrt-v2's defaults per filter: (xwidth, ywidth, a, b)
+    DEFAULTS = {PM_FILTER_NONE: (0.0, 0.0, 0.0, 0.0), PM_FILTER_BOX: (0.5, 0.5, 0.0, 0.0),
+                PM_FILTER_TRIANGLE: (2.0, 2.0, 0.0, 0.0), PM_FILTER_GAUSSIAN: (2.0, 2.0, 2.0, 0.0),
+                PM_FILTER_MITCHELL: (2.0, 2.0, 1.0 / 3.0, 1.0 / 3.0)}
+
+    @classmethod
+    def make(cls, kind="none", xwidth=None, ywidth=None, a=None, b=None):
+        """kind: a name of FILTER_TYPES, a PM_FILTER_* value or a Filter; missing
+        parameters take pbrt's defaults (ywidth: xwidth when only that is given)."""
+        if isinstance(kind, cls):
+            return kind
+        t = FILTER_TYPES[kind] if isinstance(kind, str) else int(kind)
+        d = cls.DEFAULTS.get(t, (0.0, 0.0, 0.0, 0.0))
+        xw = d[0] if xwidth is None else xwidth
+        yw = (d[1] if xwidth is None else xw) if ywidth is None else ywidth
+        return cls(t, xw, yw, d[2] if a is None else a, d[3] if b is None else b)
+
+
+class Camera(ctypes.Structure):
+    """include/pm_api.h pm_camera (116 B)."""
+    _fields_ = [
+        ("eye", ctypes.c_float * 3),
+        ("fwd", ctypes.c_float * 3),
+        ("right", ctypes.c_float * 3),
+        ("up", ctypes.c_float * 3),
+        ("width", ctypes.c_int),
+        ("height", ctypes.c_int),
+        ("xsamples", ctypes.c_int),
+        ("ysamples", ctypes.c_int),
+        ("jitter", ctypes.c_int),
+        ("lens_radius", ctypes.c_float),
+        ("focal_distance", ctypes.c_float),
+        ("sample_seed", ctypes.c_uint32),
+        ("filter", Filter),
         ("reserved", ctypes.c_int * 4),
     ]
 

@@ -9,8 +9,8 @@ import os
 
 import numpy as np
 
-from .abi import (LIGHT_TRI_DTYPE, PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PMConfig, RenderParams, Stats, f32, fptr, iptr,
-                  record_pixels)
+from .abi import (LIGHT_TRI_DTYPE, PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PM_FILM_TABLE, PM_FILTER_NONE, Camera,
+                  Filter, PMConfig, RenderParams, Stats, f32, fptr, iptr, record_pixels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libpmhip.so")
@@ -56,6 +56,10 @@ def load_library(path=None):
         "pm_add_light_mesh": (c_int, [vp, P_f, c_int, P_i, c_int, c_int, P_f, c_int, P_i]),
         "pm_set_pinhole": (c_int, [vp, P_f, P_f, P_f, P_f, c_int, c_int]),
         "pm_set_eye_rays": (c_int, [vp, P_f, i64, P_f, c_int]),
+        "pm_set_camera": (c_int, [vp, ctypes.POINTER(Camera)]),
+        "pm_film": (c_int, [vp, vp, vp, vp]),
+        "pm_camera_rays": (c_int, [vp, i64, i64, P_f, P_f]),
+        "pm_film_filter_table": (c_int, [ctypes.POINTER(Filter), P_f]),
         "pm_commit": (c_int, [vp]),
         "pm_render": (c_int, [vp, ctypes.POINTER(RenderParams), P_f, ctypes.POINTER(Stats)]),
         "pm_render_simple": (c_int, [vp, ctypes.POINTER(RenderParams), P_f, ctypes.POINTER(Stats)]),
@@ -136,6 +140,18 @@ def light_selection_cdf(types, le_rgb, areas):
     return out[:n]
 
 
+def film_filter_table(filt, **kw):
+    """The film's 16 x 16 weight table (pm_film_filter_table; host only): filt is a Filter or
+    the arguments of Filter.make. Raises ValueError where the call returns PM_ERR_INVALID."""
+    lib = load_library()
+    f = Filter.make(filt, **kw)
+    out = np.zeros((PM_FILM_TABLE, PM_FILM_TABLE), dtype=np.float32)
+    rc = lib.pm_film_filter_table(ctypes.byref(f), fptr(out))
+    if rc != 0:
+        raise ValueError(f"pm_film_filter_table failed ({rc}): {lib.pm_last_error(None).decode()}")
+    return out
+
+
 def kdtree_build_host(slots):
     """Canonical pbrt-v2 kd-tree over the valid slots (host, reference layout)."""
     lib = load_library()
@@ -167,6 +183,7 @@ class Context:
         self.devices = list(devices) if devices is not None else [device]
         self.width = self.height = 0
         self.pinhole = False
+        self.camera = None  # the Camera of set_camera; width x height is then the sample raster
 
     def close(self):
         if getattr(self, "h", None):
@@ -240,15 +257,49 @@ class Context:
         return out.value
 
     def set_pinhole(self, eye, fwd, right, up, W, H):
-        self.width, self.height, self.pinhole = int(W), int(H), True
+        self.width, self.height, self.pinhole, self.camera = int(W), int(H), True, None
         self._chk(self.lib.pm_set_pinhole(self.h, fptr(f32(eye, 3)), fptr(f32(fwd, 3)), fptr(f32(right, 3)),
                                           fptr(f32(up, 3)), int(W), int(H)))
 
     def set_eye_rays(self, rays, rand2d=None, n2d=0):
         rays = f32(rays)
         rand2d = f32(rand2d)
-        self.width, self.height, self.pinhole = rays.size // 6, 1, False
+        self.width, self.height, self.pinhole, self.camera = rays.size // 6, 1, False, None
         self._chk(self.lib.pm_set_eye_rays(self.h, fptr(rays), rays.size // 6, fptr(rand2d), int(n2d)))
+
+    def set_camera(self, eye, fwd, right, up, W, H, xsamples=1, ysamples=1, jitter=True, lens_radius=0.0,
+                   focal_distance=0.0, sample_seed=0, filter="none", **filter_kw):
+        """The supersampled thin-lens camera with its film (pm_set_camera). W x H is the image;
+        the context then works on the (W xsamples) x (H ysamples) sample raster (self.width x
+        self.height, as after set_pinhole at that size). filter: a Filter or the arguments of
+        Filter.make ("none": render() returns the sample raster)."""
+        cam = Camera()
+        cam.eye[:], cam.fwd[:], cam.right[:], cam.up[:] = f32(eye, 3), f32(fwd, 3), f32(right, 3), f32(up, 3)
+        cam.width, cam.height, cam.xsamples, cam.ysamples = int(W), int(H), int(xsamples), int(ysamples)
+        cam.jitter, cam.lens_radius, cam.focal_distance = int(bool(jitter)), float(lens_radius), float(focal_distance)
+        cam.sample_seed = int(sample_seed)
+        cam.filter = Filter.make(filter, **filter_kw)
+        self._chk(self.lib.pm_set_camera(self.h, ctypes.byref(cam)))
+        self.width, self.height, self.pinhole, self.camera = cam.width * cam.xsamples, cam.height * cam.ysamples, True, cam
+
+    def film(self, d_samples, d_image, stream=None):
+        """pm_film: device float3 sample raster (width x height) -> device float3 image."""
+        self._chk(self.lib.pm_film(self.h, ctypes.c_void_p(d_samples), ctypes.c_void_p(d_image), stream))
+
+    def camera_rays(self, first=0, count=None):
+        """(rays (count, 6), film_xy (count, 2)) of samples [first, first + count) of the sample
+        raster, computed by the device function the eye pass calls (pm_camera_rays)."""
+        if count is None:
+            count = self.width * self.height - first
+        rays, xy = np.zeros((count, 6), np.float32), np.zeros((count, 2), np.float32)
+        self._chk(self.lib.pm_camera_rays(self.h, int(first), int(count), fptr(rays), fptr(xy)))
+        return rays, xy
+
+    def _out_shape(self):
+        """(H, W) of what render() / render_simple() write for a device camera."""
+        if self.camera is not None and self.camera.filter.type != PM_FILTER_NONE:
+            return self.camera.height, self.camera.width
+        return self.height, self.width
 
     def commit(self):
         self._chk(self.lib.pm_commit(self.h))
@@ -256,23 +307,25 @@ class Context:
     # ---- whole render --------------------------------------------------------
     def render(self, params=None):
         params = params or RenderParams.defaults()
-        n = self.width * self.height if self.pinhole else self.num_records()
+        oh, ow = self._out_shape()
+        n = oh * ow if self.pinhole else self.num_records()
         out = np.zeros((n, 3), np.float32)
         st = Stats()
         self._chk(self.lib.pm_render(self.h, ctypes.byref(params), fptr(out), ctypes.byref(st)))
         if self.pinhole:
-            out = out.reshape(self.height, self.width, 3)
+            out = out.reshape(oh, ow, 3)
         return out, st.as_dict()
 
     def render_simple(self, params=None):
         """SimpleRenderer (simplerender.cpp:18-103): direct light only."""
         params = params or RenderParams.simple_defaults()
-        n = self.width * self.height if self.pinhole else self.num_records()
+        oh, ow = self._out_shape()
+        n = oh * ow if self.pinhole else self.num_records()
         out = np.zeros((n, 3), np.float32)
         st = Stats()
         self._chk(self.lib.pm_render_simple(self.h, ctypes.byref(params), fptr(out), ctypes.byref(st)))
         if self.pinhole:
-            out = out.reshape(self.height, self.width, 3)
+            out = out.reshape(oh, ow, 3)
         return out, st.as_dict()
 
     def simple_pass(self, params, d_out, stream=None):

@@ -128,6 +128,8 @@ class Scene:
         cam = self.camera
         if cam[0] == "pinhole":
             api.set_pinhole(*cam[1:])
+        elif cam[0] == "camera":  # the device camera + film (pm_set_camera): HIP contexts only
+            api.set_camera(*cam[1:7], **cam[7])
         else:
             api.set_eye_rays(*cam[1:])
         api.commit()
@@ -135,11 +137,11 @@ class Scene:
 
     @property
     def width(self):
-        return self.camera[5] if self.camera[0] == "pinhole" else len(self.camera[1])
+        return self.camera[5] if self.camera[0] in ("pinhole", "camera") else len(self.camera[1])
 
     @property
     def height(self):
-        return self.camera[6] if self.camera[0] == "pinhole" else 1
+        return self.camera[6] if self.camera[0] in ("pinhole", "camera") else 1
 
 
 def pinhole(W, H, eye=(278.0, 273.0, -800.0), look=(278.0, 273.0, 0.0), up=(0.0, 1.0, 0.0), fov_deg=39.3):
@@ -155,6 +157,16 @@ def pinhole(W, H, eye=(278.0, 273.0, -800.0), look=(278.0, 273.0, 0.0), up=(0.0,
     t = math.tan(math.radians(fov_deg) / 2.0)
     sx, sy = (t * W / H, t) if W >= H else (t, t * H / W)
     return ("pinhole", np.float32(e), np.float32(f), np.float32(r * sx), np.float32(u * sy), int(W), int(H))
+
+
+def device_camera(W, H, xsamples=1, ysamples=1, jitter=True, lens_radius=0.0, focal_distance=0.0, sample_seed=0,
+                  filter="none", filter_kw=None, **view):
+    """pinhole()'s view as the supersampled thin-lens camera with its film
+    (Context.set_camera): ("camera", eye, fwd, right, up, W, H, settings)."""
+    cam = pinhole(W, H, **view)
+    kw = dict(xsamples=xsamples, ysamples=ysamples, jitter=jitter, lens_radius=lens_radius,
+              focal_distance=focal_distance, sample_seed=sample_seed, filter=filter, **(filter_kw or {}))
+    return ("camera",) + cam[1:] + (kw,)
 
 
 def _ceiling_light(scene, Le=17.0, radius=65.0, nsamples=1, material=None):

@@ -23,6 +23,7 @@
  *   pm_add_light_mesh             (new: the reference emits from disks only, cudalight.cpp:35-56)
  *   pm_set_eye_rays               PbrtCamera::preLaunch (bRays, bRandom2D) util/camera/pbrtcamera.cpp:57-122
  *   pm_set_pinhole                (on-device eye rays for synthetic benches)
+ *   pm_set_camera / pm_film       (new: pbrt-v2 PerspectiveCamera::GenerateRay, StratifiedSampler, ImageFilm)
  *   pm_commit                     CudaRender::Render → assembleNode (Sbvh build)  cudarender.cpp:38-75,112-123
  *   pm_render                     PhotonMappingRenderer::render    photon_mapping/photonmappingrenderer.cpp:31-45
  *   pm_eye_pass                   RaytracingPass                   photonmappingrenderer.cpp:108-139 (+ raytracing.cu)
@@ -242,6 +243,78 @@ int pm_set_pinhole(void *ctx, const float eye[3], const float fwd[3], const floa
  * packs them (o.xyz, d.xyz per ray; rand2d = n2d float2 per ray, indexed
  * [ray][random2DStart + s], cudalight.cu.h:34-35). */
 int pm_set_eye_rays(void *ctx, const float *rays, int64_t nrays, const float *rand2d, int n2d);
+
+/* ... or a supersampled thin-lens camera with an on-device filtered film
+ * (pbrt-v2's perspective camera, stratified sampler and ImageFilm).
+ *
+ * Sample raster: WS = width * xsamples, HS = height * ysamples; sample
+ * (ix, iy) has index q = iy * WS + ix. After pm_set_camera the context
+ * behaves as a pinhole context of size WS x HS: record count and order,
+ * pm_record_pixel (it returns q), pm_final, the record views and the
+ * multi-device bands all work on the sample raster.
+ *
+ * Ray of sample q, in fp32, no contraction, operations in this order:
+ *   o = pmdm_philox4x32_10(lo32(q), hi32(q), 1, 0; key sample_seed, 0)
+ *   ju, jv = pmdm_u01(o[0]), pmdm_u01(o[1]) with jitter != 0, else 0.5
+ *   lu, lv = pmdm_u01(o[2]), pmdm_u01(o[3])
+ *   ndc_x = 2 (ix + ju) / WS - 1,  ndc_y = 1 - 2 (iy + jv) / HS
+ *   d0 = fwd + ndc_x right + ndc_y up
+ *   lens_radius == 0: origin eye, direction normalize(d0) (with jitter off
+ *     the pm_set_pinhole ray of a WS x HS image, bit for bit)
+ *   lens_radius > 0: (cx, cy) = the concentric-disk map of (lu, lv),
+ *     o' = eye + lens_radius (cx normalize(right) + cy normalize(up)),
+ *     Pf = eye + d0 (focal_distance / |fwd|), direction normalize(Pf - o')
+ *     (pbrt's PerspectiveCamera::GenerateRay in the world basis)
+ *   film position, in pixels: fx = (ix + ju) / xsamples, fy = (iy + jv) / ysamples
+ * The light samples of the eye pass are keyed by q as pm_set_pinhole keys
+ * them by pixel.
+ *
+ * Film (pbrt-v2 ImageFilm restated as a gather; deterministic, no atomics):
+ * with dx = fx - 0.5, dy = fy - 0.5 sample q contributes to pixel (x, y) iff
+ * ceilf(dx - xwidth) <= x <= floorf(dx + xwidth) and likewise in y, with
+ * weight table[jy * 16 + jx], jx = min((int)floorf(fabsf((x - dx) * (1 /
+ * xwidth) * 16)), 15), jy likewise. A pixel sums w L per channel and w in
+ * fp32 in ascending q; sum w == 0 gives black, else each channel is
+ * max(0, sum / sum w), one IEEE division per channel. */
+#define PM_FILTER_NONE 0      /* no film: outputs are the sample raster */
+#define PM_FILTER_BOX 1
+#define PM_FILTER_TRIANGLE 2
+#define PM_FILTER_GAUSSIAN 3  /* a = alpha */
+#define PM_FILTER_MITCHELL 4  /* a = B, b = C */
+#define PM_FILM_TABLE 16      /* pbrt ImageFilm's FILTER_TABLE_SIZE */
+typedef struct pm_filter { int type; float xwidth, ywidth, a, b; } pm_filter;
+typedef struct pm_camera {
+    float eye[3], fwd[3], right[3], up[3];  /* as pm_set_pinhole */
+    int width, height;                      /* image pixels */
+    int xsamples, ysamples;                 /* strata per pixel, 1..8 each */
+    int jitter;                             /* 0: stratum centres */
+    float lens_radius, focal_distance;      /* 0: pinhole */
+    uint32_t sample_seed;
+    pm_filter filter;
+    int reserved[4];
+} pm_camera;
+/* PM_ERR_INVALID: a null pointer, a non-finite vector, |eye| + lens_radius
+ * beyond PM_MAX_RAY_ORIGIN, width or height <= 0, a sample count outside
+ * 1..8, WS * HS >= 2^31, lens_radius < 0, lens_radius > 0 with
+ * focal_distance <= 0, an unknown filter type, a real filter with a width
+ * outside (0, 4] or with WS or HS above 2^20 (fp32 film positions). A multi-device context takes the call as well. */
+int pm_set_camera(void *ctx, const pm_camera *cam);
+/* The film as a stage: d_samples float3 x WS * HS in raster order (what
+ * pm_final writes), d_image float3 x width * height. Needs a camera with a
+ * real filter. pm_render and pm_render_simple run it themselves and write the
+ * width x height image; with PM_FILTER_NONE they write the sample raster. */
+int pm_film(void *ctx, const void *d_samples, void *d_image, void *stream);
+/* Rays (o.xyz, d.xyz) and film positions (fx, fy) of samples [first, first +
+ * count), computed on the device by the function the eye pass calls, into
+ * host arrays; either may be null. A test hook like pm_scene_section. */
+int pm_camera_rays(void *ctx, int64_t first, int64_t count, float *rays6, float *film_xy);
+/* Host only: table[j * 16 + i] = (float)F((i + 0.5) / 16 * xwidth, (j + 0.5) /
+ * 16 * ywidth), F in double from the float parameters: box 1; triangle
+ * max(0, xw - |x|) max(0, yw - |y|); gaussian g(x, xw) g(y, yw) with g(t, w) =
+ * max(0, exp(-a t^2) - exp(-a w^2)); mitchell M(x / xw) M(y / yw) with
+ * t = |2 x|, M = ((-B - 6C) t^3 + (6B + 30C) t^2 + (-12B - 48C) t + (8B + 24C))
+ * / 6 for t > 1, else ((12 - 9B - 6C) t^3 + (-18 + 12B + 6C) t^2 + (6 - 2B)) / 6. */
+int pm_film_filter_table(const pm_filter *f, float out[PM_FILM_TABLE * PM_FILM_TABLE]);
 
 /* Builds the BVH and uploads the scene. Must follow the last pm_add_*. */
 int pm_commit(void *ctx);
