@@ -1,9 +1,10 @@
 /*
  * pm_api.cpp — the C-ABI of libpmhip.so (declared in include/pm_api.h):
- * context, scene flattening, BVH build + upload, stage orchestration and
- * the whole-render entry point. Host code only; kernels live in
- * pm_kernels.hip. No CPU fallback: every compute entry point launches HIP
- * kernels and fails with PM_ERR_HIP when the device is unusable.
+ * context, scene calls, commit (the device BVH build, or the host assembly
+ * of pm_scene.cpp, and the upload), stage orchestration and the whole-render
+ * entry point. Host code only; the kernels live in the .hip files
+ * (launchers in pm_kernels.h). No CPU fallback: every compute entry point
+ * launches HIP kernels and fails with PM_ERR_HIP when the device is unusable.
  */
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -14,7 +15,6 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <functional>
 #include <mutex>
 #include <random>
 #include <string>
@@ -23,6 +23,7 @@
 
 #include "pm_build.h"
 #include "pm_kernels.h"
+#include "pm_scene.h"
 
 #pragma clang fp contract(off)
 
@@ -54,17 +55,6 @@ struct DevBuf {
     template <class T> T *as() const { return (T *)p; }
 };
 
-struct HMesh { int material, light, has_n, has_uv; };
-struct HTri { int v[3]; int mesh; uint32_t gid; }; /* gid: global id (insertion order over all triangles) */
-/* two-level instancing: an object mesh stored once in object space, and its
- * instances (pbrt ObjectBegin / ObjectInstance) */
-struct HObj {
-    std::vector<float> P, N, UV;
-    std::vector<int> idx;
-    int material = 0, light = -1;
-    bool has_n = false, has_uv = false;
-};
-struct HInst { int obj; float m[16], minv[16]; uint32_t gid_base; };
 struct Timer { hipEvent_t a = nullptr, b = nullptr; };
 struct TimerPool { std::vector<Timer> ev; size_t used = 0; };
 
@@ -74,20 +64,7 @@ struct Ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
-    /* host scene */
-    std::vector<float4> materials;
-    std::vector<float> P, N, UV;
-    std::vector<HMesh> meshes;
-    std::vector<HTri> tris;
-    int64_t next_tri_id = 0;     /* global ids handed out to triangles (meshes and instances); < 2^31 */
-    std::vector<HObj> objs;
-    std::vector<HInst> insts;
-    int64_t obj_tris_stored = 0; /* object triangles in the committed scene (each mesh once) */
-    std::vector<float4> disks;   /* 5 per disk */
-    std::vector<float4> spheres; /* 4 per sphere */
-    std::vector<float> sphere_o2w;
-    std::vector<LightDev> lights;
-    std::vector<LightTri> light_tris; /* the mesh lights' emitting triangles, light after light (SceneDev::light_tris) */
+    HostScene hs; /* the host scene (pm_scene.h): the pm_add_* calls fill it, pm_commit assembles it */
     int rand2d_total = 0;
     int pinhole = 0, W = 0, H = 0;
     /* pm_set_camera: pinhole = 1 and W x H the sample raster (image * strata),
@@ -104,23 +81,17 @@ struct Ctx {
     /* device scene */
     DevBuf d_scene, d_rays, d_rand2d; /* d_scene: the scene blob (SceneDev) */
     DevBuf d_light_tris;              /* SceneDev::light_tris (kept out of the blob: never LDS-resident) */
-    /* PM_ALL_LIGHTS: the light selection table (pm_light_selection_cdf over
-     * c->lights, made by pm_commit; all zero and light_cdf_ok false when the
-     * scene's total selection weight is 0 or not finite), its device copy
-     * (TraceParams::light_cdf: a buffer of its own like d_light_tris) */
-    std::vector<float> light_cdf;
-    bool light_cdf_ok = false;
+    /* the committed scene's layout, and its light summary: emission / albedo
+     * bounds for the fixed-point flux scale (emission_bound chooses the
+     * emission bound per call) and the PM_ALL_LIGHTS selection table, whose
+     * device copy is d_light_cdf (TraceParams::light_cdf: a buffer of its own
+     * like d_light_tris) */
+    SceneLayout L;
+    LightSummary lsum;
     DevBuf d_light_cdf;
     DevBuf d_tripairs;                /* brute-force scenes: triangle pairs interleaved (SceneDev::tri_pairs_g) */
     SceneDev S{};
     float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};
-    /* bounds for the fixed-point flux scale: emit_max the largest single
-     * light's Le / pdf bound (a fixed light_source_index); emit_max_all the
-     * same under PM_ALL_LIGHTS, where the pick's probability divides the
-     * weight: max_l(bound_l / pmf_l) over the lights with pmf_l > 0 of the
-     * float table (emission_bound chooses per call) */
-    double emit_max = 1.0, emit_max_all = 1.0, kd_max = 1.0;
-    bool scene_nonneg = true;  /* no negative emission / albedo component (fixed-point sums in double) */
     bool slots_nonneg = true;  /* the slot buffer holds no negative flux (uploaded slots are checked) */
     int bvh_depth = 0;
     /* records */
@@ -349,49 +320,6 @@ double timer_ms(Ctx *c, const char *name, size_t k = 1) {
     return ms;
 }
 
-inline float4 f4(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
-inline float ibits(int v) { float f; std::memcpy(&f, &v, 4); return f; }
-inline int fbits_h(float f) { int v; std::memcpy(&v, &f, 4); return v; }
-inline float bits_f(uint32_t v) { float f; std::memcpy(&f, &v, 4); return f; }
-
-/* Normalized shading frame of one triangle: the same IEEE float operations
- * in the same order as the closest-hit program (cudatrianglemesh.cu:36-78,
- * then normalize as cudamaterial.cu.h:84-85), so the device reads values
- * bit-identical to computing them per hit. n = e1 x e0 as in tri_geo. */
-void tri_frame(const float *p0, const float *p1, const float *p2, const float *UV, const int *v, const float *n,
-               float *ns, float *dpdu) {
-    float uv0x = 0.f, uv0y = 0.f, uv1x = 1.f, uv1y = 0.f, uv2x = 0.f, uv2y = 1.f;
-    if (UV) {
-        uv0x = UV[2 * v[0]]; uv0y = UV[2 * v[0] + 1];
-        uv1x = UV[2 * v[1]]; uv1y = UV[2 * v[1] + 1];
-        uv2x = UV[2 * v[2]]; uv2y = UV[2 * v[2] + 1];
-    }
-    const float du1 = uv0x - uv2x, du2 = uv1x - uv2x, dv1 = uv0y - uv2y, dv2 = uv1y - uv2y;
-    const float determinant = du1 * dv2 - dv1 * du2;
-    float d[3];
-    if (determinant == 0.0f) {
-        if (std::fabs(n[0]) > std::fabs(n[1])) {
-            float invLen = 1.f / std::sqrt(n[0] * n[0] + n[2] * n[2]);
-            d[0] = -n[2] * invLen; d[1] = 0.f; d[2] = n[0] * invLen;
-        } else {
-            float invLen = 1.f / std::sqrt(n[1] * n[1] + n[2] * n[2]);
-            d[0] = 0.f; d[1] = n[2] * invLen; d[2] = n[1] * invLen;
-        }
-    } else {
-        const float invdet = 1.f / determinant;
-        for (int a = 0; a < 3; ++a) {
-            float dp1 = p0[a] - p2[a], dp2 = p1[a] - p2[a];
-            d[a] = (dv2 * dp1 - dv1 * dp2) * invdet;
-        }
-    }
-    auto normalize3 = [](const float *x, float *out) {
-        float inv = 1.0f / std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-        for (int a = 0; a < 3; ++a) out[a] = x[a] * inv;
-    };
-    normalize3(n, ns);
-    normalize3(d, dpdu);
-}
-
 int64_t num_records(const Ctx *c) {
     if (c->pinhole) return (int64_t)((c->W + 7) / 8) * ((c->H + 7) / 8) * 64;
     return c->nrays;
@@ -437,9 +365,9 @@ static int materialize_slots(Ctx *c, hipStream_t s) {
     return PM_OK;
 }
 
-/* the bound of a path's emitted weight for this call's light_source_index (Ctx::emit_max) */
+/* the bound of a path's emitted weight for this call's light_source_index (LightSummary) */
 double emission_bound(const Ctx *c, const pm_render_params *p) {
-    return p->light_source_index == PM_ALL_LIGHTS ? c->emit_max_all : c->emit_max;
+    return p->light_source_index == PM_ALL_LIGHTS ? c->lsum.emit_max_all : c->lsum.emit_max;
 }
 
 template <class T>
@@ -492,7 +420,7 @@ GatherParams gather_params(Ctx *c, const pm_render_params *p) {
     G.kernel = c->gather_kernel;
     G.kd_stack = c->kd_stack;
     G.error = reinterpret_cast<unsigned int *>(c->d_counters.as<unsigned long long>() + 16);
-    G.fx_nonneg = c->scene_nonneg && c->slots_nonneg ? 1 : 0;
+    G.fx_nonneg = c->lsum.scene_nonneg && c->slots_nonneg ? 1 : 0;
     G.span = grid_span(c->grid, c->grid_r2 > 0.f ? c->grid_r2 : p->initial_radius2);
     /* The cooperative scan of a tile's direct lanes costs the sum of their
      * photons / 64 steps, the per-lane scans the largest lane's photons but
@@ -509,7 +437,7 @@ GatherParams gather_params(Ctx *c, const pm_render_params *p) {
      * alpha_max * Kd_max / pi with alpha_max = emission * Kd_max^mpc (Lambert
      * weight ~Kd, specular weight 1); x4 headroom; 2^40 per contribution
      * leaves 2^23 contributions per record before int64 overflow */
-    double cmax = emission_bound(c, p) * std::pow(c->kd_max, (double)p->max_photon_count) * (c->kd_max / M_PI) * 4.0;
+    double cmax = emission_bound(c, p) * std::pow(c->lsum.kd_max, (double)p->max_photon_count) * (c->lsum.kd_max / M_PI) * 4.0;
     int S = (int)std::floor(std::log2(std::ldexp(1.0, 40) / std::max(cmax, 1e-30)));
     S = std::max(-60, std::min(60, S));
     G.fx_scale = (float)std::ldexp(1.0, S);
@@ -552,12 +480,12 @@ int check_params(Ctx *c, const pm_render_params *p) {
     if (!c->committed) FAIL(c, PM_ERR_INVALID, "scene not committed (call pm_commit)");
     if (p->max_photon_count < 1 || p->max_photon_count > 64) FAIL(c, PM_ERR_INVALID, "max_photon_count out of range");
     if (p->light_source_index == PM_ALL_LIGHTS) {
-        if (!c->light_cdf_ok)
+        if (!c->lsum.cdf_ok)
             FAIL(c, PM_ERR_INVALID, "PM_ALL_LIGHTS: the total selection weight of the scene's %zu lights is 0 or not "
-                                    "finite (no light to pick)", c->lights.size());
-    } else if (p->light_source_index < 0 || p->light_source_index >= (int)c->lights.size())
+                                    "finite (no light to pick)", c->hs.lights.size());
+    } else if (p->light_source_index < 0 || p->light_source_index >= (int)c->hs.lights.size())
         FAIL(c, PM_ERR_INVALID, "light_source_index %d out of range (%zu lights; PM_ALL_LIGHTS = -1 for every light)",
-             p->light_source_index, c->lights.size());
+             p->light_source_index, c->hs.lights.size());
     if (!(p->initial_radius2 > 0.f)) FAIL(c, PM_ERR_INVALID, "initial_radius2 must be > 0");
     if (p->estimator != PM_ESTIMATOR_PPM && p->estimator != PM_ESTIMATOR_KNN)
         FAIL(c, PM_ERR_INVALID, "unknown estimator %d", p->estimator);
@@ -570,66 +498,6 @@ int check_params(Ctx *c, const pm_render_params *p) {
     return PM_OK;
 }
 
-/* where pm_commit put each section of the scene blob */
-struct SceneLayout {
-    size_t o_nodes = 0, o_refs = 0, o_geo = 0, o_shade = 0, o_tid = 0, o_info = 0, o_norms = 0, o_disks = 0,
-           o_spheres = 0, o_mats = 0, o_lights = 0, o_wnodes = 0, bytes = 0;
-    size_t o_insts = 0, o_objv = 0, o_objinfo = 0, o_objn = 0, o_objuv = 0, o_objmesh = 0; /* instancing */
-    int64_t n_nodes = 0, n_refs = 0, n_tris = 0;
-    bool id_order = false;
-    int wide = 0, wide_stack = 0;
-};
-
-/* per triangle t: (p0, e0, e1, n) for the intersector, the normalized
- * shading frame for hits, vertex ids + mesh */
-void tri_record(const Ctx *c, uint32_t t, float4 *geo, float4 *shade, int4 *info) {
-    const float *V = c->P.data();
-    const HTri &tr = c->tris[t];
-    const HMesh &m = c->meshes[tr.mesh];
-    const float *p0 = V + 3 * tr.v[0], *p1 = V + 3 * tr.v[1], *p2 = V + 3 * tr.v[2];
-    float e0[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-    float e1[3] = {p0[0] - p2[0], p0[1] - p2[1], p0[2] - p2[2]};
-    float n[3] = {e1[1] * e0[2] - e1[2] * e0[1], e1[2] * e0[0] - e1[0] * e0[2], e1[0] * e0[1] - e1[1] * e0[0]};
-    geo[0] = f4(p0[0], p0[1], p0[2], e0[0]);
-    geo[1] = f4(e0[1], e0[2], e1[0], e1[1]);
-    geo[2] = f4(e1[2], n[0], n[1], n[2]);
-    float ns[3], dpdu[3];
-    tri_frame(p0, p1, p2, m.has_uv ? &c->UV[0] : nullptr, tr.v, n, ns, dpdu);
-    shade[0] = f4(ns[0], ns[1], ns[2], bits_f((uint32_t)m.material | (m.has_n ? 0x80000000u : 0u)));
-    shade[1] = f4(dpdu[0], dpdu[1], dpdu[2], bits_f((uint32_t)m.light));
-    *info = make_int4(tr.v[0], tr.v[1], tr.v[2], tr.mesh);
-}
-
-std::vector<float4> vertex_normals(const Ctx *c) {
-    std::vector<float4> norms(c->N.size() / 3);
-    for (size_t i = 0; i < norms.size(); ++i) norms[i] = f4(c->N[3 * i], c->N[3 * i + 1], c->N[3 * i + 2], 0.f);
-    return norms;
-}
-
-/* PLOC neighbour radius (env PM_PLOC_RADIUS, 1..32). C3 trace per 1M paths
- * on the host-built PLOC tree (same box): r 1 5.87 ms, 2 4.70, 3 4.50, 4
- * 4.58–4.63, 8 5.12, 16 5.73; the binned-SAH tree 4.50–4.51 */
-int ploc_radius() {
-    const char *e = getenv("PM_PLOC_RADIUS");
-    return e ? std::max(1, std::min(32, atoi(e))) : 3;
-}
-
-/* env PM_BVH_BUILD: "gpu" (the device PLOC build, pm_bvh_gpu.hip), "host"
- * (the binned-SAH host build), "ploc-host" (the device's algorithm on the
- * host: A/B and test oracle); unset or "auto": the device for scenes of at
- * least PM_BVH_GPU_MIN (65,536) primitives, whose host build dominated the
- * scene setup (C3: 0.28 s SAH of a 0.51 s commit) */
-bool gpu_bvh_wanted(int64_t nprims) {
-    const char *b = getenv("PM_BVH_BUILD");
-    const std::string m = b ? b : "auto";
-    int64_t gmin = 1 << 16;
-    if (const char *e = getenv("PM_BVH_GPU_MIN")) gmin = std::max<int64_t>(2, atoll(e));
-    const bool want = m == "gpu" ? nprims >= 2 : (m == "auto" && nprims >= gmin);
-    if (!want || PM_BVH4_QUANT == 0) return false;
-    /* the breadth-first renumbering of the host tree is a host-path switch */
-    return getenv("PM_BVH4_BFS") == nullptr;
-}
-
 struct TmpBuf : DevBuf {
     ~TmpBuf() { release(); }
 };
@@ -640,24 +508,26 @@ struct TmpBuf : DevBuf {
  * while the device builds) are uploaded and permuted into storage order.
  * built = false: the caller runs the host build (the device tree exceeded a
  * limit the traversal has, or the build failed — reported on stderr) */
-int commit_gpu_bvh(Ctx *c, const std::vector<BuildPrim> &prims, int64_t nt, SceneLayout &L, bool &built, bool ptimes) {
+int commit_gpu_bvh(Ctx *c, const std::vector<BuildPrim> &prims, const BuildOptions &opt, SceneLayout &L, bool &built) {
     built = false;
+    const HostScene &hs = c->hs;
+    const int64_t nt = (int64_t)hs.tris.size();
     const auto t0 = std::chrono::steady_clock::now();
     auto ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     const int n = (int)prims.size();
     GpuBvhIn in{};
     in.n = n;
-    in.radius = ploc_radius();
+    in.radius = opt.ploc_radius;
     ploc_morton_frame(prims, in.frame_lo, in.frame_scale);
-    std::vector<float4> geo(3 * (size_t)nt), shade(2 * (size_t)nt);
-    std::vector<int4> info((size_t)nt);
+    std::vector<float> geo(TRI_GEO_FLOATS * (size_t)nt), shade(TRI_SHADE_FLOATS * (size_t)nt);
+    std::vector<int> info(TRI_INFO_INTS * (size_t)nt);
     struct Joiner {
         std::thread t;
         ~Joiner() { if (t.joinable()) t.join(); }
     } records;
     records.t = std::thread([&] {
         parallel_for(nt, [&](int64_t k0, int64_t k1) {
-            for (int64_t k = k0; k < k1; ++k) tri_record(c, (uint32_t)k, &geo[3 * k], &shade[2 * k], &info[k]);
+            for (int64_t k = k0; k < k1; ++k) tri_record(hs, (uint32_t)k, &geo[TRI_GEO_FLOATS * k], &shade[TRI_SHADE_FLOATS * k], &info[TRI_INFO_INTS * k]);
         });
     });
     std::vector<float4> hb(2 * (size_t)n);
@@ -672,39 +542,30 @@ int commit_gpu_bvh(Ctx *c, const std::vector<BuildPrim> &prims, int64_t nt, Scen
     HIPCHK(c, d_box.ensure(hb.size() * sizeof(float4)));
     HIPCHK(c, hipMemcpy(d_box.p, hb.data(), hb.size() * sizeof(float4), hipMemcpyHostToDevice));
     in.box = d_box.as<float4>();
-    /* blob sections in pm_commit's order; no binary tree (a 16-B placeholder) */
-    const std::vector<float4> norms = vertex_normals(c);
-    size_t off = 0;
-    auto sect = [&](size_t bytes) { const size_t o = (off + 15) & ~(size_t)15; off = o + bytes; return o; };
-    L.o_nodes = sect(16);
-    L.o_refs = sect(4 * (size_t)n);
-    L.o_geo = sect(48 * (size_t)nt);
-    L.o_shade = sect(32 * (size_t)nt);
-    L.o_tid = sect(4 * (size_t)nt);
-    L.o_info = sect(16 * (size_t)nt);
-    L.o_norms = sect(norms.size() * sizeof(float4));
-    L.o_disks = sect(c->disks.size() * sizeof(float4));
-    L.o_spheres = sect(c->spheres.size() * sizeof(float4));
-    L.o_mats = sect(c->materials.size() * sizeof(float4));
-    L.o_lights = sect(c->lights.size() * sizeof(LightDev));
-    L.o_wnodes = sect(64 * (size_t)(n - 1));
-    /* never LDS-resident: the LDS modes traverse the binary tree this path does not build */
-    L.bytes = std::max<size_t>((off + 15) & ~(size_t)15, (size_t)LDS_SCENE_MAX + 16);
+    /* the host assembly's layout; no binary tree (a placeholder), room
+     * for the n - 1 nodes a 4-wide tree over n leaves can have. Never
+     * LDS-resident: the LDS modes traverse the binary tree this path does not build */
+    const std::vector<float4> norms = vertex_normals(hs);
+    L = SceneLayout();
+    count_sections(L, hs, n, nt);
+    L.size[SEC_NODES] = NODE_PLACEHOLDER_BYTES;
+    L.size[SEC_WNODES] = BVH4Q_NODE_BYTES * (size_t)(n - 1);
+    plan_layout(L, true);
     HIPCHK(c, c->d_scene.ensure(L.bytes));
     char *base = c->d_scene.as<char>();
-    HIPCHK(c, hipMemsetAsync(base + L.o_nodes, 0, 16, c->stream));
-    auto put = [&](size_t o, const void *src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+    HIPCHK(c, hipMemsetAsync(base + L.off[SEC_NODES], 0, L.size[SEC_NODES], c->stream));
+    auto put = [&](SceneSection sec, const void *src) {
+        return L.size[sec] ? hipMemcpyAsync(base + L.off[sec], src, L.size[sec], hipMemcpyHostToDevice, c->stream) : hipSuccess;
     };
-    HIPCHK(c, put(L.o_norms, norms.data(), norms.size() * sizeof(float4)));
-    HIPCHK(c, put(L.o_disks, c->disks.data(), c->disks.size() * sizeof(float4)));
-    HIPCHK(c, put(L.o_spheres, c->spheres.data(), c->spheres.size() * sizeof(float4)));
-    HIPCHK(c, put(L.o_mats, c->materials.data(), c->materials.size() * sizeof(float4)));
-    HIPCHK(c, put(L.o_lights, c->lights.data(), c->lights.size() * sizeof(LightDev)));
-    HIPCHK(c, d_tord.ensure(4 * (size_t)std::max<int64_t>(nt, 1)));
+    HIPCHK(c, put(SEC_NORMS, norms.data()));
+    HIPCHK(c, put(SEC_DISKS, hs.disks.data()));
+    HIPCHK(c, put(SEC_SPHERES, hs.spheres.data()));
+    HIPCHK(c, put(SEC_MATS, hs.materials.data()));
+    HIPCHK(c, put(SEC_LIGHTS, hs.lights.data()));
+    HIPCHK(c, d_tord.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(nt, 1)));
     GpuBvhOut out;
-    out.wnodes = reinterpret_cast<uint4 *>(base + L.o_wnodes);
-    out.refs = reinterpret_cast<uint32_t *>(base + L.o_refs);
+    out.wnodes = reinterpret_cast<uint4 *>(base + L.off[SEC_WNODES]);
+    out.refs = reinterpret_cast<uint32_t *>(base + L.off[SEC_REFS]);
     out.tri_order = d_tord.as<uint32_t>();
     out.max_nodes = n - 1;
     const double t_up = ms();
@@ -722,18 +583,20 @@ int commit_gpu_bvh(Ctx *c, const std::vector<BuildPrim> &prims, int64_t nt, Scen
     }
     records.t.join();
     const double t_rec = ms();
-    HIPCHK(c, d_src.ensure(96 * (size_t)std::max<int64_t>(nt, 1)));
-    float4 *src_geo = d_src.as<float4>(), *src_shade = src_geo + 3 * nt;
-    int4 *src_info = reinterpret_cast<int4 *>(src_shade + 2 * nt);
-    HIPCHK(c, hipMemcpyAsync(src_geo, geo.data(), geo.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(src_shade, shade.data(), shade.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(src_info, info.data(), info.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, d_src.ensure((TRI_GEO_BYTES + TRI_SHADE_BYTES + TRI_INFO_BYTES) * (size_t)std::max<int64_t>(nt, 1)));
+    float4 *src_geo = d_src.as<float4>(), *src_shade = reinterpret_cast<float4 *>(d_src.as<char>() + TRI_GEO_BYTES * (size_t)nt);
+    int4 *src_info = reinterpret_cast<int4 *>(d_src.as<char>() + (TRI_GEO_BYTES + TRI_SHADE_BYTES) * (size_t)nt);
+    HIPCHK(c, hipMemcpyAsync(src_geo, geo.data(), geo.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(src_shade, shade.data(), shade.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(src_info, info.data(), info.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_tri_permute(d_tord.as<uint32_t>(), nt, src_geo, src_shade, src_info,
-                                 reinterpret_cast<float4 *>(base + L.o_geo), reinterpret_cast<float4 *>(base + L.o_shade),
-                                 reinterpret_cast<uint32_t *>(base + L.o_tid), reinterpret_cast<int4 *>(base + L.o_info),
+                                 reinterpret_cast<float4 *>(base + L.off[SEC_GEO]),
+                                 reinterpret_cast<float4 *>(base + L.off[SEC_SHADE]),
+                                 reinterpret_cast<uint32_t *>(base + L.off[SEC_TID]),
+                                 reinterpret_cast<int4 *>(base + L.off[SEC_INFO]),
                                  c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (ptimes)
+    if (opt.times)
         fprintf(stderr, "pm_commit: device build: boxes up %.1f ms, PLOC + collapse %.1f ms (%d rounds, %lld nodes, depth %d, "
                         "stack %d), records %.1f ms, permute %.1f ms\n", t_up, t_build - t_up, out.rounds,
                 (long long)out.nodes, out.depth, out.max_stack, t_rec, ms());
@@ -741,9 +604,7 @@ int commit_gpu_bvh(Ctx *c, const std::vector<BuildPrim> &prims, int64_t nt, Scen
     c->bvh4_nodes = out.nodes;
     c->bvh4_depth = out.depth;
     L.n_nodes = out.nodes;
-    L.n_refs = n;
-    L.n_tris = nt;
-    L.id_order = false;
+    L.size[SEC_WNODES] = BVH4Q_NODE_BYTES * (size_t)out.nodes; /* the nodes in use */
     L.wide = 2;
     L.wide_stack = out.max_stack;
     built = true;
@@ -912,30 +773,9 @@ int pm_halton_permutation(uint32_t seed, uint32_t out[28]) {
 }
 
 int pm_light_selection_cdf(const int *types, const float *le_rgb, const float *areas, int n, float *cdf_out) {
-    Ctx *const none = nullptr;
-    if (!types || !le_rgb || !areas || !cdf_out) FAIL(none, PM_ERR_INVALID, "pm_light_selection_cdf: null pointer");
-    if (n <= 0) FAIL(none, PM_ERR_INVALID, "pm_light_selection_cdf: no lights");
-    std::vector<double> sum((size_t)n);
-    double total = 0.0;
-    for (int l = 0; l < n; ++l) {
-        const double y = 0.212671 * (double)le_rgb[3 * l] + 0.715160 * (double)le_rgb[3 * l + 1] +
-                         0.072169 * (double)le_rgb[3 * l + 2];
-        double w;
-        switch (types[l]) {
-        case PM_LIGHT_POINT: w = y * (4.0 * M_PI); break;
-        case PM_LIGHT_AREA_DISK:
-        case PM_LIGHT_AREA_MESH: w = y * (M_PI * (double)areas[l]); break;
-        default: FAIL(none, PM_ERR_INVALID, "pm_light_selection_cdf: light %d has unknown type %d", l, types[l]);
-        }
-        if (w < 0.0) w = 0.0;
-        total += w;
-        sum[(size_t)l] = total;
-    }
-    if (!(total > 0.0) || !std::isfinite(total))
-        FAIL(none, PM_ERR_INVALID, "pm_light_selection_cdf: total selection weight %g of %d lights is 0 or not finite",
-             total, n);
-    for (int l = 0; l < n; ++l) cdf_out[l] = (float)(sum[(size_t)l] / total);
-    cdf_out[n - 1] = 1.0f;
+    std::string err;
+    const int rc = light_selection_cdf(types, le_rgb, areas, n, cdf_out, err);
+    if (rc) FAIL((Ctx *)nullptr, rc, "%s", err.c_str());
     return PM_OK;
 }
 
@@ -945,8 +785,8 @@ int pm_add_material(void *ptr, int type, const float rgb[3], int *out_id) {
     GETCTX(ptr);
     if (type != PM_MATTE && type != PM_MIRROR && type != PM_GLASS) FAIL(c, PM_ERR_INVALID, "bad material type %d", type);
     float r = rgb ? rgb[0] : 0.f, g = rgb ? rgb[1] : 0.f, b = rgb ? rgb[2] : 0.f;
-    c->materials.push_back(f4(r, g, b, ibits(type)));
-    if (out_id) *out_id = (int)c->materials.size() - 1;
+    c->hs.materials.push_back(f4(r, g, b, ibits(type)));
+    if (out_id) *out_id = (int)c->hs.materials.size() - 1;
     c->committed = false;
     return PM_OK;
 }
@@ -956,21 +796,21 @@ int pm_add_trimesh(void *ptr, const float *P, int nverts, const int *idx, int nt
     GROUP_FWD(ptr, pm_add_trimesh(sub, P, nverts, idx, ntris, N, uv, material, light));
     GETCTX(ptr);
     if (!P || !idx || nverts <= 0 || ntris <= 0) FAIL(c, PM_ERR_INVALID, "empty or null mesh");
-    if (material < 0 || material >= (int)c->materials.size()) FAIL(c, PM_ERR_INVALID, "bad material id %d", material);
+    if (material < 0 || material >= (int)c->hs.materials.size()) FAIL(c, PM_ERR_INVALID, "bad material id %d", material);
     for (int64_t i = 0; i < 3 * (int64_t)ntris; ++i)
         if (idx[i] < 0 || idx[i] >= nverts) FAIL(c, PM_ERR_INVALID, "vertex index %d out of range", idx[i]);
-    if (c->next_tri_id + ntris >= ((int64_t)1 << 31)) FAIL(c, PM_ERR_INVALID, "too many triangles (global ids reach 2^31)");
-    int64_t base = (int64_t)c->P.size() / 3;
-    c->P.insert(c->P.end(), P, P + 3 * (size_t)nverts);
-    if (N) c->N.insert(c->N.end(), N, N + 3 * (size_t)nverts);
-    else c->N.insert(c->N.end(), 3 * (size_t)nverts, 0.f);
-    if (uv) c->UV.insert(c->UV.end(), uv, uv + 2 * (size_t)nverts);
-    else c->UV.insert(c->UV.end(), 2 * (size_t)nverts, 0.f);
-    int mid = (int)c->meshes.size();
-    c->meshes.push_back(HMesh{material, light, N != nullptr, uv != nullptr});
+    if (c->hs.next_tri_id + ntris >= ((int64_t)1 << 31)) FAIL(c, PM_ERR_INVALID, "too many triangles (global ids reach 2^31)");
+    int64_t base = (int64_t)c->hs.P.size() / 3;
+    c->hs.P.insert(c->hs.P.end(), P, P + 3 * (size_t)nverts);
+    if (N) c->hs.N.insert(c->hs.N.end(), N, N + 3 * (size_t)nverts);
+    else c->hs.N.insert(c->hs.N.end(), 3 * (size_t)nverts, 0.f);
+    if (uv) c->hs.UV.insert(c->hs.UV.end(), uv, uv + 2 * (size_t)nverts);
+    else c->hs.UV.insert(c->hs.UV.end(), 2 * (size_t)nverts, 0.f);
+    int mid = (int)c->hs.meshes.size();
+    c->hs.meshes.push_back(HMesh{material, light, N != nullptr, uv != nullptr});
     for (int t = 0; t < ntris; ++t)
-        c->tris.push_back(HTri{{(int)(base + idx[3 * t]), (int)(base + idx[3 * t + 1]), (int)(base + idx[3 * t + 2])}, mid,
-                               (uint32_t)c->next_tri_id++});
+        c->hs.tris.push_back(HTri{{(int)(base + idx[3 * t]), (int)(base + idx[3 * t + 1]), (int)(base + idx[3 * t + 2])}, mid,
+                               (uint32_t)c->hs.next_tri_id++});
     c->committed = false;
     return PM_OK;
 }
@@ -980,7 +820,7 @@ int pm_add_object_mesh(void *ptr, const float *P, int nverts, const int *idx, in
     GROUP_FWD(ptr, pm_add_object_mesh(sub, P, nverts, idx, ntris, N, uv, material, light, out_object));
     GETCTX(ptr);
     if (!P || !idx || nverts <= 0 || ntris <= 0) FAIL(c, PM_ERR_INVALID, "empty or null object mesh");
-    if (material < 0 || material >= (int)c->materials.size()) FAIL(c, PM_ERR_INVALID, "bad material id %d", material);
+    if (material < 0 || material >= (int)c->hs.materials.size()) FAIL(c, PM_ERR_INVALID, "bad material id %d", material);
     for (int64_t i = 0; i < 3 * (int64_t)ntris; ++i)
         if (idx[i] < 0 || idx[i] >= nverts) FAIL(c, PM_ERR_INVALID, "vertex index %d out of range", idx[i]);
     HObj o;
@@ -989,8 +829,8 @@ int pm_add_object_mesh(void *ptr, const float *P, int nverts, const int *idx, in
     if (uv) o.UV.assign(uv, uv + 2 * (size_t)nverts);
     o.idx.assign(idx, idx + 3 * (size_t)ntris);
     o.material = material; o.light = light; o.has_n = N != nullptr; o.has_uv = uv != nullptr;
-    c->objs.push_back(std::move(o));
-    if (out_object) *out_object = (int)c->objs.size() - 1;
+    c->hs.objs.push_back(std::move(o));
+    if (out_object) *out_object = (int)c->hs.objs.size() - 1;
     c->committed = false;
     return PM_OK;
 }
@@ -998,42 +838,36 @@ int pm_add_object_mesh(void *ptr, const float *P, int nverts, const int *idx, in
 int pm_add_mesh_instance(void *ptr, int object, const float o2w[16], const float w2o[16]) {
     GROUP_FWD(ptr, pm_add_mesh_instance(sub, object, o2w, w2o));
     GETCTX(ptr);
-    if (object < 0 || object >= (int)c->objs.size()) FAIL(c, PM_ERR_INVALID, "bad object id %d", object);
+    if (object < 0 || object >= (int)c->hs.objs.size()) FAIL(c, PM_ERR_INVALID, "bad object id %d", object);
     if (!o2w || !w2o) FAIL(c, PM_ERR_INVALID, "null instance transform");
     if (o2w[12] != 0.f || o2w[13] != 0.f || o2w[14] != 0.f || o2w[15] != 1.f)
         FAIL(c, PM_ERR_INVALID, "instance transform is not affine (flatten it with pm_add_trimesh)");
     /* every instance takes global ids for all of its triangles (as the
      * flattened scene would): heavy instancing must not wrap them */
-    const int64_t n_obj_tris = (int64_t)(c->objs[object].idx.size() / 3);
-    if (c->next_tri_id + n_obj_tris >= ((int64_t)1 << 31))
+    const int64_t n_obj_tris = (int64_t)(c->hs.objs[object].idx.size() / 3);
+    if (c->hs.next_tri_id + n_obj_tris >= ((int64_t)1 << 31))
         FAIL(c, PM_ERR_INVALID, "too many instanced triangles (global ids reach 2^31)");
     HInst in;
     in.obj = object;
     std::memcpy(in.m, o2w, sizeof in.m);
     std::memcpy(in.minv, w2o, sizeof in.minv);
-    in.gid_base = (uint32_t)c->next_tri_id;
-    c->next_tri_id += n_obj_tris;
-    c->insts.push_back(in);
+    in.gid_base = (uint32_t)c->hs.next_tri_id;
+    c->hs.next_tri_id += n_obj_tris;
+    c->hs.insts.push_back(in);
     c->committed = false;
     return PM_OK;
-}
-
-/* an instance's world vertex as pbrt's Transform::operator()(Point) computes
- * it for an affine transform (w == 1): the device's inst_point, bit for bit */
-static inline void inst_point_h(const float *m, const float *p, float *o) {
-    for (int a = 0; a < 3; ++a) o[a] = m[4 * a] * p[0] + m[4 * a + 1] * p[1] + m[4 * a + 2] * p[2] + m[4 * a + 3];
 }
 
 int pm_add_sphere(void *ptr, float radius, const float o2w[16], const float w2o[16], int material, int light) {
     GROUP_FWD(ptr, pm_add_sphere(sub, radius, o2w, w2o, material, light));
     GETCTX(ptr);
     if (!o2w || !w2o || !(radius > 0.f)) FAIL(c, PM_ERR_INVALID, "bad sphere");
-    if (material < 0 || material >= (int)c->materials.size()) FAIL(c, PM_ERR_INVALID, "bad material id %d", material);
-    c->spheres.push_back(f4(w2o[0], w2o[1], w2o[2], w2o[3]));
-    c->spheres.push_back(f4(w2o[4], w2o[5], w2o[6], w2o[7]));
-    c->spheres.push_back(f4(w2o[8], w2o[9], w2o[10], w2o[11]));
-    c->spheres.push_back(f4(radius, ibits(material), ibits(light), ibits(0)));
-    c->sphere_o2w.insert(c->sphere_o2w.end(), o2w, o2w + 16);
+    if (material < 0 || material >= (int)c->hs.materials.size()) FAIL(c, PM_ERR_INVALID, "bad material id %d", material);
+    c->hs.spheres.push_back(f4(w2o[0], w2o[1], w2o[2], w2o[3]));
+    c->hs.spheres.push_back(f4(w2o[4], w2o[5], w2o[6], w2o[7]));
+    c->hs.spheres.push_back(f4(w2o[8], w2o[9], w2o[10], w2o[11]));
+    c->hs.spheres.push_back(f4(radius, ibits(material), ibits(light), ibits(0)));
+    c->hs.sphere_o2w.insert(c->hs.sphere_o2w.end(), o2w, o2w + 16);
     c->committed = false;
     return PM_OK;
 }
@@ -1044,15 +878,15 @@ int pm_add_disk(void *ptr, const float o[3], const float x[3], const float y[3],
     GROUP_FWD(ptr, pm_add_disk(sub, o, x, y, z, inner, phimax, material, light));
     GETCTX(ptr);
     if (!o || !x || !y || !z) FAIL(c, PM_ERR_INVALID, "null disk vector");
-    if (material < 0 || material >= (int)c->materials.size()) FAIL(c, PM_ERR_INVALID, "bad material id %d", material);
+    if (material < 0 || material >= (int)c->hs.materials.size()) FAIL(c, PM_ERR_INVALID, "bad material id %d", material);
     float inv_rx2 = 1.f / (x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
     float inv_ry2 = 1.f / (y[0] * y[0] + y[1] * y[1] + y[2] * y[2]);
     float moffset = o[0] * z[0] + o[1] * z[1] + o[2] * z[2];
-    c->disks.push_back(f4(o[0], o[1], o[2], inner));
-    c->disks.push_back(f4(x[0], x[1], x[2], phimax));
-    c->disks.push_back(f4(y[0], y[1], y[2], moffset));
-    c->disks.push_back(f4(z[0], z[1], z[2], inv_rx2));
-    c->disks.push_back(f4(inv_ry2, ibits(material), ibits(light), ibits(0)));
+    c->hs.disks.push_back(f4(o[0], o[1], o[2], inner));
+    c->hs.disks.push_back(f4(x[0], x[1], x[2], phimax));
+    c->hs.disks.push_back(f4(y[0], y[1], y[2], moffset));
+    c->hs.disks.push_back(f4(z[0], z[1], z[2], inv_rx2));
+    c->hs.disks.push_back(f4(inv_ry2, ibits(material), ibits(light), ibits(0)));
     c->committed = false;
     return PM_OK;
 }
@@ -1067,7 +901,7 @@ int pm_add_light_point(void *ptr, const float pos[3], const float I[3]) {
     L.p2_r2d = f4(0, 0, 0, ibits(0));
     L.n_area = f4(0, 0, 0, 0);
     L.le = f4(I[0], I[1], I[2], 0);
-    c->lights.push_back(L);
+    c->hs.lights.push_back(L);
     c->committed = false;
     return PM_OK;
 }
@@ -1085,7 +919,7 @@ int pm_add_light_disk(void *ptr, const float o[3], const float p1[3], const floa
     L.n_area = f4(n[0], n[1], n[2], area);
     L.le = f4(Le[0], Le[1], Le[2], 0);
     c->rand2d_total += ns;
-    c->lights.push_back(L);
+    c->hs.lights.push_back(L);
     c->committed = false;
     return PM_OK;
 }
@@ -1099,7 +933,7 @@ int pm_add_light_mesh(void *ptr, const float *P, int nverts, const int *idx, int
     if (nverts <= 0 || ntris <= 0) FAIL(c, PM_ERR_INVALID, "empty mesh light");
     for (int64_t i = 0; i < 3 * (int64_t)ntris; ++i)
         if (idx[i] < 0 || idx[i] >= nverts) FAIL(c, PM_ERR_INVALID, "vertex index %d out of range", idx[i]);
-    if (c->light_tris.size() + (size_t)ntris >= ((size_t)1 << 31)) FAIL(c, PM_ERR_INVALID, "too many emitting triangles");
+    if (c->hs.light_tris.size() + (size_t)ntris >= ((size_t)1 << 31)) FAIL(c, PM_ERR_INVALID, "too many emitting triangles");
     std::vector<LightTri> tris((size_t)ntris);
     std::vector<double> sum((size_t)ntris);
     double total = 0.0;
@@ -1125,15 +959,15 @@ int pm_add_light_mesh(void *ptr, const float *P, int nverts, const int *idx, int
     tris[ntris - 1].p0_cdf.w = 1.0f;
     const int ns = std::max(1, nsamples);
     LightDev L{};
-    L.o_type = f4(ibits((int)c->light_tris.size()), ibits(ntris), ibits(reverse ? 1 : 0), ibits(PM_LIGHT_AREA_MESH));
+    L.o_type = f4(ibits((int)c->hs.light_tris.size()), ibits(ntris), ibits(reverse ? 1 : 0), ibits(PM_LIGHT_AREA_MESH));
     L.p1_ns = f4(0, 0, 0, ibits(ns));
     L.p2_r2d = f4(0, 0, 0, ibits(c->rand2d_total)); /* CudaSample::Add2D offset, as the disk light */
     L.n_area = f4(0, 0, 0, (float)total);
     L.le = f4(Le[0], Le[1], Le[2], 0);
     c->rand2d_total += ns;
-    c->light_tris.insert(c->light_tris.end(), tris.begin(), tris.end());
-    c->lights.push_back(L);
-    *out_light = (int)c->lights.size() - 1;
+    c->hs.light_tris.insert(c->hs.light_tris.end(), tris.begin(), tris.end());
+    c->hs.lights.push_back(L);
+    *out_light = (int)c->hs.lights.size() - 1;
     c->committed = false;
     return PM_OK;
 }
@@ -1316,480 +1150,84 @@ int pm_camera_rays(void *ptr, int64_t first, int64_t count, float *rays6, float 
     return rc;
 }
 
-/* the object meshes of an instanced scene (two-level trees) */
-struct InstLayout {
-    std::vector<uint32_t> qn;     /* every object's quantized 4-wide nodes, object 0 first (relocated by the caller) */
-    std::vector<float4> insts;    /* 8 per instance (SceneDev::insts) */
-    int max_stack = 0;            /* the deepest object tree's stack bound */
-    size_t o_objv = 0, o_objinfo = 0, o_objn = 0, o_objuv = 0, o_objmesh = 0;
-};
-
-/* quantized 4-wide nodes moved to start at node `base`: internal child codes shift */
-static void relocate_bvh4(std::vector<uint32_t> &q, uint32_t base) {
-    for (size_t nd = 0; nd + 16 <= q.size(); nd += 16)
-        for (int k = 0; k < 4; ++k) {
-            const int16_t cnt = (int16_t)((q[nd + 10 + k / 2] >> (16 * (k & 1))) & 0xffffu);
-            if (cnt == 0) q[nd + 12 + k] += base;
-        }
-}
-
-/* Each object mesh once: its triangles (object space) in the leaf order of
- * its own binned-SAH tree, collapsed to 4-wide and quantized (every leaf a
- * LEAF_TRIS run of object slots); the instance records point at them. */
-static int commit_objects(Ctx *c, std::vector<unsigned char> &blob,
-                          const std::function<size_t(const void *, size_t)> &put, InstLayout &IL) {
-    std::vector<float4> objv, objn, objuv;
-    std::vector<int4> objinfo, objmesh;
-    std::vector<uint32_t> root(c->objs.size()), slot0(c->objs.size());
-    std::vector<int> stack(c->objs.size());
-    uint32_t vbase = 0;
-    for (size_t oi = 0; oi < c->objs.size(); ++oi) {
-        const HObj &o = c->objs[oi];
-        const int nt = (int)(o.idx.size() / 3);
-        std::vector<BuildPrim> prims(nt);
-        for (int t = 0; t < nt; ++t) {
-            BuildPrim &bp = prims[t];
-            for (int a = 0; a < 3; ++a) {
-                const float v0 = o.P[3 * o.idx[3 * t] + a], v1 = o.P[3 * o.idx[3 * t + 1] + a], v2 = o.P[3 * o.idx[3 * t + 2] + a];
-                const float lo = std::min(v0, std::min(v1, v2)), hi = std::max(v0, std::max(v1, v2));
-                const float pad = 1e-4f * std::max(1.0f, std::max(fabsf(lo), fabsf(hi)));
-                bp.lo[a] = lo - pad; bp.hi[a] = hi + pad;
-            }
-            bp.ref = (PRIM_TRI << 30) | (uint32_t)t;
-        }
-        BvhOut bvh;
-        build_bvh(prims, BVH_STACK - 2, bvh);
-        Bvh4Out w;
-        collapse_bvh4(bvh, 1, w);
-        /* storage: the tree's leaf order, at global object slots */
-        const uint32_t s0 = (uint32_t)(objv.size() / 3);
-        std::vector<uint32_t> refs(bvh.refs.size());
-        for (size_t k = 0; k < bvh.refs.size(); ++k) {
-            const uint32_t t = bvh.refs[k] & 0x3fffffffu;
-            refs[k] = (PRIM_TRI << 30) | (s0 + (uint32_t)k);
-            for (int q = 0; q < 3; ++q) {
-                const float *v = &o.P[3 * (size_t)o.idx[3 * t + q]];
-                objv.push_back(f4(v[0], v[1], v[2], q == 0 ? ibits((int)t) : 0.f));
-            }
-            objinfo.push_back(make_int4((int)vbase + o.idx[3 * t], (int)vbase + o.idx[3 * t + 1], (int)vbase + o.idx[3 * t + 2],
-                                        (int)oi));
-        }
-        std::vector<uint32_t> qn;
-        if (!quantize_bvh4(w.nodes, refs, qn)) FAIL(c, PM_ERR_INVALID, "object mesh %zu: tree not codable", oi);
-        for (size_t nd = 0; nd + 16 <= qn.size(); nd += 16)
-            for (int k = 0; k < 4; ++k) {
-                const int16_t cnt = (int16_t)((qn[nd + 10 + k / 2] >> (16 * (k & 1))) & 0xffffu);
-                if (cnt > 0 && !(cnt & LEAF_TRIS)) FAIL(c, PM_ERR_INVALID, "object mesh %zu: a leaf is not a triangle run", oi);
-            }
-        const uint32_t at = (uint32_t)(IL.qn.size() / 16);
-        relocate_bvh4(qn, at);
-        root[oi] = at;
-        slot0[oi] = s0;
-        stack[oi] = w.max_stack;
-        IL.max_stack = std::max(IL.max_stack, w.max_stack);
-        IL.qn.insert(IL.qn.end(), qn.begin(), qn.end());
-        const int nv = (int)(o.P.size() / 3);
-        for (int v = 0; v < nv; ++v) {
-            objn.push_back(o.has_n ? f4(o.N[3 * v], o.N[3 * v + 1], o.N[3 * v + 2], 0.f) : f4(0.f, 0.f, 0.f, 0.f));
-            objuv.push_back(o.has_uv ? f4(o.UV[2 * v], o.UV[2 * v + 1], 0.f, 0.f) : f4(0.f, 0.f, 0.f, 0.f));
-        }
-        vbase += (uint32_t)nv;
-        objmesh.push_back(make_int4(o.material, o.light, o.has_n ? 1 : 0, o.has_uv ? 1 : 0));
-    }
-    for (const HInst &in : c->insts) {
-        for (int r = 0; r < 3; ++r) IL.insts.push_back(f4(in.m[4 * r], in.m[4 * r + 1], in.m[4 * r + 2], in.m[4 * r + 3]));
-        for (int r = 0; r < 3; ++r)
-            IL.insts.push_back(f4(in.minv[4 * r], in.minv[4 * r + 1], in.minv[4 * r + 2], in.minv[4 * r + 3]));
-        const int nt = (int)(c->objs[in.obj].idx.size() / 3);
-        IL.insts.push_back(f4(ibits((int)root[in.obj]), ibits((int)slot0[in.obj]), ibits((int)in.gid_base), ibits(nt)));
-        /* blas_isect's box pad, 1e-5 (a (2 |o| + W) + k B): a = |w2o|, W
-         * bounds the world extent by |o2w| B + |translation|, k = |o2w| |w2o|
-         * (infinity norms of the linear parts), B the object's extent */
-        double B = 0.0, nm = 0.0, ni_ = 0.0, tr = 0.0;
-        const std::vector<float> &P = c->objs[in.obj].P;
-        for (float v : P) B = std::max(B, (double)fabsf(v));
-        for (int r = 0; r < 3; ++r) {
-            nm = std::max(nm, fabs(in.m[4 * r]) + fabs(in.m[4 * r + 1]) + fabs(in.m[4 * r + 2]));
-            ni_ = std::max(ni_, fabs(in.minv[4 * r]) + fabs(in.minv[4 * r + 1]) + fabs(in.minv[4 * r + 2]));
-            tr = std::max(tr, (double)fabsf(in.m[4 * r + 3]));
-        }
-        const double W = nm * B + tr;
-        IL.insts.push_back(f4(ibits(stack[in.obj]), (float)(ni_ * 1.001), (float)((ni_ * W + nm * ni_ * B) * 1.001), 0.f));
-    }
-    IL.o_objv = put(objv.data(), objv.size() * sizeof(float4));
-    IL.o_objinfo = put(objinfo.data(), objinfo.size() * sizeof(int4));
-    IL.o_objn = put(objn.data(), objn.size() * sizeof(float4));
-    IL.o_objuv = put(objuv.data(), objuv.size() * sizeof(float4));
-    IL.o_objmesh = put(objmesh.data(), objmesh.size() * sizeof(int4));
-    c->obj_tris_stored = (int64_t)objinfo.size();
-    (void)blob;
-    return PM_OK;
-}
-
-int pm_commit(void *ptr) {
-    GROUP_FWD(ptr, pm_commit(sub));
-    GETCTX(ptr);
-    if (c->lights.empty()) FAIL(c, PM_ERR_INVALID, "scene has no lights");
-    const int64_t nt = (int64_t)c->tris.size(), nd = (int64_t)c->disks.size() / 5,
-                  ns = (int64_t)c->spheres.size() / 4;
-    if (nt + nd + ns + (int64_t)c->insts.size() == 0) FAIL(c, PM_ERR_INVALID, "scene has no shapes");
-    if (nt >= (1 << 30) || nd >= (1 << 30) || ns >= (1 << 30)) FAIL(c, PM_ERR_INVALID, "too many primitives");
-    /* global ids: triangles (meshes and instances, in insertion order), then
-     * disks, then spheres (tie-break order) */
-    const int64_t nt_ids = (int64_t)c->next_tri_id;
-    if (nt_ids + nd + ns >= (int64_t)1 << 31) FAIL(c, PM_ERR_INVALID, "too many primitives");
-    for (int64_t i = 0; i < nd; ++i) c->disks[5 * i + 4].w = ibits((int)(nt_ids + i));
-    for (int64_t i = 0; i < ns; ++i) c->spheres[4 * i + 3].w = ibits((int)(nt_ids + nd + i));
-    const int64_t ni = (int64_t)c->insts.size();
-
-    const auto t_commit0 = std::chrono::steady_clock::now();
-    std::vector<BuildPrim> prims(nt);
-    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    auto make_box = [](const float lo[3], const float hi[3], uint32_t ref) {
-        BuildPrim bp;
-        for (int a = 0; a < 3; ++a) {
-            float pad = 1e-4f * std::max(1.0f, std::max(fabsf(lo[a]), fabsf(hi[a])));
-            bp.lo[a] = lo[a] - pad; bp.hi[a] = hi[a] + pad;
-        }
-        bp.ref = ref;
-        return bp;
-    };
-    auto add_box = [&](float lo[3], float hi[3], uint32_t ref) {
-        for (int a = 0; a < 3; ++a) { blo[a] = std::min(blo[a], lo[a]); bhi[a] = std::max(bhi[a], hi[a]); }
-        prims.push_back(make_box(lo, hi, ref));
-    };
-    const float *V = c->P.data();
-    { /* triangle boxes in parallel chunks; the scene box merged per chunk */
-        std::mutex mu;
-        parallel_for(nt, [&](int64_t t0, int64_t t1) {
-            float clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (int64_t t = t0; t < t1; ++t) {
-                const HTri &tr = c->tris[t];
-                float lo[3], hi[3];
-                for (int a = 0; a < 3; ++a) {
-                    float v0 = V[3 * tr.v[0] + a], v1 = V[3 * tr.v[1] + a], v2 = V[3 * tr.v[2] + a];
-                    lo[a] = std::min(v0, std::min(v1, v2)); hi[a] = std::max(v0, std::max(v1, v2));
-                    clo[a] = std::min(clo[a], lo[a]); chi[a] = std::max(chi[a], hi[a]);
-                }
-                prims[t] = make_box(lo, hi, (PRIM_TRI << 30) | (uint32_t)t);
-            }
-            std::lock_guard<std::mutex> g(mu);
-            for (int a = 0; a < 3; ++a) { blo[a] = std::min(blo[a], clo[a]); bhi[a] = std::max(bhi[a], chi[a]); }
-        });
-    }
-    for (int64_t i = 0; i < nd; ++i) {
-        const float4 *d = &c->disks[5 * i];
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int sx = -1; sx <= 1; sx += 2)
-            for (int sy = -1; sy <= 1; sy += 2) { /* cudadisk.cu:87-96 */
-                float p[3] = {d[0].x + sx * d[1].x + sy * d[2].x, d[0].y + sx * d[1].y + sy * d[2].y,
-                              d[0].z + sx * d[1].z + sy * d[2].z};
-                for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); }
-            }
-        add_box(lo, hi, (PRIM_DISK << 30) | (uint32_t)i);
-    }
-    for (int64_t i = 0; i < ns; ++i) {
-        const float *m = &c->sphere_o2w[16 * i];
-        float r = c->spheres[4 * i + 3].x;
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int k = 0; k < 8; ++k) {
-            float x = (k & 1) ? r : -r, y = (k & 2) ? r : -r, z = (k & 4) ? r : -r;
-            float w[3] = {m[0] * x + m[1] * y + m[2] * z + m[3], m[4] * x + m[5] * y + m[6] * z + m[7],
-                          m[8] * x + m[9] * y + m[10] * z + m[11]};
-            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], w[a]); hi[a] = std::max(hi[a], w[a]); }
-        }
-        add_box(lo, hi, (PRIM_SPHERE << 30) | (uint32_t)i);
-    }
-    /* instances: the box of the world vertices the device rebuilds */
-    for (int64_t i = 0; i < ni; ++i) {
-        const HInst &in = c->insts[i];
-        const HObj &o = c->objs[in.obj];
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int v : o.idx) {
-            float w[3];
-            inst_point_h(in.m, &o.P[3 * (size_t)v], w);
-            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], w[a]); hi[a] = std::max(hi[a], w[a]); }
-        }
-        add_box(lo, hi, (PRIM_INST << 30) | (uint32_t)i);
-    }
-    /* env PM_COMMIT_TIMES=1: the build's phases on stderr (setup-time study) */
-    const bool ptimes = getenv("PM_COMMIT_TIMES") != nullptr;
-    auto tnow = [] { return std::chrono::steady_clock::now(); };
-    auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    SceneLayout L;
-    int rc;
-    bool built = false;
-    /* env PM_BVH8=1 (round 6): scenes traversed from HBM get an 8-wide
-     * quantized tree (host build; pm_build.h quantize_bvh8) instead of the
-     * 4-wide one; instanced scenes keep 4-wide trees */
-    const bool bvh8 = ni == 0 && getenv("PM_BVH8") && atoi(getenv("PM_BVH8")) != 0;
-    if (ni == 0 && !bvh8 && gpu_bvh_wanted((int64_t)prims.size())) {
-        if ((rc = commit_gpu_bvh(c, prims, nt, L, built, ptimes))) return rc;
-        if (ptimes && built) fprintf(stderr, "pm_commit: device build, total %.1f ms\n", tms(t_commit0, tnow()));
-    }
-    if (!built) {
-        L = SceneLayout();
-        BvhOut bvh;
-        BvhCost cost;
-        const auto t_build0 = tnow();
-        /* env PM_BVH_BUILD=ploc-host: the device builder's PLOC tree built on
-         * the host (A/B of the tree quality; PM_PLOC_RADIUS) */
-        const char *bb = getenv("PM_BVH_BUILD");
-        if (bb && std::strcmp(bb, "ploc-host") == 0 && prims.size() > 1) {
-            PlocTree pt;
-            build_ploc(prims, ploc_radius(), pt);
-            ploc_to_bvh(prims, pt, bvh);
-        } else {
-            build_bvh(prims, BVH_STACK - 2, bvh, cost);
-        }
-        if (ptimes) fprintf(stderr, "pm_commit: %zu prims (boxes %.1f ms), host build %.1f ms\n", prims.size(),
-                            tms(t_commit0, t_build0), tms(t_build0, tnow()));
-        c->bvh_depth = bvh.depth;
-        if (bvh.depth >= BVH_STACK) FAIL(c, PM_ERR_INVALID, "BVH too deep (%d)", bvh.depth);
-
-        /* tiny LDS scenes skip the BVH (MODE_BRUTE). Their triangles are stored
-         * in global-id order (brute_isect's tie-break relies on it), others in
-         * leaf order. */
-        const bool id_order = ni == 0 && (int64_t)bvh.refs.size() <= BRUTE_MAX_PRIMS;
-        std::vector<uint32_t> tri_order; /* triangle ids in storage order */
-        tri_order.reserve(nt);
-        if (id_order) {
-            for (int64_t t = 0; t < nt; ++t) tri_order.push_back((uint32_t)t);
-        } else {
-            for (uint32_t ref : bvh.refs)
-                if ((ref >> 30) == PRIM_TRI) tri_order.push_back(ref & 0x3fffffffu);
-        }
-        std::vector<uint32_t> slot_of(nt);
-        for (size_t k = 0; k < tri_order.size(); ++k) slot_of[tri_order[k]] = (uint32_t)k;
-        parallel_for((int64_t)bvh.refs.size(), [&](int64_t i0, int64_t i1) {
-            for (int64_t i = i0; i < i1; ++i) {
-                uint32_t &ref = bvh.refs[i];
-                if ((ref >> 30) == PRIM_TRI) ref = (PRIM_TRI << 30) | slot_of[ref & 0x3fffffffu];
-            }
-        });
-
-        /* per-triangle precomputed (p0, e0, e1, n) for the intersector and the
-         * normalized shading frame for hits (in parallel chunks of storage slots) */
-        const int64_t nst = (int64_t)tri_order.size();
-        std::vector<float4> tri_geo(3 * nst), tri_shade(2 * nst);
-        std::vector<int4> tri_info(nst);
-        std::vector<uint32_t> tri_id(nst);
-        parallel_for(nst, [&](int64_t k0, int64_t k1) {
-            for (int64_t k = k0; k < k1; ++k) {
-                tri_record(c, tri_order[k], &tri_geo[3 * k], &tri_shade[2 * k], &tri_info[k]);
-                tri_id[k] = c->tris[tri_order[k]].gid;
-            }
-        });
-        if (ptimes) fprintf(stderr, "pm_commit: triangle records done at %.1f ms\n", tms(t_commit0, tnow()));
-        const std::vector<float4> norms = vertex_normals(c);
-        std::vector<float4> nodes4(bvh.nodes.size() / 4);
-        std::memcpy(nodes4.data(), bvh.nodes.data(), bvh.nodes.size() * sizeof(float));
-
-        /* one blob of 16-B aligned sections: the same offsets address it in HBM
-         * and, for scenes that fit (SceneDev::lds_bytes), in each block's LDS copy */
-        std::vector<unsigned char> blob;
-        /* one reservation for every section (no regrowth copies of a 250 MB blob) */
-        blob.reserve(16 * 16 + nodes4.size() * sizeof(float4) + bvh.refs.size() * 4 + tri_geo.size() * sizeof(float4) +
-                     tri_shade.size() * sizeof(float4) + tri_id.size() * 4 + tri_info.size() * sizeof(int4) +
-                     norms.size() * sizeof(float4) + (c->disks.size() + c->spheres.size() + c->materials.size()) * sizeof(float4) +
-                     c->lights.size() * sizeof(LightDev) + (size_t)(bvh.nodes.size() / 16 + 1) * 64 * 2);
-        auto put = [&](const void *src, size_t n) -> size_t {
-            size_t off = (blob.size() + 15) & ~(size_t)15;
-            blob.resize(off + n, 0);
-            if (n) std::memcpy(&blob[off], src, n);
-            return off;
-        };
-        L.o_nodes = put(nodes4.data(), nodes4.size() * sizeof(float4));
-        L.o_refs = put(bvh.refs.data(), bvh.refs.size() * sizeof(uint32_t));
-        L.o_geo = put(tri_geo.data(), tri_geo.size() * sizeof(float4));
-        L.o_shade = put(tri_shade.data(), tri_shade.size() * sizeof(float4));
-        L.o_tid = put(tri_id.data(), tri_id.size() * sizeof(uint32_t));
-        L.o_info = put(tri_info.data(), tri_info.size() * sizeof(int4));
-        L.o_norms = put(norms.data(), norms.size() * sizeof(float4));
-        L.o_disks = put(c->disks.data(), c->disks.size() * sizeof(float4));
-        L.o_spheres = put(c->spheres.data(), c->spheres.size() * sizeof(float4));
-        L.o_mats = put(c->materials.data(), c->materials.size() * sizeof(float4));
-        L.o_lights = put(c->lights.data(), c->lights.size() * sizeof(LightDev));
-        /* instances: each object mesh's own tree and object-space triangles */
-        InstLayout IL;
-        if (ni > 0 && (rc = commit_objects(c, blob, put, IL))) return rc;
-        /* scenes traversed from HBM also get the 4-wide BVH (half the dependent
-         * node fetches per ray; binary leaves of one primitive);
-         * instanced scenes always (their objects' trees are 4-wide) */
-        bool wide8 = false;
-        if (bvh8 && blob.size() > LDS_SCENE_MAX) {
-            Bvh4Out w;
-            collapse_bvh8(bvh, 1, w);
-            std::vector<uint32_t> qn;
-            if (quantize_bvh8(w.nodes, bvh.refs, qn) && w.max_stack <= BVH8_STACK) {
-                L.o_wnodes = put(qn.data(), qn.size() * sizeof(uint32_t));
-                L.wide = 3;
-                L.wide_stack = w.max_stack;
-                c->bvh4_nodes = (int64_t)(qn.size() / 32);
-                c->bvh4_depth = w.depth;
-                wide8 = true;
-            }
-        }
-        if (!wide8 && (blob.size() > LDS_SCENE_MAX || ni > 0)) {
-            {
-                Bvh4Out w;
-                const auto t_c0 = tnow();
-                collapse_bvh4(bvh, 1, w);
-                if (ptimes) fprintf(stderr, "pm_commit: collapse %.1f ms\n", tms(t_c0, tnow()));
-                /* node format fixed at build time (pm_device.h PM_BVH4_QUANT) */
-                std::vector<uint32_t> qn;
-                const bool quant = PM_BVH4_QUANT != 0;
-                /* a leaf the quantized count cannot code (>= LEAF_TRIS primitives,
-                 * possible at build_bvh's depth limit) keeps the binary traversal,
-                 * like a tree whose stack bound exceeds BVH_STACK. env
-                 * PM_BVH4_BFS=1 renumbers the tree breadth-first, the order the
-                 * device build produces (tests/test_bvh_gpu.py compares them) */
-                const char *bf = getenv("PM_BVH4_BFS");
-                if (bf && atoi(bf) != 0) bvh4_bfs_order(w.nodes);
-                const auto t_q0 = tnow();
-                const bool coded = !quant || quantize_bvh4(w.nodes, bvh.refs, qn);
-                if (ptimes) fprintf(stderr, "pm_commit: quantize %.1f ms\n", tms(t_q0, tnow()));
-                if (ni > 0 && !(coded && quant && w.max_stack + IL.max_stack + 1 <= BVH_STACK))
-                    FAIL(c, PM_ERR_INVALID, "instanced scene: top-level tree not codable (stack %d + %d)", w.max_stack,
-                         IL.max_stack);
-                if (coded && w.max_stack <= BVH_STACK) {
-                    if (ni > 0) { /* the objects' nodes follow the top-level tree's */
-                        const uint32_t top = (uint32_t)(qn.size() / 16);
-                        relocate_bvh4(IL.qn, top);
-                        for (int64_t i = 0; i < ni; ++i) IL.insts[8 * i + 6].x = ibits(fbits_h(IL.insts[8 * i + 6].x) + (int)top);
-                        qn.insert(qn.end(), IL.qn.begin(), IL.qn.end());
-                        L.o_insts = put(IL.insts.data(), IL.insts.size() * sizeof(float4));
-                    }
-                    L.o_wnodes = quant ? put(qn.data(), qn.size() * sizeof(uint32_t))
-                                       : put(w.nodes.data(), w.nodes.size() * sizeof(float));
-                    L.wide = quant ? 2 : 1;
-                    L.wide_stack = w.max_stack + (ni > 0 ? IL.max_stack : 0);
-                    c->bvh4_nodes = (int64_t)(quant ? qn.size() / 16 : w.nodes.size() / 32);
-                    c->bvh4_depth = w.depth;
-                }
-            }
-        }
-        blob.resize(std::max<size_t>((blob.size() + 15) & ~(size_t)15, 16), 0);
-        /* instanced scenes never go LDS-resident (MODE_INST walks the 4-wide trees from HBM) */
-        if (ni > 0 && blob.size() <= LDS_SCENE_MAX) blob.resize(LDS_SCENE_MAX + 16, 0);
-        L.o_objv = IL.o_objv; L.o_objinfo = IL.o_objinfo; L.o_objn = IL.o_objn; L.o_objuv = IL.o_objuv;
-        L.o_objmesh = IL.o_objmesh;
-        const auto t_u0 = tnow();
-        if ((rc = upload(c, c->d_scene, blob))) return rc;
-        if (id_order) {
-            /* triangle pairs for the brute-force loop: pair j = storage slots
-             * 2j, 2j + 1, each of the 12 (p0, e0, e1, n) components as two
-             * adjacent floats, so a scalar load puts the packed operand of
-             * both triangles in an aligned SGPR pair */
-            const int64_t np = nst / 2;
-            std::vector<float> pairs((size_t)std::max<int64_t>(np, 1) * 24, 0.f);
-            const float *geo = reinterpret_cast<const float *>(tri_geo.data());
-            for (int64_t j = 0; j < np; ++j)
-                for (int q = 0; q < 12; ++q)
-                    for (int h = 0; h < 2; ++h) pairs[(size_t)j * 24 + 2 * q + h] = geo[(size_t)(2 * j + h) * 12 + q];
-            if ((rc = upload(c, c->d_tripairs, pairs))) return rc;
-        }
-        if (ptimes) fprintf(stderr, "pm_commit: upload %.1f ms (%zu bytes), total %.1f ms\n", tms(t_u0, tnow()), blob.size(),
-                            tms(t_commit0, tnow()));
-        L.bytes = blob.size();
-        L.n_nodes = (int64_t)nodes4.size() / 4;
-        /* the traversal loops' guard: with instances it must cover an object's tree too */
-        if (ni > 0) L.n_nodes = std::max<int64_t>(L.n_nodes, c->bvh4_nodes);
-        L.n_refs = (int64_t)bvh.refs.size();
-        L.n_tris = (int64_t)tri_info.size();
-        L.id_order = id_order;
-    }
-
+/* SceneDev from the committed layout: every section pointer, the counts, the traversal mode and stack */
+static void fill_scene_dev(Ctx *c) {
+    const SceneLayout &L = c->L;
+    const HostScene &hs = c->hs;
     SceneDev &S = c->S;
     const char *base = c->d_scene.as<char>();
+    const int64_t ni = (int64_t)hs.insts.size();
     S.blob = base;
     S.blob_bytes = (uint32_t)std::min<size_t>(L.bytes, 0xffffffffu);
     S.lds_bytes = L.bytes <= LDS_SCENE_MAX ? (uint32_t)L.bytes : 0u;
-    S.nodes = (const float4 *)(base + L.o_nodes); S.refs = (const uint32_t *)(base + L.o_refs);
-    S.tri_geo = (const float4 *)(base + L.o_geo); S.tri_shade = (const float4 *)(base + L.o_shade);
-    S.tri_id = (const uint32_t *)(base + L.o_tid); S.tri_info = (const int4 *)(base + L.o_info);
-    S.norms = (const float4 *)(base + L.o_norms); S.disks = (const float4 *)(base + L.o_disks);
-    S.spheres = (const float4 *)(base + L.o_spheres); S.materials = (const float4 *)(base + L.o_mats);
-    S.lights = (const LightDev *)(base + L.o_lights);
-    S.n_lights = (int)c->lights.size(); S.n_nodes = (int)L.n_nodes;
+    S.nodes = (const float4 *)(base + L.off[SEC_NODES]); S.refs = (const uint32_t *)(base + L.off[SEC_REFS]);
+    S.tri_geo = (const float4 *)(base + L.off[SEC_GEO]); S.tri_shade = (const float4 *)(base + L.off[SEC_SHADE]);
+    S.tri_id = (const uint32_t *)(base + L.off[SEC_TID]); S.tri_info = (const int4 *)(base + L.off[SEC_INFO]);
+    S.norms = (const float4 *)(base + L.off[SEC_NORMS]); S.disks = (const float4 *)(base + L.off[SEC_DISKS]);
+    S.spheres = (const float4 *)(base + L.off[SEC_SPHERES]); S.materials = (const float4 *)(base + L.off[SEC_MATS]);
+    S.lights = (const LightDev *)(base + L.off[SEC_LIGHTS]);
+    S.n_lights = (int)hs.lights.size(); S.n_nodes = (int)L.n_nodes;
     S.n_refs = (int)L.n_refs;
-    S.n_tris = (int)L.n_tris; S.n_disks = (int)nd; S.n_spheres = (int)ns;
+    S.n_tris = (int)L.n_tris; S.n_disks = (int)(hs.disks.size() / 5); S.n_spheres = (int)(hs.spheres.size() / 4);
     S.tri_geo_g = S.tri_geo; S.tri_id_g = S.tri_id;
     S.tri_pairs_g = L.id_order ? c->d_tripairs.as<float>() : nullptr;
-    if ((rc = upload(c, c->d_light_tris, c->light_tris))) return rc;
     S.light_tris = c->d_light_tris.as<LightTri>();
     S.n_inst = (int)ni;
-    S.insts = ni ? (const float4 *)(base + L.o_insts) : nullptr;
-    S.obj_v = ni ? (const float4 *)(base + L.o_objv) : nullptr;
-    S.obj_info = ni ? (const int4 *)(base + L.o_objinfo) : nullptr;
-    S.obj_n = ni ? (const float4 *)(base + L.o_objn) : nullptr;
-    S.obj_uv = ni ? (const float4 *)(base + L.o_objuv) : nullptr;
-    S.obj_mesh = ni ? (const int4 *)(base + L.o_objmesh) : nullptr;
+    S.insts = ni ? (const float4 *)(base + L.off[SEC_INSTS]) : nullptr;
+    S.obj_v = ni ? (const float4 *)(base + L.off[SEC_OBJV]) : nullptr;
+    S.obj_info = ni ? (const int4 *)(base + L.off[SEC_OBJINFO]) : nullptr;
+    S.obj_n = ni ? (const float4 *)(base + L.off[SEC_OBJN]) : nullptr;
+    S.obj_uv = ni ? (const float4 *)(base + L.off[SEC_OBJUV]) : nullptr;
+    S.obj_mesh = ni ? (const int4 *)(base + L.off[SEC_OBJMESH]) : nullptr;
     S.brute = (S.lds_bytes > 0 && L.id_order) ? 1 : 0;
     /* a push happens only when descending a level, so depth + 1 entries suffice;
      * sizing the LDS stack by the actual tree keeps occupancy VGPR-bound */
     S.stack_depth = std::min(BVH_STACK, std::max(2, c->bvh_depth + 2));
     S.wide = L.wide;
-    S.wnodes = L.wide ? (const float4 *)(base + L.o_wnodes) : nullptr;
+    S.wnodes = L.wide ? (const float4 *)(base + L.off[SEC_WNODES]) : nullptr;
     /* wide scenes traverse only the 4-wide tree (traverse() dispatches every
      * MODE_GLOBAL query to traverse4): its exact stack bound sizes the LDS
      * stacks, not the binary tree's depth — k_trace_pool's 256-thread blocks
      * then fit four per CU (its VGPR occupancy) instead of three */
     if (L.wide) S.stack_depth = std::min(L.wide == 3 ? BVH8_STACK : BVH_STACK, std::max(2, L.wide_stack + 1));
-    for (int a = 0; a < 3; ++a) { c->bbox_lo[a] = blo[a]; c->bbox_hi[a] = bhi[a]; }
-    double em = 0.0, kd = 1.0;
-    for (const LightDev &L : c->lights) {
-        double le = std::max({std::fabs(L.le.x), std::fabs(L.le.y), std::fabs(L.le.z)});
-        /* emitted power bound (sample_le's Le / pdf): a point light's 4 pi I; a
-         * disk's Le area 2 pi; a mesh's the same with its total area */
-        switch (fbits_h(L.o_type.w)) {
-        case PM_LIGHT_POINT: em = std::max(em, le * 4.0 * M_PI); break;
-        case PM_LIGHT_AREA_DISK: em = std::max(em, le * L.n_area.w * 2.0 * M_PI); break;
-        case PM_LIGHT_AREA_MESH: em = std::max(em, le * L.n_area.w * 2.0 * M_PI); break; /* n_area.w: the total area */
-        default: FAIL(c, PM_ERR_INVALID, "light type %d has no emitted-power bound", fbits_h(L.o_type.w));
-        }
+}
+
+int pm_commit(void *ptr) {
+    GROUP_FWD(ptr, pm_commit(sub));
+    GETCTX(ptr);
+    std::string err;
+    int rc;
+    if ((rc = validate_scene(c->hs, err))) FAIL(c, rc, "%s", err.c_str());
+    const BuildOptions opt = build_options_from_env();
+    const auto t_commit0 = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point a) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+    };
+    std::vector<BuildPrim> prims;
+    scene_boxes(c->hs, prims, c->bbox_lo, c->bbox_hi);
+
+    bool built = false;
+    if (c->hs.insts.empty() && !opt.bvh8 && gpu_bvh_wanted(opt, (int64_t)prims.size())) {
+        if ((rc = commit_gpu_bvh(c, prims, opt, c->L, built))) return rc;
+        if (opt.times && built) fprintf(stderr, "pm_commit: device build, total %.1f ms\n", since(t_commit0));
     }
-    for (const float4 &m : c->materials)
-        if (fbits_h(m.w) == PM_MATTE) kd = std::max({kd, (double)m.x, (double)m.y, (double)m.z});
-    c->emit_max = std::max(em, 1e-30);
-    c->kd_max = kd;
-    /* PM_ALL_LIGHTS: the selection table, and the weight bound with the pick's
-     * probability divided out. A scene that emits nothing keeps a zero table:
-     * a fixed light_source_index still renders it, PM_ALL_LIGHTS is refused
-     * (check_params) */
-    {
-        const size_t nl = c->lights.size();
-        std::vector<int> types(nl);
-        std::vector<float> rgb(3 * nl), areas(nl);
-        for (size_t l = 0; l < nl; ++l) {
-            const LightDev &L = c->lights[l];
-            types[l] = fbits_h(L.o_type.w);
-            rgb[3 * l] = L.le.x; rgb[3 * l + 1] = L.le.y; rgb[3 * l + 2] = L.le.z;
-            areas[l] = L.n_area.w;
-        }
-        c->light_cdf.assign(nl, 0.f);
-        const std::string err_before = g_last_error;
-        c->light_cdf_ok = pm_light_selection_cdf(types.data(), rgb.data(), areas.data(), (int)nl, c->light_cdf.data()) == PM_OK;
-        if (!c->light_cdf_ok) { g_last_error = err_before; c->light_cdf.assign(nl, 0.f); }
-        if ((rc = upload(c, c->d_light_cdf, c->light_cdf))) return rc;
-        double em_all = 0.0;
-        for (size_t l = 0; l < nl && c->light_cdf_ok; ++l) {
-            const LightDev &L = c->lights[l];
-            const float pmf = c->light_cdf[l] - (l ? c->light_cdf[l - 1] : 0.f);
-            if (!(pmf > 0.f)) continue; /* never picked */
-            const double le = std::max({std::fabs(L.le.x), std::fabs(L.le.y), std::fabs(L.le.z)});
-            const double bound = fbits_h(L.o_type.w) == PM_LIGHT_POINT ? le * 4.0 * M_PI : le * L.n_area.w * 2.0 * M_PI;
-            em_all = std::max(em_all, bound / (double)pmf);
-        }
-        c->emit_max_all = std::max(em_all, 1e-30);
+    if (!built) {
+        SceneBlob blob;
+        if ((rc = assemble_scene(c->hs, prims, opt, t_commit0, blob, err))) FAIL(c, rc, "%s", err.c_str());
+        const auto t_u0 = std::chrono::steady_clock::now();
+        if ((rc = upload(c, c->d_scene, blob.bytes))) return rc;
+        if (blob.layout.id_order && (rc = upload(c, c->d_tripairs, blob.tri_pairs))) return rc;
+        if (opt.times) fprintf(stderr, "pm_commit: upload %.1f ms (%zu bytes), total %.1f ms\n", since(t_u0), blob.bytes.size(),
+                               since(t_commit0));
+        c->L = blob.layout;
+        c->bvh_depth = blob.bvh_depth;
+        if (blob.layout.wide) { c->bvh4_nodes = blob.bvh4_nodes; c->bvh4_depth = blob.bvh4_depth; }
     }
-    bool nn = true;
-    for (const LightDev &L : c->lights) nn = nn && L.le.x >= 0.f && L.le.y >= 0.f && L.le.z >= 0.f && L.n_area.w >= 0.f;
-    for (const float4 &m : c->materials)
-        if (fbits_h(m.w) == PM_MATTE) nn = nn && m.x >= 0.f && m.y >= 0.f && m.z >= 0.f;
-    c->scene_nonneg = nn;
+    if ((rc = upload(c, c->d_light_tris, c->hs.light_tris))) return rc;
+    fill_scene_dev(c);
+
+    if ((rc = light_summary(c->hs, c->lsum, err))) FAIL(c, rc, "%s", err.c_str());
+    if ((rc = upload(c, c->d_light_cdf, c->lsum.cdf))) return rc;
     c->committed = true;
     return PM_OK;
 }
@@ -2237,7 +1675,7 @@ static int gather_common(Ctx *c, const pm_render_params *p, long long *partial, 
          * the per-record scale per term (x4 headroom in amax), exact as a float
          * and as an int32, and <= PM_KNN_MAX = 2^6 terms sum below 2^28 —
          * exact in int32 */
-        const double amax = emission_bound(c, p) * std::pow(c->kd_max, (double)p->max_photon_count) * 4.0;
+        const double amax = emission_bound(c, p) * std::pow(c->lsum.kd_max, (double)p->max_photon_count) * 4.0;
         G.knn_fx = (float)(std::ldexp(1.0, 24) / std::max(amax, 1e-30));
         G.slots = c->d_slots.as<pm_photon>();
         if (c->knn_ss && !c->counting && c->gather_kernel == PM_GK_TILE) {
@@ -2932,7 +2370,7 @@ int pm_scene_info(void *ptr, int64_t out[7]) {
     GETCTX(ptr);
     if (!c->S.blob) FAIL(c, PM_ERR_INVALID, "no scene committed");
     const SceneDev &S = c->S;
-    out[0] = c->next_tri_id;   /* triangles rendered: meshes + every instance's */
+    out[0] = c->hs.next_tri_id;   /* triangles rendered: meshes + every instance's */
     out[1] = S.n_disks; out[2] = S.n_spheres;
     /* the tree the kernels traverse: the 4-wide BVH when the scene has one
      * (either builder), else the binary SAH tree */
@@ -2948,19 +2386,20 @@ int pm_scene_section(void *ptr, int section, void *out, int64_t max_bytes, int64
     GETCTX(ptr);
     if (!c->S.blob) FAIL(c, PM_ERR_INVALID, "no scene committed");
     const SceneDev &S = c->S;
+    const SceneLayout &L = c->L;
     const void *src = nullptr;
     int64_t n = 0;
     switch (section) {
-    case PM_SCENE_REFS: src = S.refs; n = 4 * (int64_t)S.n_refs; break;
-    case PM_SCENE_TRI_GEO: src = S.tri_geo; n = 48 * (int64_t)S.n_tris; break;
-    case PM_SCENE_TRI_SHADE: src = S.tri_shade; n = 32 * (int64_t)S.n_tris; break;
-    case PM_SCENE_TRI_ID: src = S.tri_id; n = 4 * (int64_t)S.n_tris; break;
-    case PM_SCENE_TRI_INFO: src = S.tri_info; n = 16 * (int64_t)S.n_tris; break;
-    case PM_SCENE_BVH4: src = S.wnodes; n = S.wide ? (S.wide == 2 ? 64 : 128) * c->bvh4_nodes : 0; break; /* 3: 8-wide, 128 B */
-    case PM_SCENE_INSTANCES: src = S.insts; n = 128 * (int64_t)S.n_inst; break;
-    case PM_SCENE_OBJ_TRIS: src = S.obj_v; n = S.n_inst ? 48 * c->obj_tris_stored : 0; break;
-    case PM_SCENE_LIGHT_TRIS: src = S.light_tris; n = (int64_t)(c->light_tris.size() * sizeof(LightTri)); break;
-    case PM_SCENE_LIGHT_CDF: src = c->d_light_cdf.p; n = 4 * (int64_t)c->light_cdf.size(); break;
+    case PM_SCENE_REFS: src = S.refs; n = (int64_t)L.size[SEC_REFS]; break;
+    case PM_SCENE_TRI_GEO: src = S.tri_geo; n = (int64_t)L.size[SEC_GEO]; break;
+    case PM_SCENE_TRI_SHADE: src = S.tri_shade; n = (int64_t)L.size[SEC_SHADE]; break;
+    case PM_SCENE_TRI_ID: src = S.tri_id; n = (int64_t)L.size[SEC_TID]; break;
+    case PM_SCENE_TRI_INFO: src = S.tri_info; n = (int64_t)L.size[SEC_INFO]; break;
+    case PM_SCENE_BVH4: src = S.wnodes; n = (int64_t)L.size[SEC_WNODES]; break; /* the wide tree, whichever format */
+    case PM_SCENE_INSTANCES: src = S.insts; n = (int64_t)L.size[SEC_INSTS]; break;
+    case PM_SCENE_OBJ_TRIS: src = S.obj_v; n = (int64_t)L.size[SEC_OBJV]; break;
+    case PM_SCENE_LIGHT_TRIS: src = S.light_tris; n = (int64_t)(c->hs.light_tris.size() * sizeof(LightTri)); break;
+    case PM_SCENE_LIGHT_CDF: src = c->d_light_cdf.p; n = (int64_t)(c->lsum.cdf.size() * sizeof(float)); break;
     default: FAIL(c, PM_ERR_INVALID, "unknown scene section %d", section);
     }
     if (bytes) *bytes = n;

@@ -14,6 +14,7 @@
 
 #include "../../include/pm_api.h"
 #include "../../include/pm_detmath.h"
+#include "pm_scene_pod.h"
 
 #pragma clang fp contract(off)
 
@@ -56,32 +57,7 @@ constexpr float INV_TWOPI = 0.15915494309189533577f;
 constexpr float RT_DEFAULT_MAX = 1.e27f;
 
 /* ---------------------------------------------------------- scene layout */
-/* prim ref = (kind << 30) | index */
-/* PRIM_INST: an object instance (pm_add_mesh_instance) in the top-level
- * tree; a hit on one of its triangles carries (PRIM_INST << 30) | the
- * object triangle's storage slot, and the triangle's global id */
-enum : uint32_t { PRIM_TRI = 0u, PRIM_DISK = 1u, PRIM_SPHERE = 2u, PRIM_INST = 3u };
-
-struct LightDev {      /* CudaLightDevice (common.cu.h:47-59), 80 B */
-    float4 o_type;     /* o.xyz, type (int bits) */
-    float4 p1_ns;      /* p1.xyz, nSample (int bits) */
-    float4 p2_r2d;     /* p2.xyz, random2DStart (int bits) */
-    float4 n_area;     /* normal.xyz, area */
-    float4 le;         /* intensity.xyz, 0 */
-    /* PM_LIGHT_AREA_MESH (ours) has no o / p1 / p2 / normal: o_type.x, .y
-     * hold (int bits) the first entry and the entry count of its triangles
-     * in SceneDev::light_tris, o_type.z its reverse_orientation flag;
-     * n_area.w is the mesh's total area, the other lanes as above */
-};
-
-/* one emitting triangle of a mesh light, 64 B (four 16-B loads per lane) */
-struct LightTri {
-    float4 p0_cdf;     /* p0.xyz, cdf[k] of the light's area distribution */
-    float4 e1;         /* p1 - p0, 0 */
-    float4 e2;         /* p2 - p0, 0 */
-    float4 n;          /* unit normal of the emitting side, 0 */
-};
-
+/* prim refs, LightDev, LightTri, LDS_SCENE_MAX, BRUTE_MAX_PRIMS, BVH_STACK_DEPTH: pm_scene_pod.h */
 struct SceneDev {
     const float4 *nodes;     /* 4 float4 per BVH node */
     const uint32_t *refs;    /* leaf primitive refs */
@@ -149,21 +125,12 @@ struct SceneDev {
     uint32_t lds_bytes; /* = blob_bytes when the blob fits LDS_SCENE_MAX (LDS-resident mode), else 0 */
 };
 
-/* Scenes up to this size are copied into each block's LDS and traversed from
- * there (Cornell C2: ~4 KB); larger ones are traversed from HBM/L2. */
-constexpr uint32_t LDS_SCENE_MAX = 16384;
-/* LDS scenes with at most this many primitives skip the BVH: every lane
- * tests every primitive (MODE_BRUTE) */
-constexpr int BRUTE_MAX_PRIMS = 64;
-
 /* how the kernels see the scene (template argument of the traversal kernels) */
 enum SceneMode : int { MODE_GLOBAL = 0, MODE_LDS = 1, MODE_BRUTE = 2, MODE_INST = 3 };
 /* MODE_INST: a MODE_GLOBAL scene with object instances (two-level 4-wide trees) */
 constexpr bool mode_lds(int mode) { return mode == MODE_LDS || mode == MODE_BRUTE; }
 
 struct Ray { v3 o, d; float tmin, tmax; };
-
-constexpr int BVH_STACK_DEPTH = 48; /* LDS stack entries per lane (builder caps depth below it) */
 
 struct Hit {
     uint32_t ref;   /* prim ref of the winner */
@@ -718,9 +685,6 @@ PMD bool traverse(const SceneDev &S, const Ray &ray, Hit &best, int *stack, int 
  * 24 byte conversions + 24 multiply-adds more per node. */
 #ifndef PM_QSLAB
 #define PM_QSLAB 1 /* quantized planes folded into the slab test (node4_decode) */
-#endif
-#ifndef PM_BVH4_QUANT
-#define PM_BVH4_QUANT 1 /* build-time node format: 1 = quantized 64-B nodes, 0 = 128-B float nodes */
 #endif
 /* a quantized node's four child boxes against the ray (the node's 64 B
  * already loaded: trav_step requests them ahead) */
