@@ -16,6 +16,7 @@
 #include "core/film.h"
 #include "cudarender.h"
 #include "lights/diffuse.h"
+#include "lights/distant.h"
 #include "lights/point.h"
 #include "materials/glass.h"
 #include "materials/matte.h"
@@ -216,6 +217,12 @@ void CudaRender::Render(const Scene *scene) {
             L.kind = pmcuda::Light::Point;
             L.pos[0] = pl->lightPos.x; L.pos[1] = pl->lightPos.y; L.pos[2] = pl->lightPos.z;
             L.intensity = toPm(pl->Intensity);
+            lights.push_back(L);
+        } else if (DistantLight *dl = dynamic_cast<DistantLight *>(l)) { /* beyond the reference */
+            pmcuda::Light L;
+            L.kind = pmcuda::Light::Distant;
+            L.dir[0] = dl->lightDir.x; L.dir[1] = dl->lightDir.y; L.dir[2] = dl->lightDir.z;
+            L.intensity = toPm(dl->L);
             lights.push_back(L);
         } else if (DiffuseAreaLight *al = dynamic_cast<DiffuseAreaLight *>(l)) {
             uint32_t samplePerShape = (uint32_t)std::max(1, al->nSamples);

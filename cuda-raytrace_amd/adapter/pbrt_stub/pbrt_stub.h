@@ -9,7 +9,7 @@
  * replaces this directory by pbrt-v2's src/ (see INTEGRATION.md §2).
  *
  * The fork exposes members that upstream pbrt-v2 keeps protected / private
- * (TriangleMesh::p, Sphere::radius, Disk::*, PointLight::lightPos,
+ * (TriangleMesh::p, Sphere::radius, Disk::*, PointLight::lightPos, DistantLight::*,
  * DiffuseAreaLight::shapeSet, MatteMaterial::Kd, ...); the reference reads
  * them directly (util/shape/cudatrianglemesh.cpp:18-66, cudasphere.cpp:17-29,
  * cudadisk.cpp:17-35, util/light/cudalight.cpp:16-57,
@@ -292,7 +292,7 @@ public:
     Reference<Texture<float> > index, bumpMap;
 };
 
-/* ---- core/light.h, lights/point.h, lights/diffuse.h ------------------------ */
+/* ---- core/light.h, lights/point.h, lights/distant.h, lights/diffuse.h */
 class Light {
 public:
     virtual ~Light() {}
@@ -311,6 +311,13 @@ public:
         : Light(light2world), lightPos(light2world(Point(0, 0, 0))), Intensity(intensity) {}
     Point lightPos;
     Spectrum Intensity;
+};
+class DistantLight : public Light { /* pbrt-v2 DistantLight(l2w, radiance, dir): dir points towards the light */
+public:
+    DistantLight(const Transform &light2world, const Spectrum &radiance, const Vector &dir)
+        : Light(light2world), lightDir(Normalize(light2world(dir))), L(radiance) {}
+    Vector lightDir;
+    Spectrum L;
 };
 class DiffuseAreaLight : public AreaLight {
 public:

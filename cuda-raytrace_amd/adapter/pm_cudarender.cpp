@@ -249,6 +249,11 @@ void CudaRender::addLights(const std::vector<Light> &lights) {
         if (L.kind == Light::Point) {
             const float I[3] = {L.intensity.r, L.intensity.g, L.intensity.b};
             check(ctx_, pm_add_light_point(ctx_, L.pos, I), "pm_add_light_point");
+        } else if (L.kind == Light::Distant) {
+            const float Lr[3] = {L.intensity.r, L.intensity.g, L.intensity.b};
+            int index = -1;
+            check(ctx_, pm_add_light_distant(ctx_, L.dir, Lr, &index), "pm_add_light_distant");
+            if (index != (int)(&L - lights.data())) throw Error("pm_add_light_distant: light indices follow the list's order");
         } else if (L.kind == Light::AreaMesh) {
             const float Le[3] = {L.Lemit.r, L.Lemit.g, L.Lemit.b};
             int index = -1;

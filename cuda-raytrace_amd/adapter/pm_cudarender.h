@@ -82,10 +82,14 @@ struct Shape {
 
 /* pbrt lights as CudaLight::setupLight flattens them (cudalight.cpp:16-59):
  * PointLight, or DiffuseAreaLight over disk shapes; and, beyond the
- * reference, DiffuseAreaLight over a triangle mesh (pm_add_light_mesh). */
+ * reference, DiffuseAreaLight over a triangle mesh (pm_add_light_mesh) and
+ * DistantLight (pm_add_light_distant). */
 struct Light {
-    enum Kind { Point, AreaDisk, AreaMesh } kind = Point;
+    enum Kind { Point, AreaDisk, AreaMesh, Distant } kind = Point;
     float pos[3] = {0, 0, 0}; /* Point */
+    /* Distant: the world-space direction towards the light, pbrt's lightDir
+     * (any non-zero length), with intensity = L */
+    float dir[3] = {0, 0, 1};
     RGB intensity = {0, 0, 0};
     Shape disk;               /* AreaDisk: the disk shape (radius, height, o2w) */
     Shape mesh;               /* AreaMesh: the world-space triangle mesh (P, indices) */

@@ -686,6 +686,20 @@ struct PbrtParser::Impl {
                     if (from.size() == 3) for (int a = 0; a < 3; ++a) L.pos[a] = L.pos[a] + from[a];
                     L.intensity = RGB{I.r * sc.r, I.g * sc.g, I.b * sc.b};
                     opts->lights.push_back(L);
+                } else if (n == "distant") { /* pbrt CreateDistantLight: lightDir = Normalize(light2world(from - to)) */
+                    const RGB Lr = spectrum(lx, line, ps, "L", RGB{1.f, 1.f, 1.f});
+                    const RGB sc = spectrum(lx, line, ps, "scale", RGB{1.f, 1.f, 1.f});
+                    const std::vector<float> from = ps.floats("from"), to = ps.floats("to");
+                    const float f[3] = {from.size() == 3 ? from[0] : 0.f, from.size() == 3 ? from[1] : 0.f,
+                                        from.size() == 3 ? from[2] : 0.f};
+                    const float t[3] = {to.size() == 3 ? to[0] : 0.f, to.size() == 3 ? to[1] : 0.f,
+                                        to.size() == 3 ? to[2] : 1.f};
+                    const float d[3] = {f[0] - t[0], f[1] - t[1], f[2] - t[2]};
+                    Light L;
+                    L.kind = Light::Distant;
+                    ctm.vector(d, L.dir);
+                    L.intensity = RGB{Lr.r * sc.r, Lr.g * sc.g, Lr.b * sc.b};
+                    opts->lights.push_back(L);
                 } else {
                     warn(lx, line, "UnImplemented Cuda Light Source: %s", n); /* cudalight.cpp:11-14,67-69 */
                 }

@@ -10,7 +10,8 @@
  *                CoordinateSystem CoordSysTransform TransformBegin/End
  *   state        WorldBegin/End AttributeBegin/End ReverseOrientation
  *                Material MakeNamedMaterial NamedMaterial Texture (constant)
- *   lights       LightSource "point" (I, scale, from), AreaLightSource "diffuse"
+ *   lights       LightSource "point" (I, scale, from), "distant" (L, scale,
+ *                from, to; towards the light = CTM (from - to)), AreaLightSource "diffuse"
  *                (L, scale, nsamples) on the following "disk" and
  *                "trianglemesh" shapes (a mesh emits from the side of
  *                cross(p1 - p0, p2 - p0); ReverseOrientation flips it)

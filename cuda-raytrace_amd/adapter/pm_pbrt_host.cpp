@@ -17,6 +17,7 @@
  *        --photonmap grid|kdtree --renderer photonmap|simple --nsamples S --instanced
  *        --quad-light]   (the box's own 130 x 105 quad light, a trianglemesh, instead of the disk)
  *        [--two-lights]  (scenes/cornell-two-lights.pbrt: the disk, then a blue quad light on the green wall)
+ *        [--sun]         (scenes/cornell-sun.pbrt: a DistantLight through the open front, the last light)
  *        [--lightsource K]  (Renderer "cuda" "integer lightsource" [K]; -1: photons from every light)
  * The header's third word is the number of light 2D samples per ray
  * (nsamples per area light).
@@ -30,6 +31,7 @@
 #include "core/film.h"
 #include "cudaapi.h"
 #include "lights/diffuse.h"
+#include "lights/distant.h"
 #include "materials/matte.h"
 #include "shapes/disk.h"
 #include "shapes/trianglemesh.h"
@@ -39,7 +41,7 @@ namespace {
 struct Opts {
     int W = 64, H = 48, paths = 16384, nsamples = 1;
     std::string photonmap = "grid", renderer = "photonmap", out;
-    bool instanced = false, quad_light = false, two_lights = false;
+    bool instanced = false, quad_light = false, two_lights = false, sun = false;
     int lightsource = 0;
     bool lightsource_set = false;
     /* --devicecamera: the Renderer "cuda" ParamSet's device camera + film */
@@ -206,6 +208,14 @@ int run(const Opts &o) {
         scene.lights.push_back(area2);
         CreateCudaShape("trianglemesh", wallq, NULL, black.GetPtr(), 1);
     }
+    /* --sun (scenes/cornell-sun.pbrt): LightSource "distant" "rgb L" [3 2.7 2.1]
+     * "point from" [0 120 -400] "point to" [0 0 0], the last light */
+    DistantLight *sun = NULL;
+    if (o.sun) {
+        const float Ls[3] = {3.f, 2.7f, 2.1f};
+        sun = new DistantLight(identity, RGBSpectrum::FromRGB(Ls, SPECTRUM_ILLUMINANT), Vector(0.f, 120.f, -400.f));
+        scene.lights.push_back(sun);
+    }
     /* MakeRenderer: Renderer "cuda" */
     KeepFilm *film = new KeepFilm(o.W, o.H);
     RecordingCamera *camera = new RecordingCamera(film, o.W, o.H);
@@ -239,6 +249,7 @@ int run(const Opts &o) {
     delete renderer; /* pbrt deletes its Renderer */
     delete area;
     delete area2;
+    delete sun;
     return 0;
 }
 
@@ -258,6 +269,7 @@ int main(int argc, char **argv) {
         else if (a == "--instanced") o.instanced = true;
         else if (a == "--quad-light") o.quad_light = true;
         else if (a == "--two-lights") o.two_lights = true;
+        else if (a == "--sun") o.sun = true;
         else if (a == "--lightsource") { o.lightsource = std::stoi(val()); o.lightsource_set = true; }
         else if (a == "--out") o.out = val();
         else if (a == "--devicecamera") o.devicecamera = 1;

@@ -298,6 +298,12 @@ int dump(const std::string &path, const CameraFlags &cflags) {
             DumpSink::arr(lights, L.pos, 3);
             lights += ", \"I\": ";
             DumpSink::arr(lights, I, 3);
+        } else if (L.kind == Light::Distant) {
+            const float Lr[3] = {L.intensity.r, L.intensity.g, L.intensity.b};
+            lights += "{\"kind\": \"distant\", \"to_light\": ";
+            DumpSink::arr(lights, L.dir, 3);
+            lights += ", \"L\": ";
+            DumpSink::arr(lights, Lr, 3);
         } else if (L.kind == Light::AreaMesh) {
             const float Le[3] = {L.Lemit.r, L.Lemit.g, L.Lemit.b};
             std::snprintf(b, sizeof b, "{\"kind\": \"mesh\", \"nsamples\": %d, \"reverse_orientation\": %d, \"Le\": ",
@@ -347,13 +353,17 @@ int dump(const std::string &path, const CameraFlags &cflags) {
     {
         std::vector<int> types;
         std::vector<float> rgb, areas, table(o.lights.size());
+        bool known = true; /* a distant light's weight needs the commit's world sphere: no table here */
         for (const Light &L : o.lights) {
-            const RGB c = L.kind == Light::Point ? L.intensity : L.Lemit;
-            types.push_back(L.kind == Light::Point ? PM_LIGHT_POINT : L.kind == Light::AreaMesh ? PM_LIGHT_AREA_MESH : PM_LIGHT_AREA_DISK);
+            const bool delta = L.kind == Light::Point || L.kind == Light::Distant;
+            const RGB c = delta ? L.intensity : L.Lemit;
+            types.push_back(L.kind == Light::Point ? PM_LIGHT_POINT : L.kind == Light::Distant ? PM_LIGHT_DISTANT :
+                            L.kind == Light::AreaMesh ? PM_LIGHT_AREA_MESH : PM_LIGHT_AREA_DISK);
             rgb.push_back(c.r); rgb.push_back(c.g); rgb.push_back(c.b);
-            areas.push_back(L.kind == Light::Point ? 0.f : lightArea(L));
+            if (L.kind == Light::Distant) known = false;
+            areas.push_back(delta ? 0.f : lightArea(L));
         }
-        if (!o.lights.empty() &&
+        if (!o.lights.empty() && known &&
             pm_light_selection_cdf(types.data(), rgb.data(), areas.data(), (int)types.size(), table.data()) == PM_OK) {
             cdf.clear();
             DumpSink::arr(cdf, table.data(), table.size());

@@ -66,6 +66,7 @@ struct Ctx {
     std::string err;
     HostScene hs; /* the host scene (pm_scene.h): the pm_add_* calls fill it, pm_commit assembles it */
     int rand2d_total = 0;
+    float world_sphere[4] = {0, 0, 0, 0}; /* PM_SCENE_WORLD_SPHERE, of the last commit */
     int pinhole = 0, W = 0, H = 0;
     /* pm_set_camera: pinhole = 1 and W x H the sample raster (image * strata),
      * so records, views and bands are the pinhole's; cam keeps the image size,
@@ -972,6 +973,21 @@ int pm_add_light_mesh(void *ptr, const float *P, int nverts, const int *idx, int
     return PM_OK;
 }
 
+/* the record is made, and the parameters checked, in the host-only unit
+ * (pm_scene.cpp), before the context is looked at */
+int pm_add_light_distant(void *ptr, const float to_light[3], const float Lrgb[3], int *out_light) {
+    LightDev L{};
+    std::string err;
+    if (!out_light) FAIL((Ctx *)nullptr, PM_ERR_INVALID, "pm_add_light_distant: null pointer");
+    if (int rc = make_distant_light(to_light, Lrgb, L, err)) FAIL((Ctx *)nullptr, rc, "%s", err.c_str());
+    GROUP_FWD(ptr, pm_add_light_distant(sub, to_light, Lrgb, out_light));
+    GETCTX(ptr);
+    c->hs.lights.push_back(L);
+    *out_light = (int)c->hs.lights.size() - 1;
+    c->committed = false;
+    return PM_OK;
+}
+
 int pm_set_pinhole(void *ptr, const float eye[3], const float fwd[3], const float right[3], const float up[3], int W,
                    int H) {
     GROUP_FWD(ptr, pm_set_pinhole(sub, eye, fwd, right, up, W, H));
@@ -1205,6 +1221,8 @@ int pm_commit(void *ptr) {
     };
     std::vector<BuildPrim> prims;
     scene_boxes(c->hs, prims, c->bbox_lo, c->bbox_hi);
+    /* the distant lights' records, before either builder copies the lights */
+    if ((rc = finish_lights(c->hs, c->bbox_lo, c->bbox_hi, c->world_sphere, err))) FAIL(c, rc, "%s", err.c_str());
 
     bool built = false;
     if (c->hs.insts.empty() && !opt.bvh8 && gpu_bvh_wanted(opt, (int64_t)prims.size())) {
@@ -2400,6 +2418,13 @@ int pm_scene_section(void *ptr, int section, void *out, int64_t max_bytes, int64
     case PM_SCENE_OBJ_TRIS: src = S.obj_v; n = (int64_t)L.size[SEC_OBJV]; break;
     case PM_SCENE_LIGHT_TRIS: src = S.light_tris; n = (int64_t)(c->hs.light_tris.size() * sizeof(LightTri)); break;
     case PM_SCENE_LIGHT_CDF: src = c->d_light_cdf.p; n = (int64_t)(c->lsum.cdf.size() * sizeof(float)); break;
+    case PM_SCENE_WORLD_SPHERE: /* a host value */
+        if (bytes) *bytes = (int64_t)sizeof c->world_sphere;
+        if (out) {
+            if (max_bytes < (int64_t)sizeof c->world_sphere) FAIL(c, PM_ERR_INVALID, "scene section needs 16 bytes");
+            std::memcpy(out, c->world_sphere, sizeof c->world_sphere);
+        }
+        return PM_OK;
     default: FAIL(c, PM_ERR_INVALID, "unknown scene section %d", section);
     }
     if (bytes) *bytes = n;

@@ -1379,6 +1379,11 @@ PMD v3 sample_l_shading(const LightDev &L, const LightTri *tris, v3 point, float
         *pdf = 1.f;
         return xyz(L.le) * invlength2;
     }
+    if (type == PM_LIGHT_DISTANT) { /* 2 R to_light: the shadow segment ends outside the world sphere */
+        *uwi = -(xyz(L.n_area) * L.le.w);
+        *pdf = 1.f;
+        return xyz(L.le);
+    }
     if (type == PM_LIGHT_AREA_MESH) { /* the disk's estimator below, with the sampled triangle's normal */
         v3 n;
         *uwi = sample_light_mesh(L, tris, u1, u2, &n) - point;
@@ -1409,6 +1414,16 @@ PMD v3 sample_le(const LightDev &L, const LightTri *tris, float lu1, float lu2, 
         *Ns = ray->d;
         *pdf = (float)(1.f / (4.f * M_PI));
         return xyz(L.le);
+    }
+    if (type == PM_LIGHT_DISTANT) { /* the disk's point below on the world sphere's disk, one direction */
+        float x, y;
+        concentric_sample_disk(lu1, lu2, &x, &y);
+        ray->o = xyz(L.o_type) + x * xyz(L.p1_ns) + y * xyz(L.p2_r2d);
+        ray->d = xyz(L.n_area);
+        ray->tmin = eps;
+        *Ns = ray->d;
+        *pdf = 1.f; /* 1 / (pi R^2), with the area on Le as the disk carries it */
+        return xyz(L.le) * L.n_area.w;
     }
     if (type == PM_LIGHT_AREA_MESH) { /* the disk's emission below from a point of the mesh */
         v3 org = sample_light_mesh(L, tris, lu1, lu2, Ns);

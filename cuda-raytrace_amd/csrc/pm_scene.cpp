@@ -501,6 +501,85 @@ int assemble_scene(const HostScene &hs, std::vector<BuildPrim> &prims, const Bui
     return PM_OK;
 }
 
+/* ---------------------------------------------------------- distant light */
+void coordinate_system(const double v[3], double v1[3], double v2[3]) {
+    if (std::fabs(v[0]) > std::fabs(v[1])) {
+        const double inv = 1.0 / std::sqrt(v[0] * v[0] + v[2] * v[2]);
+        v1[0] = -v[2] * inv; v1[1] = 0.0; v1[2] = v[0] * inv;
+    } else {
+        const double inv = 1.0 / std::sqrt(v[1] * v[1] + v[2] * v[2]);
+        v1[0] = 0.0; v1[1] = v[2] * inv; v1[2] = -v[1] * inv;
+    }
+    v2[0] = v[1] * v1[2] - v[2] * v1[1];
+    v2[1] = v[2] * v1[0] - v[0] * v1[2];
+    v2[2] = v[0] * v1[1] - v[1] * v1[0];
+}
+
+namespace {
+
+bool finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+/* the unit vector of v in double, rounded to float; false for a zero v */
+bool unit3(const float v[3], float out[3]) {
+    const double len = std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]);
+    if (!(len > 0.0) || !std::isfinite(len)) return false;
+    for (int a = 0; a < 3; ++a) out[a] = (float)((double)v[a] / len);
+    return true;
+}
+
+} // namespace
+
+int make_distant_light(const float to_light[3], const float L[3], LightDev &out, std::string &err) {
+    if (!to_light || !L) return fail(err, "pm_add_light_distant: null pointer");
+    if (!finite3(to_light) || !finite3(L)) return fail(err, "pm_add_light_distant: a value is not finite");
+    float w[3];
+    if (!unit3(to_light, w)) return fail(err, "pm_add_light_distant: zero direction");
+    out = LightDev{};
+    out.o_type = f4(0, 0, 0, ibits(PM_LIGHT_DISTANT));
+    out.p1_ns = f4(0, 0, 0, ibits(1));
+    out.p2_r2d = f4(0, 0, 0, 0);
+    out.n_area = f4(-w[0], -w[1], -w[2], 0);
+    out.le = f4(L[0], L[1], L[2], 0);
+    return PM_OK;
+}
+
+void world_sphere(const float blo[3], const float bhi[3], float sphere[4]) {
+    double r2 = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        sphere[a] = (float)(0.5 * ((double)blo[a] + (double)bhi[a]));
+        const double d = std::max(std::fabs((double)bhi[a] - (double)sphere[a]), std::fabs((double)blo[a] - (double)sphere[a]));
+        r2 += d * d;
+    }
+    const double r = std::sqrt(r2);
+    float rf = (float)r;
+    if ((double)rf < r) rf = std::nextafter(rf, INFINITY);
+    sphere[3] = rf;
+}
+
+int finish_lights(HostScene &hs, const float blo[3], const float bhi[3], float sphere[4], std::string &err) {
+    world_sphere(blo, bhi, sphere);
+    const double R = sphere[3];
+    for (size_t l = 0; l < hs.lights.size(); ++l) {
+        LightDev &L = hs.lights[l];
+        if (fbits_h(L.o_type.w) != PM_LIGHT_DISTANT) continue;
+        const double area = M_PI * R * R;
+        if (!(sphere[3] > 0.f) || !std::isfinite(sphere[0]) || !std::isfinite(sphere[1]) || !std::isfinite(sphere[2]) ||
+            !std::isfinite((float)area))
+            return fail(err, "distant light %zu: the world sphere's radius %g is 0 or not finite", l, R);
+        const double w[3] = {-(double)L.n_area.x, -(double)L.n_area.y, -(double)L.n_area.z};
+        double v1[3], v2[3];
+        coordinate_system(w, v1, v2);
+        L.o_type = f4((float)(sphere[0] + R * w[0]), (float)(sphere[1] + R * w[1]), (float)(sphere[2] + R * w[2]),
+                      ibits(PM_LIGHT_DISTANT));
+        L.p1_ns = f4((float)(R * v1[0]), (float)(R * v1[1]), (float)(R * v1[2]), ibits(1));
+        L.p2_r2d = f4((float)(R * v2[0]), (float)(R * v2[1]), (float)(R * v2[2]), 0.f);
+        L.n_area.w = (float)area;
+        L.le.w = 2.f * sphere[3];
+        if (!std::isfinite(L.le.w)) return fail(err, "distant light %zu: the world sphere's radius %g is not finite", l, R);
+    }
+    return PM_OK;
+}
+
 /* --------------------------------------------------------- light summary */
 int light_selection_cdf(const int *types, const float *le_rgb, const float *areas, int n, float *cdf_out, std::string &err) {
     if (!types || !le_rgb || !areas || !cdf_out) return fail(err, "pm_light_selection_cdf: null pointer");
@@ -515,6 +594,7 @@ int light_selection_cdf(const int *types, const float *le_rgb, const float *area
         case PM_LIGHT_POINT: w = y * (4.0 * M_PI); break;
         case PM_LIGHT_AREA_DISK:
         case PM_LIGHT_AREA_MESH: w = y * (M_PI * (double)areas[l]); break;
+        case PM_LIGHT_DISTANT: w = y * (double)areas[l]; break;
         default: return fail(err, "pm_light_selection_cdf: light %d has unknown type %d", l, types[l]);
         }
         if (w < 0.0) w = 0.0;
@@ -530,13 +610,15 @@ int light_selection_cdf(const int *types, const float *le_rgb, const float *area
 
 /* emitted power bound of a light (sample_le's Le / pdf): a point light's
  * 4 pi I; a disk's Le area 2 pi; a mesh's the same with its total area
- * (n_area.w). Negative: a type that has none */
+ * (n_area.w); a distant light's L pi R^2 (a hair above the device's
+ * |d.d| L area: 1.001). Negative: a type that has none */
 static double light_power_bound(const LightDev &L) {
     const double le = std::max({std::fabs(L.le.x), std::fabs(L.le.y), std::fabs(L.le.z)});
     switch (fbits_h(L.o_type.w)) {
     case PM_LIGHT_POINT: return le * 4.0 * M_PI;
     case PM_LIGHT_AREA_DISK:
     case PM_LIGHT_AREA_MESH: return le * L.n_area.w * 2.0 * M_PI;
+    case PM_LIGHT_DISTANT: return le * L.n_area.w * 1.001;
     default: return -1.0;
     }
 }

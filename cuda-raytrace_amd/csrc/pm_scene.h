@@ -149,6 +149,19 @@ int assemble_scene(const HostScene &hs, std::vector<BuildPrim> &prims, const Bui
 /* quantized 4-wide nodes moved to start at node `base`: internal child codes shift */
 void relocate_bvh4(std::vector<uint32_t> &q, uint32_t base);
 
+/* ---------------------------------------------------------- distant light */
+/* pbrt's CoordinateSystem(v, &v1, &v2) for a unit v, in double */
+void coordinate_system(const double v[3], double v1[3], double v2[3]);
+/* the record of pm_add_light_distant (pm_api.h), its parameters checked; it
+ * carries the direction only (n_area.xyz = -to_light) until finish_lights */
+int make_distant_light(const float to_light[3], const float L[3], LightDev &out, std::string &err);
+/* the world sphere (pm_api.h pm_add_light_distant) of scene_boxes' unpadded
+ * bounds: sphere = centre xyz, radius */
+void world_sphere(const float blo[3], const float bhi[3], float sphere[4]);
+/* a commit's last word on the lights, before either builder copies them:
+ * the world sphere, and every distant light's record filled from it */
+int finish_lights(HostScene &hs, const float blo[3], const float bhi[3], float sphere[4], std::string &err);
+
 /* --------------------------------------------------------- light summary */
 /* pm_light_selection_cdf (pm_api.h) */
 int light_selection_cdf(const int *types, const float *le_rgb, const float *areas, int n, float *cdf_out, std::string &err);

@@ -40,6 +40,11 @@ struct LightDev {      /* CudaLightDevice (common.cu.h:47-59), 80 B */
      * hold (int bits) the first entry and the entry count of its triangles
      * in SceneDev::light_tris, o_type.z its reverse_orientation flag;
      * n_area.w is the mesh's total area, the other lanes as above */
+    /* PM_LIGHT_DISTANT (ours): the disk light's lanes for the world sphere's
+     * disk, filled at commit (pm_scene.h finish_lights): o = C + R to_light,
+     * p1 / p2 = R v1, R v2, normal = -to_light (set when the light is added,
+     * the one lane a commit reads), n_area.w = pi R R, le.w = 2 R,
+     * p2_r2d.w = 0, nSample = 1 */
 };
 
 /* one emitting triangle of a mesh light, 64 B (four 16-B loads per lane) */

@@ -13,6 +13,8 @@ PM_ERR_NOMEM = 4
 PM_MATTE, PM_MIRROR, PM_GLASS = 0, 1, 2
 PM_LIGHT_POINT, PM_LIGHT_AREA_DISK = 1, 3
 PM_LIGHT_AREA_MESH = 4  # ours: an emitting triangle mesh (pm_add_light_mesh)
+PM_LIGHT_DISTANT = 6  # ours: pbrt-v2's distant light (pm_add_light_distant); 5 is kept for a spot light
+PM_SCENE_WORLD_SPHERE = 10  # pm_scene_section: centre xyz, radius of the last commit's world sphere
 PM_REC_EXCEPTION, PM_REC_MISS, PM_REC_INVALID, PM_REC_BACKFACE = 0x1, 0x2, 0x4, 0x8
 PM_REC_INACTIVE = PM_REC_EXCEPTION | PM_REC_MISS | PM_REC_INVALID
 PM_GATHER_GRID, PM_GATHER_KDTREE = 0, 1

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .abi import (LIGHT_TRI_DTYPE, PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PM_FILM_TABLE, PM_FILTER_NONE, Camera,
+from .abi import (LIGHT_TRI_DTYPE, PM_SCENE_WORLD_SPHERE, PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PM_FILM_TABLE, PM_FILTER_NONE, Camera,
                   Filter, PMConfig, RenderParams, Stats, f32, fptr, iptr, record_pixels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,6 +54,7 @@ def load_library(path=None):
         "pm_add_light_point": (c_int, [vp, P_f, P_f]),
         "pm_add_light_disk": (c_int, [vp, P_f, P_f, P_f, P_f, P_f, c_float, c_int]),
         "pm_add_light_mesh": (c_int, [vp, P_f, c_int, P_i, c_int, c_int, P_f, c_int, P_i]),
+        "pm_add_light_distant": (c_int, [vp, P_f, P_f, P_i]),
         "pm_set_pinhole": (c_int, [vp, P_f, P_f, P_f, P_f, c_int, c_int]),
         "pm_set_eye_rays": (c_int, [vp, P_f, i64, P_f, c_int]),
         "pm_set_camera": (c_int, [vp, ctypes.POINTER(Camera)]),
@@ -254,6 +255,12 @@ class Context:
         self._chk(self.lib.pm_add_light_mesh(self.h, fptr(P), P.size // 3, iptr(idx), idx.size // 3,
                                              int(bool(reverse_orientation)), fptr(f32(Le, 3)), int(nsamples),
                                              ctypes.byref(out)))
+        return out.value
+
+    def add_light_distant(self, to_light, L):
+        """A distant light (pm_add_light_distant): radiance L from the direction to_light; returns its light index."""
+        out = ctypes.c_int()
+        self._chk(self.lib.pm_add_light_distant(self.h, fptr(f32(to_light, 3)), fptr(f32(L, 3)), ctypes.byref(out)))
         return out.value
 
     def set_pinhole(self, eye, fwd, right, up, W, H):
@@ -498,6 +505,15 @@ class Context:
         out = np.zeros(n.value // np.dtype(dt).itemsize, dtype=dt)
         if n.value:
             self._chk(self.lib.pm_scene_section(self.h, sec, out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
+
+    def world_sphere(self):
+        """The last commit's world sphere (PM_SCENE_WORLD_SPHERE; a host value, not a section of the
+        scene blob): float32 centre x, y, z and radius, as the distant lights use it."""
+        out = np.zeros(4, np.float32)
+        n = ctypes.c_int64()
+        self._chk(self.lib.pm_scene_section(self.h, PM_SCENE_WORLD_SPHERE, out.ctypes.data, out.nbytes, ctypes.byref(n)))
+        assert n.value == out.nbytes
         return out
 
     def map_info(self):

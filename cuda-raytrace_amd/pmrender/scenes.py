@@ -11,6 +11,8 @@ bit-identical inputs.
   triangle-mesh area light (scenes/cornell-box-quad.pbrt).
 * cornell_two_lights: the Cornell box with its disk and a blue quad light on
   the green wall (scenes/cornell-two-lights.pbrt; PM_ALL_LIGHTS).
+* cornell_sun: the Cornell box with its disk light and a distant light
+  through the open front (scenes/cornell-sun.pbrt).
 * triangle_soup: Cornell enclosure + N random triangles, centres
   U[30,525]^3, edges U[-4,4]^3, Kd 0.5 (reference default matte,
   cudamaterial.cpp:40), numpy seed 1 (C3).
@@ -38,6 +40,7 @@ class Scene:
     spheres: list = field(default_factory=list)     # (r, o2w, w2o, material, light)
     disks: list = field(default_factory=list)       # (o, x, y, z, inner, phimax, material, light)
     # ("point", pos, I) | ("disk", o, p1, p2, n, Le, area, ns) | ("mesh", P, idx, Le, ns, reverse_orientation)
+    # | ("distant", to_light, L)
     lights: list = field(default_factory=list)
     objects: list = field(default_factory=list)     # object meshes (as meshes), placed by `instances` only
     instances: list = field(default_factory=list)   # (object index, o2w 4x4, w2o 4x4), affine
@@ -57,6 +60,13 @@ class Scene:
         self.lights.append(("mesh", P, idx, np.asarray(Le, np.float32), int(nsamples), bool(reverse_orientation)))
         self.meshes.append(dict(P=P, idx=idx, N=None, uv=None, material=material, light=light_id))
         return light_id
+
+    def add_distant_light(self, from_, to, L):
+        """pbrt's LightSource "distant" (pm_add_light_distant): light travels from `from_` towards `to`;
+        returns the light index."""
+        w = (np.asarray(from_, np.float32) - np.asarray(to, np.float32)).astype(np.float32)
+        self.lights.append(("distant", w, np.asarray(L, np.float32)))
+        return len(self.lights) - 1
 
     def add_quads(self, quads, material, light=-1):
         P, idx = [], []
@@ -98,6 +108,9 @@ class Scene:
         if any(L[0] == "mesh" for L in self.lights) and not hasattr(api, "add_light_mesh"):
             raise NotImplementedError(f"{type(api).__name__} has no triangle-mesh area lights (pm_add_light_mesh); "
                                       "only disks emit there, as in the reference")
+        if any(L[0] == "distant" for L in self.lights) and not hasattr(api, "add_light_distant"):
+            raise NotImplementedError(f"{type(api).__name__} has no distant lights (pm_add_light_distant); "
+                                      "only point and disk lights exist there, as in the reference")
         for mtype, rgb in self.materials:
             api.add_material(mtype, rgb)
         for m in self.meshes:
@@ -122,6 +135,9 @@ class Scene:
                 api.add_light_point(L[1], L[2])
             elif L[0] == "mesh":
                 got = api.add_light_mesh(L[1], L[2], L[3], L[4], L[5])
+                assert got == i, "light indices follow the order of Scene.lights"
+            elif L[0] == "distant":
+                got = api.add_light_distant(*L[1:])
                 assert got == i, "light indices follow the order of Scene.lights"
             else:
                 api.add_light_disk(*L[1:])
@@ -248,6 +264,14 @@ def cornell_two_lights(W=256, H=256, blocks=True, nsamples=1):
     s = cornell_box(W, H, blocks=blocks, nsamples=nsamples)
     black = s.disks[0][6]  # the ceiling disk's black matte serves the quad
     s.add_mesh_light(WALL_LIGHT, [(0, 1, 2), (0, 2, 3)], WALL_LIGHT_LE, nsamples, material=black)
+    return s
+
+
+def cornell_sun(W=256, H=256, blocks=True, nsamples=1):
+    """The Cornell box with its ceiling disk light and a distant light shining in
+    through the open front, slightly downwards (scenes/cornell-sun.pbrt)."""
+    s = cornell_box(W, H, blocks=blocks, nsamples=nsamples)
+    s.add_distant_light((0.0, 120.0, -400.0), (0.0, 0.0, 0.0), (3.0, 2.7, 2.1))
     return s
 
 

@@ -21,6 +21,7 @@
  *   pm_add_light_point            CudaLight::setupLight<PointLight>        util/light/cudalight.cpp:16-24
  *   pm_add_light_disk             CudaLight::setupLight<DiffuseAreaLight>  util/light/cudalight.cpp:26-59
  *   pm_add_light_mesh             (new: the reference emits from disks only, cudalight.cpp:35-56)
+ *   pm_add_light_distant          (new: pbrt-v2 DistantLight; the reference warns and skips it)
  *   pm_set_eye_rays               PbrtCamera::preLaunch (bRays, bRandom2D) util/camera/pbrtcamera.cpp:57-122
  *   pm_set_pinhole                (on-device eye rays for synthetic benches)
  *   pm_set_camera / pm_film       (new: pbrt-v2 PerspectiveCamera::GenerateRay, StratifiedSampler, ImageFilm)
@@ -60,6 +61,8 @@ extern "C" {
 #define PM_LIGHT_AREA_DISK 3
 /* ours (the reference's enum ends at 3): a triangle mesh that emits, pm_add_light_mesh */
 #define PM_LIGHT_AREA_MESH 4
+/* ours too: pbrt-v2's distant light, pm_add_light_distant (5 is kept for a spot light) */
+#define PM_LIGHT_DISTANT 6
 /* RayTracingRecord flags, photon_mapping/photonmapping.h:25-26 (+ INVALID for padding) */
 #define PM_REC_EXCEPTION 0x01u
 #define PM_REC_MISS 0x02u
@@ -222,6 +225,28 @@ int pm_add_light_disk(void *ctx, const float o[3], const float p1[3], const floa
  * ntris <= 0, an index out of range, a total area of 0 or not finite. */
 int pm_add_light_mesh(void *ctx, const float *P, int nverts, const int *indices, int ntris,
                       int reverse_orientation, const float Le[3], int n_samples, int *out_light);
+/* Distant light (pbrt-v2 DistantLight): radiance L arriving from the direction
+ * to_light (any non-zero length: normalised in double, stored as float). A
+ * delta light: one shadow sample per gather point, no 2-D light sample.
+ * pm_commit computes the world sphere (PM_SCENE_WORLD_SPHERE):
+ * centre C = the midpoint of the exact, unpadded bounds of all world-space
+ * geometry (mesh vertices, instance boxes, disks, spheres), in double, rounded
+ * to float; radius R = the distance from that float centre to the farthest
+ * bound corner in double, rounded up to float. The light's record is then the
+ * disk light's: centre (float)(C + R to_light), radius vectors (float)(R v1),
+ * (float)(R v2) with (v1, v2) = CoordinateSystem(to_light), normal -to_light,
+ * area (float)(pi R R), all evaluated in double.
+ *   emission: the disk light's point for (lu1, lu2), o + x p1 + y p2 with
+ *       (x, y) the concentric-disk map; direction -to_light = Ns; tmin =
+ *       scene_epsilon; Le = L area and pdf = 1, i.e. L over the density
+ *       1 / (pi R R), as the disk light carries its area
+ *   direct light: uwi = -(-to_light (2 R)) (2 R as a stored float), pdf = 1,
+ *       li = L; the shadow segment [0.001, 0.999] uwi leaves the world sphere
+ *       from any point inside it
+ * PM_ERR_INVALID here: a null pointer, a value that is not finite, a zero
+ * direction (checked before the context is); at pm_commit: R = 0 or not
+ * finite (the message names the light). */
+int pm_add_light_distant(void *ctx, const float to_light[3], const float L[3], int *out_light);
 
 /* The largest |component| of an eye-ray origin (2^20). Up to it every
  * traversal mode returns the same hit bit for bit for any finite eye ray
@@ -464,6 +489,9 @@ int pm_scene_info(void *ctx, int64_t out[7]);
  * pm_light_selection_cdf over the scene's lights as pm_commit calls it (all
  * zero when that call fails: the scene emits nothing) */
 #define PM_SCENE_LIGHT_CDF 9
+/* 16 B, host values: the world sphere of the last pm_commit, centre x y z and
+ * radius (float), as pm_add_light_distant states it */
+#define PM_SCENE_WORLD_SPHERE 10
 int pm_scene_section(void *ctx, int section, void *out, int64_t max_bytes, int64_t *bytes);
 /* the current photon map (pm_build_photon_map; the reference's
  * CreatePhotonMap, photonmappingrenderer.cpp:150-180): [0] structure
@@ -510,14 +538,15 @@ int pm_halton_permutation(uint32_t seed, uint32_t out[28]);
  * by the probability of the pick; the reference emits from light 0 only).
  * Light l has type types[l] (PM_LIGHT_*), colour le_rgb[3l .. 3l+2] (a point
  * light's intensity, an area light's emitted radiance Le) and area areas[l]
- * (disk: its area; mesh: its total area; ignored for a point light). All in
- * double, from the float inputs:
+ * (disk: its area; mesh: its total area; ignored for a point light; distant:
+ * the world disk's area pi R R). All in double, from the float inputs:
  *   y(c) = 0.212671 r + 0.715160 g + 0.072169 b     (pbrt's luminance, summed
  *                                                    left to right)
  *   w[l] = y(c) * (4 pi)         point light        (pbrt PointLight::Power)
  *   w[l] = y(c) * (pi * area)    disk or mesh light (DiffuseAreaLight::Power;
  *          also the mean of the path weight |cos| Le area / pdf that the
  *          emission produces with its uniform-hemisphere direction)
+ *   w[l] = y(c) * area           distant light      (DistantLight::Power)
  * with pi = M_PI; a negative w[l] counts as 0. Running sum in double in light
  * order, cdf[l] = (float)(sum[l] / sum[n - 1]), cdf[n - 1] = 1 (the
  * pm_add_light_mesh convention). A path with selection sample u — dimension 5

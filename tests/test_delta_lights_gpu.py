@@ -1,0 +1,516 @@
+"""The distant light on the device (pm_add_light_distant; pm_device.h sample_le,
+sample_l_shading) against the float64 restatement in delta_light_ref.py, at
+the same Halton samples.
+
+Tolerances follow test_mesh_light_gpu.py's method: the point and the disk
+light (both pinned to the oracle bit for bit) are first compared with their
+own float64 restatement on these scenes; the larger of the two deviations per
+quantity is the fp32 floor FLOOR, and the new light gets 8 x that. Alpha and
+direct light are scaled by the light's (image's) largest value.
+"""
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import delta_light_ref as R
+import mesh_light_ref as M
+import multi_light_ref as ML
+from parity_util import assert_bitexact, u32
+from pmrender import scenes
+from pmrender.abi import (PM_ALL_LIGHTS, PM_ESTIMATOR_KNN, PM_GATHER_GRID, PM_GATHER_KDTREE, PM_MATTE, PM_MIRROR,
+                          PM_REC_INACTIVE, RenderParams)
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "cuda-raytrace_amd", "lib", "pm_render_cli")
+SCENES = os.path.join(ROOT, "cuda-raytrace_amd", "scenes")
+HOST = os.path.join(ROOT, "cuda-raytrace_amd", "lib", "pm_pbrt_host")
+
+PATHS, W, H, MPC = 4096, 64, 48, 4
+# The fp32 floor: the larger deviation of the point and of the disk light from
+# their float64 restatement, measured on the MI355X with these scenes and
+# samples (test_noise_floor prints both; rounded up to three digits):
+#   emission origin / scene extent: point 6.33e-9, disk 5.11e-8
+#   direction (recovered through the mirror's fp32 reflection): point 4.62e-7, disk 1.14e-6
+#   alpha / largest alpha: point 1.42e-7, disk 1.08e-7
+#   direct light / largest value: point 2.06e-7, disk 3.45e-7; simple renderer: point 2.06e-7, disk 1.85e-7
+FLOOR = {"position": 5.12e-8, "direction": 1.15e-6, "alpha": 1.42e-7, "dl": 3.46e-7, "simple": 2.06e-7}
+TOL = {k: 8 * v for k, v in FLOOR.items()}
+# measured for the distant light (same units): position 1.04e-7 of the world sphere's diameter, alpha 2.93e-8
+# of L pi R^2, direction exact; direct light = simple renderer 3.81e-8, the same with the slab
+LE = M.LE
+INTENSITY = (9000.0, 6000.0, 3000.0)
+
+
+@functools.lru_cache(maxsize=None)
+def emission_samples():
+    return M.emission_samples(PATHS)
+
+
+def first_deposits(ctx, light=0, begin=0, count=PATHS):
+    p = RenderParams.defaults(paths_per_pass=PATHS, light_source_index=light)
+    ctx.trace_photons(p, 0, begin, count, slot_path_base=begin)
+    return ctx.download_slots(count * MPC)
+
+
+def active_records(ctx):
+    recs = ctx.download_records()
+    act = (recs["flags"] & PM_REC_INACTIVE) == 0
+    return recs, act, ctx.record_pixels()
+
+
+def scaled_dev(got, ref):
+    """largest |got - ref| over the largest reference value"""
+    ref = np.asarray(ref, np.float64)
+    assert ref.max() > 0
+    return float(np.abs(np.asarray(got, np.float64) - ref).max() / ref.max())
+
+
+def through_mirror(first, org_ref, d_ref, a_ref, a_max):
+    """deviations of the first deposits of the paths whose reference ray goes up into the mirror;
+    a_max: the largest alpha the light can emit (the samples need not reach it)"""
+    up = d_ref[:, 2] > 0.05
+    ok = up & ((first["bits"] & 1) == 1)
+    assert ok.sum() == up.sum() > PATHS // 8, (ok.sum(), up.sum())
+    org, d = M.unfold(first[ok])
+    dev_p = float(np.abs(org - org_ref[ok]).max() / M.EXTENT)
+    dev_d = float(np.abs(d - d_ref[ok]).max())
+    dev_a = float(np.abs(first["alpha"][ok].astype(np.float64) - a_ref[ok]).max() / a_max)
+    return dev_p, dev_d, dev_a, ok, d
+
+
+def point_emission_ref(I):
+    smp = emission_samples()
+    d = M.uniform_sphere(smp[:, 0], smp[:, 1], np.array([0.0, 0.0, 0.0]))
+    a = np.broadcast_to(4.0 * np.pi * np.float32(I).astype(np.float64), d.shape)
+    return np.zeros_like(d), d, a
+
+
+def disk_emission_ref(r, area):
+    smp = emission_samples()
+    x, y = M.concentric_disk(smp[:, 0], smp[:, 1])
+    org = np.stack([x * r, y * r, np.zeros_like(x)], 1)
+    d = M.uniform_sphere(smp[:, 2], smp[:, 3], np.array([0.0, 0.0, 1.0]))
+    return org, d, 2.0 * np.pi * area * np.float32(LE).astype(np.float64)[None, :] * np.abs(d[:, 2:3])
+
+
+def point_direct(pos, I, points, ns):
+    uwi = np.asarray(pos, np.float64)[None, :] - points.astype(np.float64)
+    d2 = np.sum(uwi * uwi, 1)
+    w = np.abs(np.sum(ns.astype(np.float64) * uwi, 1)) / np.sqrt(d2) / d2
+    return w[:, None] * (np.float32(R.KD).astype(np.float64) / np.pi)[None, :] * np.float32(I).astype(np.float64)[None, :]
+
+
+def direct_devs(ctx, ref_fn):
+    """(dl, simple renderer) deviations of every active record, scaled by the image's largest value"""
+    ctx.eye_pass(RenderParams.defaults())
+    recs, act, pix = active_records(ctx)
+    assert act.sum() > W * H // 2
+    ref = ref_fn(recs["pos"][act], recs["ns"][act])
+    img, _ = ctx.render_simple(RenderParams.simple_defaults())
+    return scaled_dev(recs["dl"][act], ref), scaled_dev(img.reshape(-1, 3)[pix[act]], ref), recs, act, ref
+
+
+def test_noise_floor(hip_mod):
+    """the point and the disk light against their float64 restatement: the floor FLOOR was read from"""
+    devs = {}
+    ctx = R.mirror_scene(("point", INTENSITY)).load_into(hip_mod.Context(0))
+    try:
+        p, d, a, _, _ = through_mirror(first_deposits(ctx)[0::MPC], *point_emission_ref(INTENSITY), 4.0 * np.pi * max(INTENSITY))
+        devs["point"] = {"position": p, "direction": d, "alpha": a}
+    finally:
+        ctx.close()
+    r = 20.0
+    area = float(np.float32(np.float32(2.0 * np.pi) * np.float32(0.5) * np.float32(r * r)))
+    ctx = M.mirror_scene(("disk", r)).load_into(hip_mod.Context(0))
+    try:
+        p, d, a, _, _ = through_mirror(first_deposits(ctx)[0::MPC], *disk_emission_ref(r, area), 2.0 * np.pi * area * max(LE))
+        devs["disk"] = {"position": p, "direction": d, "alpha": a}
+    finally:
+        ctx.close()
+    ctx = R.floor_scene(("point", INTENSITY)).load_into(hip_mod.Context(0))
+    try:
+        devs["point"]["dl"], devs["point"]["simple"] = direct_devs(ctx, lambda P, N: point_direct((0, 100, 0), INTENSITY, P, N))[:2]
+    finally:
+        ctx.close()
+    ctx = M.floor_scene(("disk", r)).load_into(hip_mod.Context(0))
+    try:
+        ctx.eye_pass(RenderParams.defaults())
+        recs, act, pix = active_records(ctx)
+        o, x, y = np.array([0.0, 100.0, 0.0]), np.array([r, 0, 0]), np.array([0, 0, r])
+        uv = M.philox_uv(range(W * H), 0, 2047)[pix[act]]
+        dx, dy = M.concentric_disk(uv[:, 0], uv[:, 1])
+        pts = o[None, :] + dx[:, None] * x[None, :] + dy[:, None] * y[None, :]
+        nrm = np.broadcast_to(np.array([0.0, -1.0, 0.0]), pts.shape)
+        devs["disk"]["dl"] = scaled_dev(recs["dl"][act], M.direct_light(recs["pos"][act], recs["ns"][act], [pts], [nrm], area, 1))
+        img, _ = ctx.render_simple(RenderParams.simple_defaults())
+        ref = M.direct_light(recs["pos"][act], recs["ns"][act], [pts], [nrm], area, 1, pdf_division=False)
+        devs["disk"]["simple"] = scaled_dev(img.reshape(-1, 3)[pix[act]], ref)
+    finally:
+        ctx.close()
+    print("noise floor:", {k: {q: f"{v:.3g}" for q, v in d.items()} for k, d in devs.items()})
+    for q in FLOOR:
+        assert max(devs["point"][q], devs["disk"][q]) <= FLOOR[q], (q, devs)
+
+
+# ------------------------------------------------------------------ emission
+SUN = (0.6, 0.15, 0.8)          # towards the light: it shines down (-z) and along -x
+SUN_L = (3.0, 2.0, 1.0)
+
+
+def sun_scene():
+    """a mirror in z = 0 and a matte wall at x = -1000: the distant light's rays that
+    land on the mirror leave their first deposit on the wall"""
+    s = scenes.Scene()
+    mir = s.material(PM_MIRROR, (1.0, 1.0, 1.0))
+    grey = s.material(PM_MATTE, (0.5, 0.5, 0.5))
+    # the mirror's edges are 2048 long and each triangle's first edge lies along x: its normalized shading
+    # frame is the coordinate axes exactly, so the reflection changes no bit of the direction
+    s.meshes.append(dict(P=np.float32([(-1024, -1024, 0), (1024, -1024, 0), (1024, 1024, 0), (-1024, 1024, 0)]),
+                         idx=np.int32([(0, 1, 2), (2, 3, 0)]), N=None, uv=None, material=mir, light=-1))
+    s.add_quads([[(-1000, -1500, 0), (-1000, -1500, 3000), (-1000, 1500, 3000), (-1000, 1500, 0)]], grey)
+    s.add_distant_light(SUN, (0.0, 0.0, 0.0), SUN_L)
+    s.camera = scenes.pinhole(W, H, eye=(0.0, 0.0, 200.0), look=(-1000.0, 0.0, 200.0), up=(0.0, 0.0, 1.0))
+    return s
+
+
+def test_distant_emission_and_world_sphere(hip_mod):
+    sc = sun_scene()
+    ctx = sc.load_into(hip_mod.Context(0))
+    try:
+        sph = ctx.world_sphere().astype(np.float64)
+        first = first_deposits(ctx)[0::MPC]
+    finally:
+        ctx.close()
+    V = R.scene_points(sc)
+    c_ref, r_ref = R.world_sphere(V)
+    assert np.all(sph[:3] == c_ref) and 0 <= sph[3] - r_ref <= 1e-5 * r_ref
+    assert np.all(np.linalg.norm(V.astype(np.float64) - sph[None, :3], axis=1) <= sph[3])
+    smp = emission_samples()
+    org_ref, d_ref, a_ref = R.distant_emission(SUN, SUN_L, sph[:3], sph[3], smp[:, 0], smp[:, 1])
+    w = R.unit32(SUN)
+    # the paths whose reference ray lands well inside the mirror and, reflected, well inside the wall
+    t = -org_ref[:, 2] / d_ref[:, 2]
+    land = org_ref + t[:, None] * d_ref
+    rd = d_ref * np.array([1.0, 1.0, -1.0])
+    tw = (-1000.0 - land[:, 0]) / rd[:, 0]
+    wall = land + tw[:, None] * rd
+    on = (np.abs(land[:, 0]) < 900) & (np.abs(land[:, 1]) < 900) & (tw > 0) & (np.abs(wall[:, 1]) < 1400) & (wall[:, 2] < 2900)
+    ok = on & ((first["bits"] & 1) == 1)
+    assert ok.sum() == on.sum() >= 256, (ok.sum(), on.sum())
+    # unfold the mirror in z = 0: the travel direction before it, the point on the light's plane
+    p, r = first["p"][ok].astype(np.float64), -first["wi"][ok]
+    d = r * np.float32([1, 1, -1])
+    assert np.array_equal(d, np.broadcast_to((-w).astype(np.float32), d.shape)), "direction is not -to_light exactly"
+    q = p * np.array([1.0, 1.0, -1.0])
+    tt = ((q - sph[None, :3]) @ w - sph[3]) / (d.astype(np.float64) @ w)
+    org = q - tt[:, None] * d.astype(np.float64)
+    extent = 2.0 * sph[3]
+    dev_p = float(np.abs(org - org_ref[ok]).max() / extent)
+    on_plane = float(np.abs((org_ref[ok] - sph[None, :3]) @ w - sph[3]).max() / extent)
+    a = first["alpha"][ok].astype(np.float64)
+    dev_a = scaled_dev(a, a_ref[ok])
+    print(f"distant: position {dev_p:.3g} alpha {dev_a:.3g} ({ok.sum()} paths), R {sph[3]:.9g} vs {r_ref:.9g}")
+    assert dev_p <= TOL["position"] and on_plane <= TOL["position"] and dev_a <= TOL["alpha"]
+    assert np.all(a == a[0])                                    # one weight for every path: L pi R^2
+
+
+# ------------------------------------------------------------------ direct light
+SLANTED_SUN = ("distant", (0.4, 1.0, -0.3), SUN_L)
+
+
+def test_direct_light_unoccluded(hip_mod):
+    ctx = R.floor_scene(SLANTED_SUN).load_into(hip_mod.Context(0))
+    try:
+        dl, simple, recs, act, ref = direct_devs(ctx, lambda P, N: R.distant_direct(SLANTED_SUN[1], SUN_L, N))
+    finally:
+        ctx.close()
+    print(f"distant: dl {dl:.3g} simple renderer {simple:.3g}")
+    assert dl <= TOL["dl"] and simple <= TOL["simple"], (dl, simple)
+
+
+SLAB = (-20.0, 15.0, -12.0, 25.0)   # at y = 50, behind the camera: its shadow is a block of pixels
+
+
+def test_direct_light_occlusion(hip_mod):
+    light = SLANTED_SUN
+    ctx = R.floor_scene(light, slab=SLAB, wall=True).load_into(hip_mod.Context(0))
+    try:
+        sph = ctx.world_sphere().astype(np.float64)
+        ctx.eye_pass(RenderParams.defaults())
+        recs, act, _ = active_records(ctx)
+    finally:
+        ctx.close()
+    floor = act & (recs["pos"][:, 1] < 1.0)
+    P, N = recs["pos"][floor].astype(np.float64), recs["ns"][floor]
+    end, ref = P + 2.0 * sph[3] * R.unit32(light[1])[None, :], R.distant_direct(light[1], SUN_L, N)
+    hit, near = R.segment_hits_rect(P, end, 50.0, *SLAB, margin=1e-3)
+    assert near.mean() <= 0.02, near.mean()
+    keep = ~near
+    ref = np.where(hit[:, None], 0.0, ref)
+    assert hit[keep].sum() > 20 and (ref[keep].sum(1) > 0).sum() > 20
+    dev = scaled_dev(recs["dl"][floor][keep], ref[keep])
+    print(f"{light[0]} with the slab: dl {dev:.3g}, {int(near.sum())} of {len(near)} records near the silhouette left out")
+    assert dev <= TOL["dl"]
+    assert np.all(recs["dl"][floor][keep & hit] == 0)
+    if True:   # a record just inside the far wall is lit: the 2R segment leaves the scene
+        far = floor & (recs["pos"][:, 0] < -85.0)               # the wall at x = -96, away from the light
+        lit = far.copy()
+        lit[floor] &= ~hit & ~near
+        assert lit.sum() > 0 and np.all(recs["dl"][lit].sum(1) > 0)
+
+
+# ------------------------------------------------------------------ modes
+MODES = {0: "brute", 66: "bvh-lds", 300: "bvh-hbm", "inst": "bvh-instanced"}
+
+
+def test_distant_modes_agree_on_one_world(hip_mod):
+    """the distant light in every traversal mode of one scene: the padding lies inside the bounds the
+    catcher already sets, so the world sphere, and with it every slot and record, is the same"""
+    light = ("distant", (1.0, 0.1, 0.02), SUN_L)    # grazes in between the mirror and the catcher
+    out = {}
+    for pad, mode in MODES.items():
+        s = R.mirror_scene(light, pad)
+        s.add_quads([[(-4000, -4000, -210), (4000, -4000, -210), (4000, 4000, -210), (-4000, 4000, -210)]], 1)
+        ctx = s.load_into(hip_mod.Context(0))
+        try:
+            assert ctx.scene_info()["mode"] == mode
+            sl = first_deposits(ctx)
+            ctx.eye_pass(RenderParams.defaults())
+            out[mode] = (sl, ctx.download_records(), ctx.world_sphere())
+        finally:
+            ctx.close()
+    assert out["brute"][1]["dl"].max() > 0
+    for mode in MODES.values():
+        assert np.array_equal(out[mode][2], out["brute"][2])
+        assert_bitexact(out[mode][0], out["brute"][0], f"slots, {mode} vs brute")
+        assert_bitexact(out[mode][1], out["brute"][1], f"records, {mode} vs brute")
+
+
+# ------------------------------------------------------------------ every light
+def three_light_scene(sun_L=SUN_L):
+    """a floor under a disk, a point and a distant light"""
+    s = M.floor_scene(("disk", 20.0))
+    s.lights.append(("point", np.float32([80.0, 120.0, 30.0]), np.float32(INTENSITY)))
+    s.add_distant_light((0.3, 1.0, 0.2), (0.0, 0.0, 0.0), sun_L)
+    return s
+
+
+def light_arrays(sc, R_world):
+    """(types, le, areas) as pm_commit hands them to pm_light_selection_cdf; the distant light's area is
+    the float of pi R^2 evaluated in double from the float radius"""
+    types, le, areas = [], [], []
+    for L in sc.lights:
+        if L[0] == "disk":
+            types.append(3); le.append(L[5]); areas.append(L[6])
+        elif L[0] == "point":
+            types.append(1); le.append(L[2]); areas.append(0.0)
+        else:
+            types.append(6); le.append(L[2]); areas.append(np.float32(np.pi * float(R_world) ** 2))
+    return types, np.float32(le), np.float32(areas)
+
+
+def fixed_unit(sc, cdf, R_world):
+    """one unit of the PPM gather's fixed point under PM_ALL_LIGHTS (multi_light_ref.ppm_fixed_unit with the
+    distant light's emission bound L pi R^2 x 1.001, pm_scene.cpp light_power_bound)"""
+    types, le, areas = light_arrays(sc, R_world)
+    em = 0.0
+    for t, c, a, p in zip(types, le, areas, ML.pmf_of(cdf)):
+        if p > 0:
+            b = float(np.abs(c).max()) * (4.0 * np.pi if t == 1 else float(a) * 2.0 * np.pi if t == 3 else float(a) * 1.001)
+            em = max(em, b / float(p))
+    kd = max([1.0] + [float(np.max(rgb)) for mtype, rgb in sc.materials if mtype == PM_MATTE])
+    cmax = em * kd ** MPC * (kd / np.pi) * 4.0
+    return 2.0 ** -max(-60, min(60, int(np.floor(np.log2(2.0 ** 40 / cmax)))))
+
+
+def replay(ctx):
+    """the all-lights slots against the per-light traces (test_multi_light_gpu.replay's property): bits, p and
+    wi of path p are those of the light it picked, alpha within multi_light_ref.alpha_bound of alpha_k / pmf;
+    returns the slot buffer composed from the per-light traces, alpha = fl(alpha_k / pmf)"""
+    cdf = ctx.scene_section("light_cdf")
+    pmf = ML.pmf_of(cdf)
+    pick = ML.pick(cdf, ML.u5(np.arange(PATHS, dtype=np.int64), MPC))
+    per = np.stack([first_deposits(ctx, k).reshape(PATHS, MPC) for k in range(len(cdf))])
+    ref = per[pick, np.arange(PATHS)]
+    got = first_deposits(ctx, PM_ALL_LIGHTS).reshape(PATHS, MPC)
+    for f in ("bits", "p", "wi"):
+        assert np.array_equal(u32(got[f].reshape(PATHS, -1)), u32(ref[f].reshape(PATHS, -1))), f
+    assert np.all(pmf[pick] > 0)
+    want = ref["alpha"].astype(np.float64) / pmf[pick].astype(np.float64)[:, None, None]
+    for k in range(MPC):
+        v = (ref["bits"][:, k] & 1) == 1
+        nz = v[:, None] & (want[:, k] > 0)
+        rel = np.abs(got["alpha"][:, k].astype(np.float64)[nz] - want[:, k][nz]) / want[:, k][nz]
+        assert rel.size == 0 or rel.max() <= float(ML.alpha_bound(k + 1))
+    comp = ref.copy()
+    comp["alpha"] = (ref["alpha"] / pmf[pick][:, None, None]).astype(np.float32)
+    return pick, comp.reshape(-1)
+
+
+def test_every_light(hip_mod):
+    sc = three_light_scene()
+    ctx = sc.load_into(hip_mod.Context(0))
+    try:
+        sph = ctx.world_sphere()
+        cdf = ctx.scene_section("light_cdf")
+        host = hip_mod.light_selection_cdf(*light_arrays(sc, sph[3]))
+        assert np.array_equal(cdf.view(np.uint32), host.view(np.uint32)), (cdf, host)
+        pick, _ = replay(ctx)
+        assert len(np.unique(pick)) == 3
+        # a PPM and a kNN render complete with finite, non-negative radiance
+        for kw in (dict(gather_structure=PM_GATHER_KDTREE), dict(gather_structure=PM_GATHER_GRID, estimator=PM_ESTIMATOR_KNN)):
+            img, st = ctx.render(RenderParams.defaults(paths_per_pass=PATHS, light_source_index=PM_ALL_LIGHTS, **kw))
+            assert st["photons_valid"] > 0 and np.all(np.isfinite(img)) and np.all(img >= 0) and img.max() > 0
+    finally:
+        ctx.close()
+
+
+def test_bright_sun_render_equals_composed_photons(hip_mod):
+    """a distant light of radiance 1e4 (alpha = L pi R^2 of the order 1e10) beside a dim disk in the Cornell box
+    does not overflow the fixed point: pm_render(PM_ALL_LIGHTS) equals build + gather over the slot buffer
+    composed on the host from the per-light traces, as test_multi_light_gpu.test_render_equals_composed_photons
+    checks it"""
+    sc = scenes.cornell_sun(W, H)          # an enclosure: the photons' second hits are in view
+    sc.lights[0] = sc.lights[0][:5] + (np.float32([0.01, 0.01, 0.01]),) + sc.lights[0][6:]
+    sc.lights[1] = sc.lights[1][:2] + (np.float32([1e4, 1e4, 1e4]),)
+    ctx = sc.load_into(hip_mod.Context(0))
+    try:
+        _, comp = replay(ctx)
+        p = RenderParams.defaults(paths_per_pass=PATHS, light_source_index=PM_ALL_LIGHTS, initial_radius2=2500.0)
+        img, st = ctx.render(p)
+        got = ctx.download_records()
+        assert st["photons_valid"] == int((comp["bits"] & 1).sum()) > 0
+        ctx.eye_pass(p)
+        ctx.upload_slots(comp)
+        ctx.build_photon_map(p, len(comp))
+        ctx.gather(p)
+        ref = ctx.download_records()
+        unit = fixed_unit(sc, ctx.scene_section("light_cdf"), ctx.world_sphere()[3])
+    finally:
+        ctx.close()
+    act = (ref["flags"] & PM_REC_INACTIVE) == 0
+    assert np.array_equal(got["flags"], ref["flags"]) and act.sum() > W * H // 2
+    assert np.array_equal(got["photon_count"], ref["photon_count"]), "N' differs"
+    assert np.array_equal(u32(got["radius2"]), u32(ref["radius2"])), "r^2 differs"
+    # most of the sun's 4,096 paths land on the outside of the box (the world disk is far wider than the open
+    # front, and the first Halton dimension at index 4 pid covers a quarter of it): about 190 records find photons
+    assert (ref["photon_count"][act] > 0).sum() > 100
+    # the tolerance of test_render_equals_composed_photons: one rounding more than the replay's bound, a few
+    # ulps of the update, one fixed-point unit per photon found
+    u = ML.U24 / (1 - ML.U24)
+    rel = (1.0 + float(ML.alpha_bound(MPC))) * (1.0 + u) ** 5 - 1.0
+    found = ref["photon_count"].astype(np.float64) / 0.7 + 1.0
+    g, r = got["flux"].astype(np.float64), ref["flux"].astype(np.float64)
+    assert np.all(r[act] >= 0) and r[act].max() > 1e6        # the sun's photons are in the sums
+    tol = rel * np.maximum(g, r) + (found * unit)[:, None]
+    dev = np.abs(g - r)
+    print(f"flux: largest deviation {(dev[act] / np.maximum(tol[act], 1e-300)).max():.3g} of its tolerance "
+          f"(relative part {rel:.3g}, unit {unit:.3g}, largest flux {r[act].max():.3g})")
+    assert np.all(dev[act] <= tol[act])
+    assert np.isfinite(img).all() and (img > 0).any()
+
+
+# ------------------------------------------------------------------ end to end, unchanged
+def read_pfm(path):
+    with open(path, "rb") as f:
+        assert f.readline().strip() == b"PF"
+        w, h = (int(v) for v in f.readline().split())
+        scale = float(f.readline())
+        a = np.frombuffer(f.read(), "<f4" if scale < 0 else ">f4").reshape(h, w, 3)
+    return np.ascontiguousarray(a[::-1]).astype(np.float32)
+
+
+def test_scene_file_end_to_end(tmp_path, hip_mod):
+    """cornell-sun.pbrt through the CLI with --light all equals cornell_sun() through the Python driver bit for
+    bit, photon-mapped and direct-only; the sun's share of the direct-only image is the reference's"""
+    paths = 16384
+    imgs = {}
+    for name, extra in (("pm", ["--paths", str(paths)]), ("simple", ["--renderer", "simple"])):
+        out = tmp_path / (name + ".pfm")
+        r = subprocess.run([CLI, "--pbrt", os.path.join(SCENES, "cornell-sun.pbrt"), "--light", "all", "--out", str(out)] + extra,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        imgs[name] = read_pfm(out)
+    ctx = scenes.cornell_sun(256, 256).load_into(hip_mod.Context(0))
+    try:
+        p = RenderParams.defaults(paths_per_pass=paths, gather_structure=PM_GATHER_GRID, light_source_index=PM_ALL_LIGHTS)
+        ref, st = ctx.render(p)
+        assert st["photons_valid"] > 0 and np.isfinite(ref).all() and np.all(ref >= 0)
+        assert np.array_equal(imgs["pm"].view(np.uint32), ref.view(np.uint32)), ".pbrt image differs from cornell_sun()"
+        simple = ctx.render_simple(RenderParams.simple_defaults())[0]
+        assert np.array_equal(imgs["simple"].view(np.uint32), simple.view(np.uint32))
+        recs, act, pix = active_records(ctx)
+    finally:
+        ctx.close()
+    ctx = scenes.cornell_box(256, 256).load_into(hip_mod.Context(0))
+    try:
+        box = ctx.render_simple(RenderParams.simple_defaults())[0]
+    finally:
+        ctx.close()
+    # the sun's direct light on the floor = the image with the sun minus the image without it: where the float64
+    # shadow segment (towards the light, 2 R long) stays inside the open front below the ceiling's front edge,
+    # it is Kd / pi L |n . w|; each image carries half an ulp of its own value
+    w = R.unit32((0.0, 120.0, -400.0))
+    floor = act & (recs["pos"][:, 1] < 0.5) & (recs["ns"][:, 1] > 0.99)
+    P = recs["pos"][floor].astype(np.float64)
+    t = (0.0 - P[:, 2]) / w[2]                                        # where the segment crosses the front plane z = 0
+    front = P + t[:, None] * w[None, :]
+    clear = (front[:, 1] < 540.0) & (front[:, 0] > 10.0) & (front[:, 0] < 540.0)
+    # the blocks stand between some floor points and the front: keep the points in front of both blocks (z < 60)
+    clear &= P[:, 2] < 60.0
+    assert clear.sum() > 200
+    kd = np.float64(np.float32(scenes.WHITE))
+    want = (kd / np.pi) * np.float64(np.float32([3.0, 2.7, 2.1])) * abs(w[1])
+    sun = simple.reshape(-1, 3).astype(np.float64)[pix[floor]][clear] - box.reshape(-1, 3).astype(np.float64)[pix[floor]][clear]
+    big = float(simple.reshape(-1, 3)[pix[floor]][clear].max())
+    dev = np.abs(sun - want[None, :]).max() / want.max()
+    print(f"sun on the floor: deviation {dev:.3g} of its value (image values up to {big:.3g})")
+    assert dev <= TOL["simple"] + 2.0 ** -23 * big / want.max()
+
+
+def test_distant_light_through_pbrt_boundary(tmp_path, hip_mod):
+    """pm_pbrt_host --sun: a DistantLight through cudaapi.cpp equals the stage driver on the host's rays and
+    light randoms (pbrt normalizes lightDir in float; the stage driver is handed that vector)"""
+    from test_pbrt_boundary import read_host_output
+    out = tmp_path / "host.bin"
+    r = subprocess.run([HOST, "--width", str(W), "--height", str(H), "--paths", "16384", "--sun", "--lightsource", "-1",
+                        "--out", str(out)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rays, rand2d, n2d, written, img = read_host_output(out, W, H)
+    assert written == 1 and n2d == 1
+    sc = scenes.cornell_sun(W, H)
+    d = np.float32([0.0, 120.0, -400.0])
+    inv = np.float32(1.0) / np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2], dtype=np.float32)    # pbrt Normalize
+    sc.lights[1] = ("distant", (d * inv).astype(np.float32), sc.lights[1][2])
+    sc.camera = ("rays", rays.copy(), rand2d.copy(), n2d)
+    ctx = sc.load_into(hip_mod.Context(0))
+    try:
+        ref, _ = ctx.render(RenderParams.defaults(paths_per_pass=16384, light_source_index=PM_ALL_LIGHTS))
+    finally:
+        ctx.close()
+    assert (ref > 0).any()
+    assert np.array_equal(img.view(np.uint32), ref.reshape(-1, 3).view(np.uint32))
+    # and the sun is in it: the host's image without --sun differs
+    r = subprocess.run([HOST, "--width", str(W), "--height", str(H), "--paths", "16384", "--out", str(out)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert not np.array_equal(read_host_output(out, W, H)[4], img)
+
+
+def test_old_lights_unchanged(hip_mod, oracle_mod):
+    """the Cornell box with its disk light and a point-light scene: the same bits as the oracle"""
+    for sc in (scenes.cornell_box(W, H), R.floor_scene(("point", INTENSITY), slab=SLAB)):
+        ctx, orc = sc.load_into(hip_mod.Context(0)), sc.load_into(oracle_mod.Oracle())
+        try:
+            p = RenderParams.defaults(paths_per_pass=PATHS)
+            ctx.trace_photons(p, 0, 0, PATHS)
+            assert_bitexact(ctx.download_slots(PATHS * MPC), orc.trace_photons(p), "photon slots")
+            ctx.eye_pass(p)
+            assert_bitexact(ctx.download_records(), orc.eye_pass(p), "records")
+        finally:
+            ctx.close()
