@@ -1,8 +1,8 @@
 /*
  * pm_api.cpp — the C-ABI of libpmhip.so (declared in include/pm_api.h):
  * context, scene calls, commit (the device BVH build, or the host assembly
- * of pm_scene.cpp, and the upload), stage orchestration and the whole-render
- * entry point. Host code only; the kernels live in the .hip files
+ * of pm_scene.cpp, and the upload), stage orchestration (the grid each pass
+ * gets is planned by pm_plan.cpp) and the whole-render entry point. Host code only; the kernels live in the .hip files
  * (launchers in pm_kernels.h). No CPU fallback: every compute entry point
  * launches HIP kernels and fails with PM_ERR_HIP when the device is unusable.
  */
@@ -23,6 +23,7 @@
 
 #include "pm_build.h"
 #include "pm_kernels.h"
+#include "pm_plan.h"
 #include "pm_scene.h"
 
 #pragma clang fp contract(off)
@@ -53,6 +54,63 @@ struct DevBuf {
     bool external = false; /* caller-owned memory: never freed or grown here */
     void release() { if (p && !external) (void)hipFree(p); p = nullptr; bytes = 0; external = false; }
     template <class T> T *as() const { return (T *)p; }
+};
+
+/* The tiles (64 records) that hold an active record, in record order:
+ * full-range tile gathers launch over these only (records are fixed after
+ * the eye pass). Built on the device without a host wait: flags + an
+ * in-order compaction, its length copied to pinned memory behind an event.
+ * Until that copy has landed (hipEventQuery, never waited on) the gather
+ * kernels read the length from device memory and the grid covers every
+ * tile. The list is reordered once by the measured cost of its tiles (the
+ * first full-range tile gather on it records them, launch_tile_sort). */
+struct TileList {
+    DevBuf d_list, d_flags, d_count, d_cost, d_sorted;
+    bool sort = true;         /* env PM_TILE_SORT=0 keeps record order */
+    bool valid = false;       /* the list on the device matches the records */
+    bool sorted = false;
+    bool count_known = false; /* its length has landed in n */
+    int64_t n = 0;
+    uint32_t *h_count = nullptr;
+    hipEvent_t event = nullptr;
+
+    void invalidate() { valid = false; }
+    hipError_t ensure(const RecordsDev &R, hipStream_t s) {
+        hipError_t e = hipSuccess;
+        auto ok = [&e](hipError_t r) { return (e = r) == hipSuccess; };
+        if (!valid) {
+            const int64_t nt = (R.count + 63) / 64;
+            if (!ok(d_flags.ensure(std::max<int64_t>(nt, 16))) || !ok(d_list.ensure(std::max<int64_t>(nt * 4, 16))) ||
+                !ok(d_count.ensure(16)))
+                return e;
+            if (!h_count && !ok(hipHostMalloc((void **)&h_count, 4, hipHostMallocDefault))) return e;
+            if (!event) {
+                if (!ok(hipEventCreateWithFlags(&event, hipEventDisableTiming))) return e;
+            } else if (!count_known && !ok(hipEventSynchronize(event))) {
+                /* a previous list's length still in flight (records replaced before
+                 * any gather read it): that copy lands before the pinned word is reused */
+                return e;
+            }
+            if (!ok(launch_tile_list(R, d_flags.as<uint8_t>(), d_list.as<uint32_t>(), d_count.as<uint32_t>(), s)) ||
+                !ok(hipMemcpyAsync(h_count, d_count.p, 4, hipMemcpyDeviceToHost, s)) || !ok(hipEventRecord(event, s)))
+                return e;
+            valid = true;
+            sorted = false;
+            count_known = false;
+        }
+        if (!count_known && hipEventQuery(event) == hipSuccess) {
+            n = (int64_t)*h_count;
+            count_known = true;
+        }
+        return hipSuccess;
+    }
+    /* launch_tile_sort wrote the reordered list into d_sorted */
+    void swap_sorted() { std::swap(d_list, d_sorted); sorted = true; }
+    void release() {
+        for (DevBuf *b : {&d_list, &d_flags, &d_count, &d_cost, &d_sorted}) b->release();
+        if (event) (void)hipEventDestroy(event);
+        if (h_count) (void)hipHostFree(h_count);
+    }
 };
 
 struct Timer { hipEvent_t a = nullptr, b = nullptr; };
@@ -136,19 +194,7 @@ struct Ctx {
     bool view_active = false;
     int64_t n_view = 0;
     DevBuf d_vflags, d_vrank, d_vlist, d_vsums;
-    /* tiles (64 records) holding an active record, in record order: full-range
-     * tile gathers launch over these only (records fixed after the eye pass) */
-    DevBuf d_tiles, d_tile_flags, d_tile_count;
-    int64_t n_tiles = 0;           /* valid once tile_count_known */
-    bool tiles_valid = false;      /* the list on the device matches the records */
-    /* the list is reordered once by the measured cost of its tiles (the first
-     * full-range tile gather on it records them; launch_tile_sort); env
-     * PM_TILE_SORT=0 keeps record order */
-    DevBuf d_tile_cost, d_tiles2;
-    bool tile_sort = true, tiles_sorted = false;
-    bool tile_count_known = false; /* its length read back (pinned copy + event, never waited on) */
-    uint32_t *h_tile_count = nullptr;
-    hipEvent_t tile_event = nullptr;
+    TileList tiles;
     /* pm_reset_records is deferred: records read as (flux 0, N 0, r2 = rec_fresh_r2) */
     bool rec_fresh = false;
     float rec_fresh_r2 = 0.f;
@@ -162,27 +208,14 @@ struct Ctx {
     DevBuf d_spill;                 /* pooled kernel: stack entries beyond pool_stack */
     int gather_kernel = PM_GK_TILE; /* bucket gather kernel (env PM_GATHER_KERNEL=tile|lane) */
     int cell_span = 2;              /* PPM grid: cells per axis of a query box (env PM_CELL_SPAN 2..5) */
-    /* adaptive grid radius (progressive PPM: radii shrink pass by pass). The
-     * fused tile gather bins every updated r^2 (R2_BINS log bins per copy,
-     * 8 copies) into d_r2hist; the histogram is copied to pinned memory
-     * behind r2_event and, once landed, sets the next passes' grid radius to
-     * the grid_quantile of the records' radii (the rest scan per lane).
-     * Staleness is safe (radii only shrink); anything that can raise a
-     * radius (eye pass, reset, upload, set_radius2, split / partial updates)
-     * invalidates it. env PM_GRID_QUANTILE (default 0.9; <= 0 disables). */
-    DevBuf d_r2hist;
-    uint32_t *h_r2hist = nullptr, *h_r2hist_dev = nullptr; /* host-mapped R2_BINS words, its device address */
-    hipEvent_t r2_event = nullptr;
-    hipStream_t r2_stream = nullptr; /* the stream the last histogram reduce ran on (r2_event) */
-    bool r2_wanted = false;    /* a progressive pass asked for the radii (no histogram otherwise) */
-    bool r2_accum = false;     /* d_r2hist holds bins of this pass's gathers (every band), not yet reduced */
-    bool r2_dirty = false;     /* d_r2hist holds bins of invalidated radii: zero before binning again */
-    float r2_accum_init = 0.f; /* the r^2 the accumulated bins are relative to */
-    bool r2_pending = false;   /* a histogram copy in flight */
-    bool r2_valid = false;     /* the last landed / in-flight histogram describes the records */
-    float r2_hist_init = 0.f;  /* the r^2 its bins are relative to */
-    float design_r2 = 0.f;     /* grid radius^2 of the current photon map (0: initial_radius2) */
-    double grid_quantile = 0.9; /* C5 step (same box, 3 runs each): 0.95 0.82-0.85 ms, 0.9 0.784-0.790, 0.8 0.826 */
+    /* adaptive grid radius: the state machine (pm_plan.h R2Plan) and the HIP
+     * objects it speaks of — the device bins (R2_COPIES x R2_BINS), the
+     * host-mapped R2_BINS words a reduce writes (and their device address),
+     * the event behind the reduce */
+    R2Plan grid_plan;
+    DevBuf d_hist;
+    uint32_t *h_hist = nullptr, *h_hist_dev = nullptr;
+    hipEvent_t hist_event = nullptr;
     /* leading words of d_count known to be zero (the bucket scan clears the
      * counters it reads); valid while d_count.p == count_zero_ptr */
     size_t count_zero_words = 0;
@@ -343,15 +376,6 @@ void halton_perm(uint32_t seed, uint32_t out[28]) {
     }
 }
 
-/* the records' radii changed in a way that may raise them (eye pass, reset,
- * upload, set_radius2, kNN radii): the adaptive grid falls back to the
- * initial radius, and bins accumulated from the old radii are dropped */
-static void r2_invalidate(Ctx *c) {
-    c->r2_valid = false;
-    c->design_r2 = 0.f;
-    if (c->r2_accum) { c->r2_accum = false; c->r2_dirty = true; }
-}
-
 /* the deferred zero fill of a lazy_zero trace, on stream s after the trace
  * (s == nullptr: on the trace's own stream, waited for) */
 static int materialize_slots(Ctx *c, hipStream_t s) {
@@ -387,8 +411,8 @@ int ensure_records(Ctx *c) {
     HIPCHK(c, c->d_n.ensure(n * sizeof(float)));
     HIPCHK(c, c->d_dl.ensure(n * sizeof(float4)));
     c->nrec = n;
-    c->tiles_valid = false;
-    r2_invalidate(c);
+    c->tiles.invalidate();
+    c->grid_plan.invalidate();
     return PM_OK;
 }
 
@@ -444,6 +468,17 @@ GatherParams gather_params(Ctx *c, const pm_render_params *p) {
     G.fx_scale = (float)std::ldexp(1.0, S);
     G.fx_inv = std::ldexp(1.0, -S);
     return G;
+}
+
+/* the final pass over records [begin, begin + count) into out, one radiance
+ * per record in record order (callers set raster / view for another layout) */
+FinalParams final_params(Ctx *c, double emitted, int64_t begin, int64_t count, float *out) {
+    FinalParams F{};
+    F.R = recs(c);
+    F.knn = c->rec_estimator == PM_ESTIMATOR_KNN; F.materials = c->S.materials;
+    F.emitted = (float)emitted; /* gContext["emittingPhotons"]->setFloat((float)totalPhotons) */
+    F.rec_begin = begin; F.rec_count = count; F.out = out; F.raster = 0; F.W = c->W;
+    return F;
 }
 
 /* (re)builds the active-record view from the current records; synchronizes to read its size */
@@ -698,9 +733,9 @@ int pm_create(void **out, const pm_config *cfg) {
         c->gather_kernel = !strcmp(e, "lane") ? PM_GK_LANE : PM_GK_TILE;
     if (const char *e = getenv("PM_KNN_SS")) c->knn_ss = atoi(e) != 0;
     if (const char *e = getenv("PM_CELL_SPAN")) c->cell_span = std::max(2, std::min(5, atoi(e)));
-    if (const char *e = getenv("PM_TILE_SORT")) c->tile_sort = atoi(e) != 0;
+    if (const char *e = getenv("PM_TILE_SORT")) c->tiles.sort = atoi(e) != 0;
     if (const char *e = getenv("PM_LAZY_ZERO")) c->lazy_zero = atoi(e) != 0;
-    if (const char *e = getenv("PM_GRID_QUANTILE")) c->grid_quantile = atof(e);
+    if (const char *e = getenv("PM_GRID_QUANTILE")) c->grid_plan.quantile = atof(e);
     if (const char *e = getenv("PM_TRACE_HOLD")) c->trace_hold = atoi(e) != 0;
     if (const char *e = getenv("PM_TRACE_POOL")) c->trace_pool = atoi(e) != 0;
     if (const char *e = getenv("PM_POOL_STACK")) c->pool_stack = std::max(0, atoi(e));
@@ -741,15 +776,13 @@ void pm_destroy(void *ptr) {
         }
     DevBuf *bufs[] = {&c->d_scene, &c->d_rays, &c->d_rand2d, &c->d_pos, &c->d_nrm, &c->d_state, &c->d_n,
                       &c->d_dl, &c->d_slots, &c->d_count, &c->d_scratch, &c->d_vflags, &c->d_vrank, &c->d_vlist, &c->d_vsums,
-                      &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times, &c->d_tile_cost, &c->d_tiles2,
-                      &c->d_kd, &c->d_out, &c->d_counters, &c->d_tiles, &c->d_tile_flags, &c->d_tile_count,
-                      &c->d_r2hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf, &c->d_film_table, &c->d_img};
+                      &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times,
+                      &c->d_kd, &c->d_out, &c->d_counters, &c->d_hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf, &c->d_film_table, &c->d_img};
     for (DevBuf *b : bufs) b->release();
-    if (c->tile_event) (void)hipEventDestroy(c->tile_event);
-    if (c->r2_event) (void)hipEventDestroy(c->r2_event);
+    c->tiles.release();
+    if (c->hist_event) (void)hipEventDestroy(c->hist_event);
     if (c->dirty_event) (void)hipEventDestroy(c->dirty_event);
-    if (c->h_r2hist) (void)hipHostFree(c->h_r2hist);
-    if (c->h_tile_count) (void)hipHostFree(c->h_tile_count);
+    if (c->h_hist) (void)hipHostFree(c->h_hist);
     (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1270,8 +1303,8 @@ int pm_eye_pass(void *ptr, const pm_render_params *p, void *stream) {
     HIPCHK(c, launch_eye(E, s));
     timer_end(c, "eye", s);
     c->rec_fresh = false; /* the eye pass writes every record */
-    c->tiles_valid = false;
-    r2_invalidate(c);
+    c->tiles.invalidate();
+    c->grid_plan.invalidate();
     if (c->view_active && (rc = build_view(c, s))) return rc;
     return PM_OK;
 }
@@ -1320,83 +1353,31 @@ int pm_set_slot_buffer(void *ptr, void *d, int64_t n) {
     return PM_OK;
 }
 
-/* photon-bucket grid of a render: cell edge 2 r_max / (span - 1) over the
- * scene box, so a query box [p - r', p + r'] spans <= span cells per axis
- * (PPM radii only shrink, so it holds for every pass of the render) */
-/* radius^2 the PPM grid is designed for: the grid_quantile of the records'
- * current radii from the last landed histogram (k_gather_tile), else the
- * initial radius. Refreshed only where a photon map's grid is chosen
- * (pm_trace_photons with fused counting, or pm_build_photon_map without), so
- * the trace and the build of one pass agree. */
-static float grid_radius2(Ctx *c, const pm_render_params *p, bool refresh, hipStream_t s) {
+/* radius^2 the grid of a new pass is designed for (pm_plan.h R2Plan): asked
+ * only where a photon map's grid is chosen (pm_trace_photons with fused
+ * counting, or pm_build_photon_map without), so the trace and the build of
+ * one pass agree. A landed histogram sets it; the bins of the previous
+ * pass's gathers are reduced on s into host-mapped memory by a one-block
+ * kernel (no copy-engine transfer in the stream: a per-pass D2H copy cost
+ * ~0.5 ms of C2 step). */
+static float grid_radius2(Ctx *c, const pm_render_params *p, hipStream_t s) {
+    R2Plan &r = c->grid_plan;
     const float init = p->initial_radius2;
-    if (p->estimator == PM_ESTIMATOR_KNN || c->grid_quantile <= 0.0) return init;
-    if (refresh) {
-        /* a new pass. First a landed sum sets the grid radius (if it still
-         * describes the records) ... */
-        if (c->r2_pending && hipEventQuery(c->r2_event) == hipSuccess) {
-            c->r2_pending = false;
-            if (c->r2_valid && c->r2_hist_init == init) {
-                uint64_t cnt[R2_BINS] = {0}, total = 0;
-                for (int b = 0; b < R2_BINS; ++b) cnt[b] = ((volatile uint32_t *)c->h_r2hist)[b];
-                for (int b = 0; b < R2_BINS; ++b) total += cnt[b];
-                /* bins b.. hold t = r^2 / init <= 2^(-b/8): the largest b that still
-                 * covers the quantile */
-                int best = 0;
-                uint64_t above = total;
-                for (int b = 0; b < R2_BINS; ++b) {
-                    if ((double)above < c->grid_quantile * (double)total) break;
-                    best = b;
-                    above -= cnt[b];
-                }
-                /* the bins come from an approximate log2: a small margin */
-                c->design_r2 = total ? std::min(init, (float)(init * std::exp2(-best / (double)R2_PER_OCTAVE) * 1.01)) : 0.f;
-            }
-        }
-        /* ... then the previous pass's gathers — all of its record ranges (a
-         * group device's or an all-gather rank's bands) — binned their radii
-         * into d_r2hist: sum them once, into host-mapped memory (not while a
-         * sum is in flight: the pinned buffer is reused; the bins keep
-         * accumulating, and older radii only overestimate) */
-        if (c->r2_accum && !c->r2_pending &&
-            launch_r2hist_reduce(c->d_r2hist.as<uint32_t>(), c->h_r2hist_dev, s) == hipSuccess &&
-            hipEventRecord(c->r2_event, s) == hipSuccess) {
-            c->r2_pending = true;
-            c->r2_stream = s;
-            c->r2_accum = false;
-            c->r2_valid = true;
-            c->r2_hist_init = c->r2_accum_init;
-        }
-        /* a pass that continues a render (no reset pending): its gathers bin
-         * their radii for the passes after it */
-        c->r2_wanted = !c->rec_fresh;
+    if (!r.active(p->estimator)) return init;
+    if (r.pending && hipEventQuery(c->hist_event) == hipSuccess) {
+        uint32_t hist[R2_BINS];
+        for (int b = 0; b < R2_BINS; ++b) hist[b] = ((volatile uint32_t *)c->h_hist)[b];
+        r.landed(hist, init);
     }
-    if (c->rec_fresh || !c->r2_valid || c->r2_hist_init != init) return init;
-    return c->design_r2 > 0.f ? c->design_r2 : init;
+    if (r.reduce_due() && launch_r2hist_reduce(c->d_hist.as<uint32_t>(), c->h_hist_dev, s) == hipSuccess &&
+        hipEventRecord(c->hist_event, s) == hipSuccess)
+        r.reduce_issued(s);
+    r.pass_began(c->rec_fresh);
+    return r.radius2(init, c->rec_fresh);
 }
 
 static GridDesc make_grid(const Ctx *c, const pm_render_params *p, float radius2) {
-    GridDesc g{};
-    const float rq = sqrtf(radius2) * 1.0001f + 1e-4f;
-    /* PPM: span 2 by default (cell edge >= 2 r_max: at most 2x2x2 cells;
-     * env PM_CELL_SPAN 3..5 for finer cells, DESIGN.md §5 sweep). kNN:
-     * r_max / 2 — the query visits rows nearest first and prunes cells
-     * beyond the shrinking k-th distance (k_gather_knn) */
-    const float f = p->estimator == PM_ESTIMATOR_KNN ? 0.5f : 2.0f / (float)(c->cell_span - 1);
-    float cs = f * rq * 1.001f;
-    float ext[3];
-    for (int a = 0; a < 3; ++a) ext[a] = std::max(c->bbox_hi[a] - c->bbox_lo[a], 1e-3f);
-    int64_t dims[3];
-    while (true) {
-        for (int a = 0; a < 3; ++a) dims[a] = std::max<int64_t>(1, (int64_t)std::ceil(ext[a] / cs) + 1);
-        if (dims[0] * dims[1] * dims[2] <= (int64_t)1 << 25) break;
-        cs *= 1.25f;
-    }
-    g.gx = c->bbox_lo[0]; g.gy = c->bbox_lo[1]; g.gz = c->bbox_lo[2];
-    g.inv_cs = 1.0f / cs;
-    g.dx = (int)dims[0]; g.dy = (int)dims[1]; g.dz = (int)dims[2];
-    g.ncells = (uint32_t)(dims[0] * dims[1] * dims[2]);
-    return g;
+    return pm::make_grid(c->bbox_lo, c->bbox_hi, p->estimator, c->cell_span, radius2);
 }
 
 static bool same_grid(const GridDesc &a, const GridDesc &b) { return std::memcmp(&a, &b, sizeof(GridDesc)) == 0; }
@@ -1487,7 +1468,7 @@ int pm_trace_photons(void *ptr, const pm_render_params *p, int pass, int64_t pat
      * build then skips it (c->fused). Any other slot producer invalidates it. */
     c->fused.valid = false;
     if (fuse) {
-        c->fused.r2 = grid_radius2(c, p, true, s);
+        c->fused.r2 = grid_radius2(c, p, s);
         const GridDesc g = make_grid(c, p, c->fused.r2);
         HIPCHK(c, c->d_count.ensure_slack(((size_t)g.ncells + 1) * 4));
         HIPCHK(c, c->d_scratch.ensure_slack(bucket_scratch_words(end_slot, g.ncells) * 4));
@@ -1553,7 +1534,7 @@ int pm_build_photon_map(void *ptr, const pm_render_params *p, int64_t n_slots, v
     GridDesc &g = c->grid;
     /* the grid of the trace's fused counts, if they cover these slots */
     const bool fused_ok = c->fused.valid && c->fused.n == n_slots;
-    c->grid_r2 = fused_ok ? c->fused.r2 : grid_radius2(c, p, true, s);
+    c->grid_r2 = fused_ok ? c->fused.r2 : grid_radius2(c, p, s);
     g = make_grid(c, p, c->grid_r2);
     const bool counted = fused_ok && same_grid(c->fused.grid, g);
     /* the counting pass below reads every slot's valid bit (and overwrites the keys) */
@@ -1580,207 +1561,165 @@ int pm_build_photon_map(void *ptr, const pm_render_params *p, int64_t n_slots, v
 }
 
 
-/* the tile list of the current records, built on the device without a host
- * wait: flags + an in-order compaction, its length copied to pinned memory
- * behind an event. Until that copy has landed (hipEventQuery, never waited
- * on) the gather kernels read the length from device memory and the grid
- * covers every tile. */
-static int ensure_tiles(Ctx *c, hipStream_t s) {
-    if (!c->tiles_valid) {
-        const int64_t nt = (c->nrec + 63) / 64;
-        HIPCHK(c, c->d_tile_flags.ensure(std::max<int64_t>(nt, 16)));
-        HIPCHK(c, c->d_tiles.ensure(std::max<int64_t>(nt * 4, 16)));
-        HIPCHK(c, c->d_tile_count.ensure(16));
-        if (!c->h_tile_count) HIPCHK(c, hipHostMalloc((void **)&c->h_tile_count, 4, hipHostMallocDefault));
-        if (!c->tile_event) HIPCHK(c, hipEventCreateWithFlags(&c->tile_event, hipEventDisableTiming));
-        /* a previous list's length still in flight (records replaced before
-         * any gather read it): let that copy land before the pinned word is reused */
-        else if (!c->tile_count_known) HIPCHK(c, hipEventSynchronize(c->tile_event));
-        HIPCHK(c, launch_tile_list(recs(c), c->d_tile_flags.as<uint8_t>(), c->d_tiles.as<uint32_t>(),
-                                   c->d_tile_count.as<uint32_t>(), s));
-        HIPCHK(c, hipMemcpyAsync(c->h_tile_count, c->d_tile_count.p, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipEventRecord(c->tile_event, s));
-        c->tiles_valid = true;
-        c->tiles_sorted = false;
-        c->tile_count_known = false;
-    }
-    if (!c->tile_count_known && hipEventQuery(c->tile_event) == hipSuccess) {
-        c->n_tiles = (int64_t)*c->h_tile_count;
-        c->tile_count_known = true;
-    }
-    return PM_OK;
-}
-
-static int gather_common(Ctx *c, const pm_render_params *p, long long *partial, int64_t rec_begin, int64_t rec_count,
-                         void *stream, int *count = nullptr, long long *flux = nullptr) {
+/* ---- the steps of a gather (gather_common), in order ---------------------- */
+static int gather_validate(Ctx *c, const pm_render_params *p, bool partials, int64_t rec_begin, int64_t rec_count) {
     int rc;
     if ((rc = check_params(c, p))) return rc;
     if (c->nrec <= 0) FAIL(c, PM_ERR_INVALID, "no records (run pm_eye_pass first)");
     if (c->map_kind != p->gather_structure) FAIL(c, PM_ERR_INVALID, "photon map not built for this gather structure");
-    if (p->estimator == PM_ESTIMATOR_KNN && (partial || count))
+    if (p->estimator == PM_ESTIMATOR_KNN && partials)
         FAIL(c, PM_ERR_INVALID, "the kNN estimator is not linear in the photon set: no partial / split gathers "
                                 "(multi-GPU: all-gather the photons, then pm_gather_range)");
     if (rec_begin < 0 || rec_count < 0 || rec_begin + rec_count > c->nrec) FAIL(c, PM_ERR_INVALID, "bad record range");
-    hipStream_t s = pick(c, stream);
-    GatherParams G = gather_params(c, p);
-    G.partial = partial;
-    G.count = count;
-    G.flux = flux;
-    G.rec_begin = rec_begin;
-    G.rec_end = rec_begin + rec_count;
-    /* a pending reset is consumed by a fused gather over all records (it starts
-     * from the initial PPM state and writes it); a split partial gather reads
-     * the initial radius and leaves the reset to pm_ppm_update_split, which
-     * writes every view record; any other gather needs it applied */
-    const bool split = count != nullptr;
-    const bool consume = c->rec_fresh && !partial && !split && rec_begin == 0 && rec_count == c->nrec;
-    if (consume || (split && c->rec_fresh)) { G.fresh = 1; G.r2init = c->rec_fresh_r2; }
-    else if ((rc = materialize_reset(c, s))) return rc;
-    /* full-range tile gathers skip the tiles without an active record (their
-     * records are neither read nor written, except as partials outside a view) */
-    if (c->gather_kernel == PM_GK_TILE && !c->counting && rec_begin == 0 && rec_count == c->nrec &&
-        p->gather_structure == PM_GATHER_GRID && ((!partial && !split) || c->view_active)) {
-        if ((rc = ensure_tiles(c, s))) return rc;
-        G.tiles = c->d_tiles.as<uint32_t>();
-        if (c->tile_count_known) { G.n_tiles = c->n_tiles; G.n_tiles_dev = nullptr; }
-        else { G.n_tiles = (c->nrec + 63) / 64; G.n_tiles_dev = c->d_tile_count.as<uint32_t>(); }
-        /* the PPM tile gather and the kNN scalar-stream kernel record the costs */
-        if (c->tile_sort && !c->tiles_sorted && (p->estimator == PM_ESTIMATOR_PPM || c->knn_ss)) {
-            HIPCHK(c, c->d_tile_cost.ensure((size_t)((c->nrec + 63) / 64 + 8) * 2));
-            HIPCHK(c, c->d_tiles2.ensure(c->d_tiles.bytes));
-            G.tile_cost = c->d_tile_cost.as<uint16_t>();
-        }
-        /* fresh PPM gather: every radius is r2init, the first group's box comes from the tile's position box */
+    return PM_OK;
+}
+
+/* a pending reset is consumed by a fused gather over all records (it starts
+ * from the initial PPM state and writes it: consume); a split partial gather
+ * reads the initial radius and leaves the reset to pm_ppm_update_split, which
+ * writes every view record; any other gather needs it applied */
+static int gather_resolve_reset(Ctx *c, GatherParams &G, bool fused_full, bool split, hipStream_t s, bool &consume) {
+    consume = c->rec_fresh && fused_full;
+    if (!consume && !(split && c->rec_fresh)) return materialize_reset(c, s);
+    G.fresh = 1; /* every radius is r2init, the first group's box comes from the tile's position box */
+    G.r2init = c->rec_fresh_r2;
+    return PM_OK;
+}
+
+/* full-range tile gathers skip the tiles without an active record (their
+ * records are neither read nor written, except as partials outside a view) */
+static int gather_attach_tiles(Ctx *c, const pm_render_params *p, GatherParams &G, hipStream_t s) {
+    TileList &t = c->tiles;
+    HIPCHK(c, t.ensure(recs(c), s));
+    G.tiles = t.d_list.as<uint32_t>();
+    if (t.count_known) { G.n_tiles = t.n; G.n_tiles_dev = nullptr; }
+    else { G.n_tiles = (c->nrec + 63) / 64; G.n_tiles_dev = t.d_count.as<uint32_t>(); }
+    /* the PPM tile gather and the kNN scalar-stream kernel record the costs */
+    if (t.sort && !t.sorted && (p->estimator == PM_ESTIMATOR_PPM || c->knn_ss)) {
+        HIPCHK(c, t.d_cost.ensure((size_t)((c->nrec + 63) / 64 + 8) * 2));
+        HIPCHK(c, t.d_sorted.ensure(t.d_list.bytes));
+        G.tile_cost = t.d_cost.as<uint16_t>();
     }
-    if (c->counting) HIPCHK(c, hipMemsetAsync(c->d_counters.p, 0, 32, s));
-    /* a fused PPM tile gather bins the updated radii (grid_radius2) — over
-     * all records, or over each of a pass's bands (a device's bands in a
-     * group render or an all-gather rank): every gather of the pass adds to
-     * the same bins, summed once when the next pass chooses its grid, so the
-     * quantile describes every record the context gathers (the grid only
-     * sets the cost, never the sums) */
-    const bool hist = p->estimator == PM_ESTIMATOR_PPM && p->gather_structure == PM_GATHER_GRID && !partial &&
-                      !split && c->gather_kernel == PM_GK_TILE &&
-                      !c->counting && c->grid_quantile > 0.0 && c->r2_wanted;
-    if (hist) {
-        /* the reduce that read and re-zeroed the bins may have run on another
-         * stream (a trace issued ahead on a second stream chose its grid:
-         * dist.py's pipelined passes): this gather bins (and may clear) only
-         * after it — otherwise the two race on d_r2hist */
-        if (c->r2_pending && c->r2_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->r2_event, 0));
-        if (c->r2_accum && c->r2_accum_init != p->initial_radius2) { c->r2_accum = false; c->r2_dirty = true; }
-        if (!c->d_r2hist.p) {
-            HIPCHK(c, c->d_r2hist.ensure(R2_COPIES * R2_BINS * 4));
-            c->r2_dirty = true;
-        }
-        if (c->r2_dirty) { /* the reduce re-zeroes it; anything else left in it is dropped here */
-            HIPCHK(c, hipMemsetAsync(c->d_r2hist.p, 0, R2_COPIES * R2_BINS * 4, s));
-            c->r2_dirty = false;
-        }
-        if (!c->h_r2hist) {
-            HIPCHK(c, hipHostMalloc((void **)&c->h_r2hist, R2_BINS * 4, hipHostMallocMapped));
-            HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_r2hist_dev, c->h_r2hist, 0));
-        }
-        if (!c->r2_event) HIPCHK(c, hipEventCreateWithFlags(&c->r2_event, hipEventDisableTiming));
-        G.r2hist = c->d_r2hist.as<uint32_t>();
-        G.r2hist_inv = 1.0f / p->initial_radius2;
+    return PM_OK;
+}
+
+/* a fused PPM tile gather bins the updated radii (R2Plan) — over all
+ * records, or over each of a pass's bands (a device's bands in a group
+ * render or an all-gather rank): every gather of the pass adds to the same
+ * bins, summed once when the next pass chooses its grid (grid_radius2), so
+ * the quantile describes every record the context gathers */
+static int gather_attach_hist(Ctx *c, const pm_render_params *p, GatherParams &G, hipStream_t s) {
+    HIPCHK(c, c->d_hist.ensure(R2_COPIES * R2_BINS * 4));
+    if (!c->h_hist) {
+        HIPCHK(c, hipHostMalloc((void **)&c->h_hist, R2_BINS * 4, hipHostMallocMapped));
+        HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_hist_dev, c->h_hist, 0));
     }
-    timer_begin(c, "gather", s);
-    if (p->estimator == PM_ESTIMATOR_KNN) {
-        G.knn_k = p->knn_lookup;
-        G.knn_r2 = p->initial_radius2; /* pbrt's maxDistSquared: the buckets cover it */
-        /* every term (kernel <= 3/pi < 1) is <= alpha_max / r_k^2: <= 2^22 of
-         * the per-record scale per term (x4 headroom in amax), exact as a float
-         * and as an int32, and <= PM_KNN_MAX = 2^6 terms sum below 2^28 —
-         * exact in int32 */
-        const double amax = emission_bound(c, p) * std::pow(c->lsum.kd_max, (double)p->max_photon_count) * 4.0;
-        G.knn_fx = (float)(std::ldexp(1.0, 24) / std::max(amax, 1e-30));
-        G.slots = c->d_slots.as<pm_photon>();
-        if (c->knn_ss && !c->counting && c->gather_kernel == PM_GK_TILE) {
-            const int64_t nph = (int64_t)(c->d_pha.bytes / 16), pairs = (nph + 1) / 2 + 16;
-            const int64_t ntiles = (G.rec_end - G.rec_begin + 63) / 64;
-            HIPCHK(c, c->d_knnpk.ensure((size_t)pairs * 80));
-            HIPCHK(c, c->d_knnovf.ensure((size_t)(ntiles + KNN_OVF_HDR) * 4));
-            G.knn_pk_p = c->d_knnpk.as<float4>();
-            G.knn_pk_q = G.knn_pk_p + 2 * pairs;
-            G.knn_pk_pairs = pairs;
-            G.knn_pack = c->knn_pack_gen != c->map_gen || c->knn_pack_ptr != c->d_knnpk.p;
-            c->knn_pack_gen = c->map_gen;
-            c->knn_pack_ptr = c->d_knnpk.p;
-            G.knn_ovf_n = c->d_knnovf.as<uint32_t>();
-            G.knn_ovf = G.knn_ovf_n + KNN_OVF_HDR;
-        }
-#ifdef PM_TILE_TIMES
-        const char *tt_path = getenv("PM_TILE_TIMES");
-        const int64_t tt_n = (c->nrec + 63) / 64;
-        if (tt_path && G.tiles) {
-            HIPCHK(c, c->d_tile_times.ensure((size_t)tt_n * 64));
-            HIPCHK(c, hipMemsetAsync(c->d_tile_times.p, 0, (size_t)tt_n * 64, s));
-            G.tile_times = c->d_tile_times.as<unsigned long long>();
-        }
-#endif
-        HIPCHK(c, launch_gather_knn(G, c->counting, s));
-#ifdef PM_TILE_TIMES
-        if (G.tile_times) {
-            std::vector<unsigned long long> h((size_t)tt_n * 8);
-            HIPCHK(c, hipMemcpyAsync(h.data(), G.tile_times, h.size() * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-            if (FILE *f = fopen(tt_path, "ab")) {
-                const unsigned long long hdr[4] = {0xffffffffffffffffull, (unsigned long long)tt_n, 0, 0};
-                fwrite(hdr, 8, 4, f);
-                fwrite(h.data(), 8, h.size(), f);
-                fclose(f);
-            }
-        }
-#endif
-        if (G.knn_ovf_n && getenv("PM_KNN_SS_DEBUG")) { /* tiles handed back to k_gather_knn_tile */
-            uint32_t nb = 0;
-            HIPCHK(c, hipMemcpyAsync(&nb, G.knn_ovf_n, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-            fprintf(stderr, "pm knn_ss: %u of %lld tiles handed back\n", nb, (long long)(G.tiles ? G.n_tiles : (G.rec_end - G.rec_begin + 63) / 64));
-            std::vector<uint32_t> hdr(KNN_OVF_HDR);
-            HIPCHK(c, hipMemcpy(hdr.data(), G.knn_ovf_n, KNN_OVF_HDR * 4, hipMemcpyDeviceToHost));
-            if (hdr[1] || hdr[2]) { /* PM_KNN_SS_DBG builds */
-                fprintf(stderr, "pm knn_ss dbg: %u bad collects, %u NaN radii\n", hdr[1], hdr[2]);
-                for (uint32_t i = 0; i < std::min<uint32_t>(hdr[1], 60); ++i) {
-                    fprintf(stderr, "  ");
-                    for (int w = 0; w < 16; ++w) fprintf(stderr, " %u", hdr[64 + 16 * i + w]);
-                    fprintf(stderr, "\n");
-                }
-            }
-        }
-    } else {
-        if (p->gather_structure == PM_GATHER_KDTREE) HIPCHK(c, hipMemsetAsync(G.error, 0, 4, s));
-#ifdef PM_TILE_TIMES
-        /* diagnostic builds: env PM_TILE_TIMES=file appends each tile launch's
-         * per-wave (start, end, XCC_ID, HW_ID) records (tools/tile_times.py) */
-        const char *tt_path = getenv("PM_TILE_TIMES");
-        const int64_t tt_n = (c->nrec + 63) / 64;
-        if (tt_path && G.tiles) {
-            HIPCHK(c, c->d_tile_times.ensure((size_t)tt_n * 64));
-            HIPCHK(c, hipMemsetAsync(c->d_tile_times.p, 0, (size_t)tt_n * 64, s));
-            G.tile_times = c->d_tile_times.as<unsigned long long>();
-        }
-#endif
-        HIPCHK(c, launch_gather(G, p->gather_structure, partial != nullptr || split, c->counting, s));
-#ifdef PM_TILE_TIMES
-        if (G.tile_times) {
-            std::vector<unsigned long long> h((size_t)tt_n * 8);
-            HIPCHK(c, hipMemcpyAsync(h.data(), G.tile_times, h.size() * 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-            if (FILE *f = fopen(tt_path, "ab")) {
-                const unsigned long long hdr[4] = {0xffffffffffffffffull, (unsigned long long)tt_n, 0, 0};
-                fwrite(hdr, 8, 4, f);
-                fwrite(h.data(), 8, h.size(), f);
-                fclose(f);
-            }
-        }
-#endif
+    if (!c->hist_event) HIPCHK(c, hipEventCreateWithFlags(&c->hist_event, hipEventDisableTiming));
+    const R2Plan::BinPrep prep = c->grid_plan.before_bin(p->initial_radius2, s);
+    /* the reduce may have run on another stream (a trace issued ahead on a
+     * second stream chose its grid: dist.py's pipelined passes): without
+     * the wait the two race on the bins */
+    if (prep.wait) HIPCHK(c, hipStreamWaitEvent(s, c->hist_event, 0));
+    if (prep.clear) HIPCHK(c, hipMemsetAsync(c->d_hist.p, 0, R2_COPIES * R2_BINS * 4, s));
+    G.r2hist = c->d_hist.as<uint32_t>();
+    G.r2hist_inv = 1.0f / p->initial_radius2;
+    return PM_OK;
+}
+
+static int gather_knn_setup(Ctx *c, const pm_render_params *p, GatherParams &G) {
+    G.knn_k = p->knn_lookup;
+    G.knn_r2 = p->initial_radius2; /* pbrt's maxDistSquared: the buckets cover it */
+    /* every term (kernel <= 3/pi < 1) is <= alpha_max / r_k^2: <= 2^22 of
+     * the per-record scale per term (x4 headroom in amax), exact as a float
+     * and as an int32, and <= PM_KNN_MAX = 2^6 terms sum below 2^28 —
+     * exact in int32 */
+    const double amax = emission_bound(c, p) * std::pow(c->lsum.kd_max, (double)p->max_photon_count) * 4.0;
+    G.knn_fx = (float)(std::ldexp(1.0, 24) / std::max(amax, 1e-30));
+    G.slots = c->d_slots.as<pm_photon>();
+    if (c->knn_ss && !c->counting && c->gather_kernel == PM_GK_TILE) {
+        const int64_t nph = (int64_t)(c->d_pha.bytes / 16), pairs = (nph + 1) / 2 + 16;
+        const int64_t ntiles = (G.rec_end - G.rec_begin + 63) / 64;
+        HIPCHK(c, c->d_knnpk.ensure((size_t)pairs * 80));
+        HIPCHK(c, c->d_knnovf.ensure((size_t)(ntiles + KNN_OVF_HDR) * 4));
+        G.knn_pk_p = c->d_knnpk.as<float4>();
+        G.knn_pk_q = G.knn_pk_p + 2 * pairs;
+        G.knn_pk_pairs = pairs;
+        G.knn_pack = c->knn_pack_gen != c->map_gen || c->knn_pack_ptr != c->d_knnpk.p;
+        c->knn_pack_gen = c->map_gen;
+        c->knn_pack_ptr = c->d_knnpk.p;
+        G.knn_ovf_n = c->d_knnovf.as<uint32_t>();
+        G.knn_ovf = G.knn_ovf_n + KNN_OVF_HDR;
     }
+    return PM_OK;
+}
+
+/* diagnostic builds (-DPM_TILE_TIMES): env PM_TILE_TIMES=file appends each
+ * tile launch's per-wave (start, end, XCC_ID, HW_ID) records (tools/tile_times.py) */
+static int tile_times_attach(Ctx *c, GatherParams &G, hipStream_t s) {
+#ifdef PM_TILE_TIMES
+    const size_t bytes = (size_t)((c->nrec + 63) / 64) * 64;
+    if (getenv("PM_TILE_TIMES") && G.tiles) {
+        HIPCHK(c, c->d_tile_times.ensure(bytes));
+        HIPCHK(c, hipMemsetAsync(c->d_tile_times.p, 0, bytes, s));
+        G.tile_times = c->d_tile_times.as<unsigned long long>();
+    }
+#endif
+    return PM_OK;
+}
+
+static int tile_times_dump(Ctx *c, const GatherParams &G, hipStream_t s) {
+#ifdef PM_TILE_TIMES
+    if (!G.tile_times) return PM_OK;
+    const int64_t tt_n = (c->nrec + 63) / 64;
+    std::vector<unsigned long long> h((size_t)tt_n * 8);
+    HIPCHK(c, hipMemcpyAsync(h.data(), G.tile_times, h.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (FILE *f = fopen(getenv("PM_TILE_TIMES"), "ab")) {
+        const unsigned long long hdr[4] = {0xffffffffffffffffull, (unsigned long long)tt_n, 0, 0};
+        fwrite(hdr, 8, 4, f);
+        fwrite(h.data(), 8, h.size(), f);
+        fclose(f);
+    }
+#endif
+    return PM_OK;
+}
+
+/* env PM_KNN_SS_DEBUG: the tiles k_gather_knn_ss handed back to k_gather_knn_tile */
+static int knn_ss_debug_dump(Ctx *c, const GatherParams &G, hipStream_t s) {
+    uint32_t nb = 0;
+    HIPCHK(c, hipMemcpyAsync(&nb, G.knn_ovf_n, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    fprintf(stderr, "pm knn_ss: %u of %lld tiles handed back\n", nb, (long long)(G.tiles ? G.n_tiles : (G.rec_end - G.rec_begin + 63) / 64));
+    std::vector<uint32_t> hdr(KNN_OVF_HDR);
+    HIPCHK(c, hipMemcpy(hdr.data(), G.knn_ovf_n, KNN_OVF_HDR * 4, hipMemcpyDeviceToHost));
+    if (hdr[1] || hdr[2]) { /* PM_KNN_SS_DBG builds */
+        fprintf(stderr, "pm knn_ss dbg: %u bad collects, %u NaN radii\n", hdr[1], hdr[2]);
+        for (uint32_t i = 0; i < std::min<uint32_t>(hdr[1], 60); ++i) {
+            fprintf(stderr, "  ");
+            for (int w = 0; w < 16; ++w) fprintf(stderr, " %u", hdr[64 + 16 * i + w]);
+            fprintf(stderr, "\n");
+        }
+    }
+    return PM_OK;
+}
+
+static int gather_launch(Ctx *c, const pm_render_params *p, GatherParams &G, bool partials, hipStream_t s) {
+    const bool knn = p->estimator == PM_ESTIMATOR_KNN;
+    int rc;
+    if (!knn && p->gather_structure == PM_GATHER_KDTREE) HIPCHK(c, hipMemsetAsync(G.error, 0, 4, s));
+    if ((rc = tile_times_attach(c, G, s))) return rc;
+    if (knn) HIPCHK(c, launch_gather_knn(G, c->counting, s));
+    else HIPCHK(c, launch_gather(G, p->gather_structure, partials, c->counting, s));
+    if ((rc = tile_times_dump(c, G, s))) return rc;
+    if (knn && G.knn_ovf_n && getenv("PM_KNN_SS_DEBUG")) return knn_ss_debug_dump(c, G, s);
+    return PM_OK;
+}
+
+/* after the launch: the tile sort, the kd-tree gather's error word, the state the gather leaves */
+static int gather_post(Ctx *c, const pm_render_params *p, GatherParams &G, bool consume, bool hist, hipStream_t s) {
     if (G.tile_cost) { /* the measured wave lifetimes reorder the list for the next gathers */
-        HIPCHK(c, launch_tile_sort(G.tiles, G.tile_cost, G.n_tiles_dev, G.n_tiles, c->d_tiles2.as<uint32_t>(), s));
-        std::swap(c->d_tiles, c->d_tiles2);
-        c->tiles_sorted = true;
+        HIPCHK(c, launch_tile_sort(G.tiles, G.tile_cost, G.n_tiles_dev, G.n_tiles, c->tiles.d_sorted.as<uint32_t>(), s));
+        c->tiles.swap_sorted();
     }
     timer_end(c, "gather", s);
     if (p->estimator != PM_ESTIMATOR_KNN && p->gather_structure == PM_GATHER_KDTREE) {
@@ -1794,16 +1733,35 @@ static int gather_common(Ctx *c, const pm_render_params *p, long long *partial, 
     }
     c->rec_estimator = p->estimator;
     if (consume) c->rec_fresh = false;
-    if (hist) {
-        /* summed by grid_radius2 at the next pass, into host-mapped memory by
-         * a one-block kernel: no copy-engine transfer in the stream (a
-         * per-pass D2H copy cost ~0.5 ms of C2 step) */
-        c->r2_accum = true;
-        c->r2_accum_init = p->initial_radius2;
-    } else if (p->estimator == PM_ESTIMATOR_KNN) {
-        r2_invalidate(c); /* r_k^2 replaced the radii */
-    }
+    if (hist) c->grid_plan.binned(p->initial_radius2);
+    else if (p->estimator == PM_ESTIMATOR_KNN) c->grid_plan.invalidate(); /* r_k^2 replaced the radii */
     return PM_OK;
+}
+
+static int gather_common(Ctx *c, const pm_render_params *p, long long *partial, int64_t rec_begin, int64_t rec_count,
+                         void *stream, int *count = nullptr, long long *flux = nullptr) {
+    const bool split = count != nullptr, partials = partial != nullptr || split;
+    int rc;
+    if ((rc = gather_validate(c, p, partials, rec_begin, rec_count))) return rc;
+    hipStream_t s = pick(c, stream);
+    const bool full = rec_begin == 0 && rec_count == c->nrec;
+    const bool tile_kernel = c->gather_kernel == PM_GK_TILE && !c->counting && p->gather_structure == PM_GATHER_GRID;
+    GatherParams G = gather_params(c, p);
+    G.partial = partial;
+    G.count = count;
+    G.flux = flux;
+    G.rec_begin = rec_begin;
+    G.rec_end = rec_begin + rec_count;
+    bool consume;
+    if ((rc = gather_resolve_reset(c, G, full && !partials, split, s, consume))) return rc;
+    if (tile_kernel && full && (!partials || c->view_active) && (rc = gather_attach_tiles(c, p, G, s))) return rc;
+    if (c->counting) HIPCHK(c, hipMemsetAsync(c->d_counters.p, 0, 32, s));
+    const bool hist = tile_kernel && !partials && c->grid_plan.active(p->estimator) && c->grid_plan.wanted;
+    if (hist && (rc = gather_attach_hist(c, p, G, s))) return rc;
+    timer_begin(c, "gather", s);
+    if (p->estimator == PM_ESTIMATOR_KNN && (rc = gather_knn_setup(c, p, G))) return rc;
+    if ((rc = gather_launch(c, p, G, partials, s))) return rc;
+    return gather_post(c, p, G, consume, hist, s);
 }
 
 int pm_gather(void *ptr, const pm_render_params *p, void *stream) {
@@ -1912,7 +1870,7 @@ int pm_set_radius2(void *ptr, const void *d_in, int64_t rec_begin, int64_t rec_c
     int rc;
     if ((rc = materialize_reset(c, pick(c, stream)))) return rc;
     HIPCHK(c, launch_radius2_io(recs(c), (float *)d_in, rec_begin, rec_count, 1, view_list(c), pick(c, stream)));
-    r2_invalidate(c); /* radii may have grown */
+    c->grid_plan.invalidate(); /* radii may have grown */
     return PM_OK;
 }
 
@@ -1923,11 +1881,7 @@ int pm_final(void *ptr, double emitted, int64_t rec_begin, int64_t rec_count, vo
     hipStream_t s = pick(c, stream);
     int rc;
     if ((rc = materialize_reset(c, s))) return rc;
-    FinalParams F{};
-    F.R = recs(c);
-    F.knn = c->rec_estimator == PM_ESTIMATOR_KNN; F.materials = c->S.materials;
-    F.emitted = (float)emitted; /* gContext["emittingPhotons"]->setFloat((float)totalPhotons) */
-    F.rec_begin = rec_begin; F.rec_count = rec_count; F.out = (float *)d_out; F.raster = 0; F.W = c->W;
+    const FinalParams F = final_params(c, emitted, rec_begin, rec_count, (float *)d_out);
     timer_begin(c, "final", s);
     HIPCHK(c, launch_final(F, s));
     timer_end(c, "final", s);
@@ -1935,19 +1889,46 @@ int pm_final(void *ptr, double emitted, int64_t rec_begin, int64_t rec_count, vo
 }
 
 /* ------------------------------------------------------------ whole render */
-/* the all-gather mode's record ranges of each device: 8-row bands (`unit`
- * records each) in runs dealt round-robin, about four runs per device
- * (pmrender/dist.py _bands) */
-static std::vector<std::vector<std::pair<int64_t, int64_t>>> device_bands(int64_t n, int64_t unit, int world) {
-    std::vector<std::vector<std::pair<int64_t, int64_t>>> owned(world);
-    const int64_t units = (n + unit - 1) / unit;
-    const int64_t runs = std::max<int64_t>(1, (units + (int64_t)world * 4 - 1) / ((int64_t)world * 4));
-    int k = 0;
-    for (int64_t u = 0; u < units; u += runs, ++k) {
-        const int64_t b = u * unit, e = std::min(n, (u + runs) * unit);
-        owned[k % world].push_back({b, e - b});
+/* the pieces pm_render, group_render and pm_render_simple share; HIP errors
+ * are reported on ec (a group's context, or c itself) */
+
+/* valid photons of the map c just built; waits for its stream */
+static int valid_photons(Ctx *ec, Ctx *c, const pm_render_params *p, int64_t &nvalid) {
+    nvalid = c->kd_count;
+    if (p->gather_structure == PM_GATHER_GRID) {
+        uint32_t nv = 0;
+        HIPCHK(ec, hipMemcpyAsync(&nv, c->d_cell_start.as<uint32_t>() + c->grid.ncells, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(ec, hipStreamSynchronize(c->stream));
+        nvalid = nv;
     }
-    return owned;
+    if (nvalid == 0) FAIL(ec, PM_ERR_NO_PHOTONS, "0 valid photons (photonmappingrenderer.cpp:165-167)");
+    return PM_OK;
+}
+
+/* c->d_out (nout radiances: the sample raster, or one per ray) -> the host
+ * image, through the film when the camera has a filter; waits */
+static int deliver_image(Ctx *c, int64_t nout, float *out_rgb) {
+    const void *src = c->d_out.p;
+    if (has_film(c)) {
+        nout = (int64_t)c->cam.width * c->cam.height;
+        HIPCHK(c, c->d_img.ensure(nout * 3 * sizeof(float)));
+        if (int rc = pm_film(c, c->d_out.p, c->d_img.p, c->stream)) return rc;
+        src = c->d_img.p;
+    }
+    HIPCHK(c, hipMemcpyAsync(out_rgb, src, nout * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PM_OK;
+}
+
+/* the stats every photon render reports: paths, valid photons, active records (read back from c) */
+static int render_stats(Ctx *ec, Ctx *c, double emitted, int64_t nvalid, pm_stats *st) {
+    std::memset(st, 0, sizeof(*st));
+    st->paths_emitted = (int64_t)emitted;
+    st->photons_valid = nvalid;
+    std::vector<float4> pos(c->nrec);
+    HIPCHK(ec, hipMemcpy(pos.data(), c->d_pos.p, c->nrec * sizeof(float4), hipMemcpyDeviceToHost));
+    for (auto &q : pos) st->gather_points += (fbits_h(q.w) & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID)) == 0;
+    return PM_OK;
 }
 
 /* one progressive render over the group's devices (Group): per pass every
@@ -2027,16 +2008,8 @@ static int group_render(Ctx *gc, const pm_render_params *p, float *out_rgb, pm_s
                 return sub_fail(c, rc);
             }
         }
-        if (p->gather_structure == PM_GATHER_GRID) {
-            uint32_t nv = 0;
-            (void)hipSetDevice(c0->device);
-            HIPCHK(gc, hipMemcpyAsync(&nv, c0->d_cell_start.as<uint32_t>() + c0->grid.ncells, 4, hipMemcpyDeviceToHost, c0->stream));
-            HIPCHK(gc, hipStreamSynchronize(c0->stream));
-            nvalid = nv;
-        } else {
-            nvalid = c0->kd_count;
-        }
-        if (nvalid == 0) FAIL(gc, PM_ERR_NO_PHOTONS, "0 valid photons (photonmappingrenderer.cpp:165-167)");
+        (void)hipSetDevice(c0->device);
+        if ((rc = valid_photons(gc, c0, p, nvalid))) return rc;
         for (int d = 0; d < n; ++d) {
             Ctx *c = G.subs[d];
             (void)hipSetDevice(c->device);
@@ -2072,12 +2045,9 @@ static int group_render(Ctx *gc, const pm_render_params *p, float *out_rgb, pm_s
         if ((rc = materialize_reset(c, c->stream))) return sub_fail(c, rc);
         HIPCHK(gc, c->d_out.ensure(nout * 3 * sizeof(float)));
         for (const auto &bc : bands[d]) {
-            FinalParams F{};
-            F.R = recs(c);
-            F.knn = c->rec_estimator == PM_ESTIMATOR_KNN; F.materials = c->S.materials;
-            F.emitted = (float)emitted;
-            F.rec_begin = bc.first; F.rec_count = bc.second; F.raster = c->pinhole; F.W = c->W;
-            F.out = c->pinhole ? c->d_out.as<float>() : c->d_out.as<float>() + 3 * bc.first;
+            FinalParams F = final_params(c, emitted, bc.first, bc.second,
+                                         c->pinhole ? c->d_out.as<float>() : c->d_out.as<float>() + 3 * bc.first);
+            F.raster = c->pinhole;
             HIPCHK(gc, launch_final(F, c->stream));
             int64_t o0 = bc.first, o1 = bc.first + bc.second; /* output elements of the band */
             if (c->pinhole) {
@@ -2093,23 +2063,12 @@ static int group_render(Ctx *gc, const pm_render_params *p, float *out_rgb, pm_s
     for (int d = 0; d < n; ++d) { (void)hipSetDevice(G.subs[d]->device); HIPCHK(gc, hipStreamSynchronize(G.subs[d]->stream)); }
     if (film) {
         (void)hipSetDevice(c0->device);
-        const int64_t nimg = (int64_t)c0->cam.width * c0->cam.height;
-        HIPCHK(gc, c0->d_img.ensure(nimg * 3 * sizeof(float)));
         HIPCHK(gc, hipMemcpyAsync(c0->d_out.p, raster.data(), raster.size() * sizeof(float), hipMemcpyHostToDevice, c0->stream));
-        if ((rc = pm_film(c0, c0->d_out.p, c0->d_img.p, c0->stream))) return sub_fail(c0, rc);
-        HIPCHK(gc, hipMemcpyAsync(img_rgb, c0->d_img.p, nimg * 3 * sizeof(float), hipMemcpyDeviceToHost, c0->stream));
-        HIPCHK(gc, hipStreamSynchronize(c0->stream));
+        if ((rc = deliver_image(c0, nout, img_rgb))) return sub_fail(c0, rc);
     }
     if (st) {
-        std::memset(st, 0, sizeof(*st));
-        st->paths_emitted = (int64_t)emitted;
-        st->photons_valid = nvalid;
-        std::vector<float4> pos(nrec);
         (void)hipSetDevice(c0->device);
-        HIPCHK(gc, hipMemcpy(pos.data(), c0->d_pos.p, nrec * sizeof(float4), hipMemcpyDeviceToHost));
-        int64_t act = 0;
-        for (auto &q : pos) act += (fbits_h(q.w) & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID)) == 0;
-        st->gather_points = act;
+        if ((rc = render_stats(gc, c0, emitted, nvalid, st))) return rc;
         st->ms_eye = timer_ms(c0, "eye"); st->ms_trace = t_trace; st->ms_build = t_build; st->ms_gather = t_gather;
     }
     return PM_OK;
@@ -2133,15 +2092,7 @@ int pm_render(void *ptr, const pm_render_params *p, float *out_rgb, pm_stats *st
         t_trace += timer_ms(c, "trace");
         if ((rc = pm_build_photon_map(c, p, p->paths_per_pass * p->max_photon_count, s))) return rc;
         t_build += timer_ms(c, "build");
-        if (p->gather_structure == PM_GATHER_GRID) {
-            uint32_t nv = 0;
-            HIPCHK(c, hipMemcpyAsync(&nv, c->d_cell_start.as<uint32_t>() + c->grid.ncells, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-            nvalid = nv;
-        } else {
-            nvalid = c->kd_count;
-        }
-        if (nvalid == 0) FAIL(c, PM_ERR_NO_PHOTONS, "0 valid photons (photonmappingrenderer.cpp:165-167)");
+        if ((rc = valid_photons(c, c, p, nvalid))) return rc;
         if ((rc = pm_gather(c, p, s))) return rc;
         t_gather += timer_ms(c, "gather");
         if (c->counting) {
@@ -2153,33 +2104,15 @@ int pm_render(void *ptr, const pm_render_params *p, float *out_rgb, pm_stats *st
     const double emitted = (double)p->paths_per_pass * p->passes;
     const int64_t nout = c->pinhole ? (int64_t)c->W * c->H : c->nrec;
     HIPCHK(c, c->d_out.ensure(nout * 3 * sizeof(float)));
-    FinalParams F{};
-    F.R = recs(c);
-    F.knn = c->rec_estimator == PM_ESTIMATOR_KNN; F.materials = c->S.materials;
-    F.emitted = (float)emitted;
-    F.rec_begin = 0; F.rec_count = c->nrec; F.out = c->d_out.as<float>(); F.raster = c->pinhole; F.W = c->W;
+    FinalParams F = final_params(c, emitted, 0, c->nrec, c->d_out.as<float>());
+    F.raster = c->pinhole;
     timer_begin(c, "final", s);
     HIPCHK(c, launch_final(F, s));
     timer_end(c, "final", s);
-    if (has_film(c)) { /* sample raster -> image */
-        const int64_t nimg = (int64_t)c->cam.width * c->cam.height;
-        HIPCHK(c, c->d_img.ensure(nimg * 3 * sizeof(float)));
-        if ((rc = pm_film(c, c->d_out.p, c->d_img.p, s))) return rc;
-        HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_img.p, nimg * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-    } else {
-        HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_out.p, nout * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(c, hipStreamSynchronize(s));
+    if ((rc = deliver_image(c, nout, out_rgb))) return rc;
     t_final = timer_ms(c, "final");
     if (st) {
-        std::memset(st, 0, sizeof(*st));
-        st->paths_emitted = (int64_t)emitted;
-        st->photons_valid = nvalid;
-        std::vector<float4> pos(c->nrec);
-        HIPCHK(c, hipMemcpy(pos.data(), c->d_pos.p, c->nrec * sizeof(float4), hipMemcpyDeviceToHost));
-        int64_t act = 0;
-        for (auto &q : pos) act += (fbits_h(q.w) & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID)) == 0;
-        st->gather_points = act;
+        if ((rc = render_stats(c, c, emitted, nvalid, st))) return rc;
         st->nodes_visited = counters[0];
         st->photons_in_radius = counters[1];
         st->ms_eye = t_eye; st->ms_trace = t_trace; st->ms_build = t_build; st->ms_gather = t_gather;
@@ -2223,15 +2156,7 @@ int pm_render_simple(void *ptr, const pm_render_params *p, float *out_rgb, pm_st
     hipStream_t s = c->stream;
     int rc;
     if ((rc = pm_simple_pass(c, p, c->d_out.p, s))) return rc;
-    if (has_film(c)) {
-        const int64_t nimg = (int64_t)c->cam.width * c->cam.height;
-        HIPCHK(c, c->d_img.ensure(nimg * 3 * sizeof(float)));
-        if ((rc = pm_film(c, c->d_out.p, c->d_img.p, s))) return rc;
-        HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_img.p, nimg * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-    } else {
-        HIPCHK(c, hipMemcpyAsync(out_rgb, c->d_out.p, nout * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(c, hipStreamSynchronize(s));
+    if ((rc = deliver_image(c, nout, out_rgb))) return rc;
     if (st) {
         std::memset(st, 0, sizeof(*st));
         st->gather_points = nout;
@@ -2330,8 +2255,8 @@ int pm_upload_records(void *ptr, const pm_record *in, int64_t n) {
     HIPCHK(c, hipMemcpy(c->d_dl.p, dl.data(), n * 16, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_n.p, N.data(), n * 4, hipMemcpyHostToDevice));
     c->rec_fresh = false; /* every record overwritten */
-    c->tiles_valid = false;
-    r2_invalidate(c);
+    c->tiles.invalidate();
+    c->grid_plan.invalidate();
     if (c->view_active && (rc = build_view(c, c->stream))) return rc;
     return PM_OK;
 }
@@ -2453,11 +2378,7 @@ int pm_final_view(void *ptr, double emitted, int64_t v_begin, int64_t v_count, v
     hipStream_t s = pick(c, stream);
     int rc;
     if ((rc = materialize_reset(c, s))) return rc;
-    FinalParams F{};
-    F.R = recs(c);
-    F.knn = c->rec_estimator == PM_ESTIMATOR_KNN; F.materials = c->S.materials;
-    F.emitted = (float)emitted;
-    F.rec_begin = v_begin; F.rec_count = v_count; F.out = (float *)d_out; F.raster = 0; F.W = c->W;
+    FinalParams F = final_params(c, emitted, v_begin, v_count, (float *)d_out);
     F.view = c->d_vlist.as<uint32_t>();
     timer_begin(c, "final", s);
     HIPCHK(c, launch_final(F, s));
@@ -2548,7 +2469,7 @@ int pm_reset_records(void *ptr, const pm_render_params *p, void *stream) {
      * other reader applies it first (materialize_reset) */
     c->rec_fresh = true;
     c->rec_fresh_r2 = p->initial_radius2;
-    r2_invalidate(c);
+    c->grid_plan.invalidate();
     return PM_OK;
 }
 

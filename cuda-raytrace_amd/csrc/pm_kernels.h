@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "pm_device.h"
+#include "pm_plan_pod.h"
 
 namespace pm {
 
@@ -143,12 +144,7 @@ struct FilmParams {
     int row_w, band_rows; /* staged row width (samples) and rows per band */
 };
 
-constexpr int R2_BINS = 64, R2_COPIES = 256, R2_PER_OCTAVE = 8; /* radius histogram (adaptive grid) */
-struct GridDesc {
-    float gx, gy, gz, inv_cs;
-    int dx, dy, dz;
-    uint32_t ncells;
-};
+/* GridDesc, R2_BINS, R2_COPIES, R2_PER_OCTAVE: pm_plan_pod.h */
 
 /* bucket coordinate along one axis, clamped (points outside the scene box
  * map to the border cells on both the build and the query side) */

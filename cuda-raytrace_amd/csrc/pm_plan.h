@@ -1,0 +1,89 @@
+/*
+ * pm_plan.h — pass planning: which photon grid a pass gets (the grid of a
+ * radius, the adaptive radius and its state machine) and which record bands
+ * a device of a group gathers. Host code only, no HIP: pm_api.cpp performs
+ * the HIP call each answer asks for, and tests/native drives the same code
+ * on a CPU (tests/test_pass_plan.py).
+ */
+#pragma once
+#include <stdint.h>
+
+#include <utility>
+#include <vector>
+
+#include "../../include/pm_api.h"
+#include "pm_plan_pod.h"
+
+namespace pm {
+
+/* photon-bucket grid over the scene box [lo, hi] for queries of radius^2
+ * `radius2`. PPM: cell edge 2 r / (cell_span - 1), so a query box
+ * [p - r', p + r'], r' <= r, spans <= cell_span cells per axis (span 2 by
+ * default: at most 2x2x2 cells; env PM_CELL_SPAN 3..5 for finer cells,
+ * DESIGN.md §5 sweep). kNN: r / 2 — the query visits rows nearest first and
+ * prunes cells beyond the shrinking k-th distance (k_gather_knn). Cells grow
+ * by 1.25 until the grid has at most 2^25 of them. */
+GridDesc make_grid(const float lo[3], const float hi[3], int estimator, int cell_span, float radius2);
+
+/* the grid radius^2 that covers `quantile` of the radii binned in hist
+ * (bin b counts r^2 / init in (2^(-(b+1)/8), 2^(-b/8)], pm_gather.hip), at
+ * most init; 0 for an empty histogram. *bin: the bin chosen. */
+float quantile_radius2(const uint32_t hist[R2_BINS], float init, double quantile, int *bin = nullptr);
+
+/* Adaptive grid radius (progressive PPM: radii shrink pass by pass). The
+ * fused tile gather bins every updated r^2 (R2_BINS log bins per copy,
+ * R2_COPIES copies) on the device; when the next pass chooses its grid the
+ * bins are reduced into host-mapped memory behind an event and, once landed,
+ * set the following passes' grid radius to the `quantile` of the records'
+ * radii (the rest scan per lane). Staleness is safe (radii only shrink);
+ * anything that can raise a radius (eye pass, reset, upload, set_radius2,
+ * kNN radii) invalidates it. The grid only sets the cost of a gather, never
+ * its sums. Streams are opaque identities. */
+struct R2Plan {
+    double quantile = 0.9;   /* env PM_GRID_QUANTILE; <= 0 disables. C5 step (same box, 3 runs each): 0.95 0.82-0.85 ms, 0.9 0.784-0.790, 0.8 0.826 */
+    bool wanted = false;     /* a progressive pass asked for the radii (no histogram otherwise) */
+    bool accum = false;      /* the device bins hold this pass's gathers (every band), not yet reduced */
+    bool dirty = true;       /* the device bins hold nothing usable (never zeroed, or invalidated radii): zero before binning */
+    bool pending = false;    /* a reduce in flight */
+    bool valid = false;      /* the last landed / in-flight histogram describes the records */
+    float accum_init = 0.f;  /* the r^2 the accumulated bins are relative to */
+    float hist_init = 0.f;   /* the r^2 the histogram's bins are relative to */
+    float design_r2 = 0.f;   /* grid radius^2 from the last landed histogram (0: the initial radius) */
+    const void *stream = nullptr; /* the stream the last reduce ran on */
+
+    /* false (kNN, or disabled): the grid radius is the initial radius and no event below is delivered */
+    bool active(int estimator) const { return estimator != PM_ESTIMATOR_KNN && quantile > 0.0; }
+
+    /* a new pass chooses its grid, in this order: */
+    /* the pending reduce's event has fired: the R2_BINS host words set the
+     * grid radius if they still describe the records of a pass with `init` */
+    void landed(const uint32_t hist[R2_BINS], float init);
+    /* the previous pass's gathers binned their radii: reduce them once (not
+     * while a reduce is in flight: the host words are reused; the bins keep
+     * accumulating, and older radii only overestimate) */
+    bool reduce_due() const { return accum && !pending; }
+    /* the reduce and its event were issued on `s` (both succeeded) */
+    void reduce_issued(const void *s);
+    /* a pass that continues a render (no reset pending) has its gathers bin their radii for the passes after it */
+    void pass_began(bool rec_fresh) { wanted = !rec_fresh; }
+    float radius2(float init, bool rec_fresh) const;
+
+    /* a gather is about to bin radii relative to `init` on stream `s`.
+     * wait: the pending reduce reads and re-zeroes the bins on another
+     * stream — bin (and clear) only after its event. clear: zero the bins
+     * first (whatever they hold is dropped). */
+    struct BinPrep { bool wait, clear; };
+    BinPrep before_bin(float init, const void *s);
+    void binned(float init) { accum = true; accum_init = init; }
+
+    /* the records' radii changed in a way that may raise them: back to the
+     * initial radius; bins accumulated from the old radii are dropped */
+    void invalidate();
+};
+
+/* the all-gather mode's record ranges (begin, count) of each device: 8-row
+ * bands (`unit` records each) in runs dealt round-robin, about four runs per
+ * device (pmrender/dist.py _bands; tests/test_pass_plan.py holds them equal) */
+std::vector<std::vector<std::pair<int64_t, int64_t>>> device_bands(int64_t n, int64_t unit, int world);
+
+} // namespace pm

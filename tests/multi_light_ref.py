@@ -201,7 +201,7 @@ def scene_light_arrays(scene):
 
 
 def emission_bounds(scene, cdf=None):
-    """the emitted-weight bound of the fixed-point scales (pm_api.cpp pm_commit):
+    """the emitted-weight bound of the fixed-point scales (pm_scene.cpp light_summary):
     max over the lights of max|Le| * (4 pi | 2 pi area), each divided by its
     float pmf (lights with pmf > 0 only) when `cdf` is given"""
     types, le, areas = scene_light_arrays(scene)
