@@ -24,6 +24,9 @@
 #include "shapes/disk.h"
 #include "shapes/sphere.h"
 #include "shapes/trianglemesh.h"
+#include "textures/checkerboard.h"
+#include "textures/imagemap.h"
+#include "textures/scale.h"
 
 /* ---------------------------------------------------------------- pbrt -> descriptors */
 static pmcuda::Transform toPm(const Transform &t) {
@@ -88,6 +91,53 @@ CudaRender::~CudaRender() { /* the sub-renderer's pbrt objects (photonmappingren
     delete camera_;
 }
 
+/* a pbrt spectrum texture as the operand of a Kd texture: a constant, or an
+ * image with a UVMapping2D; false for anything else */
+static bool toPmOperand(const Texture<Spectrum> *t, pmcuda::TexOperand &o) {
+    DifferentialGeometry dg;
+    if (dynamic_cast<const ConstantTexture<Spectrum> *>(t)) {
+        o = pmcuda::TexOperand();
+        o.rgb = toPm(t->Evaluate(dg));
+        return true;
+    }
+    if (const ImageTexture<RGBSpectrum, Spectrum> *im = dynamic_cast<const ImageTexture<RGBSpectrum, Spectrum> *>(t)) {
+        const UVMapping2D *uv = dynamic_cast<const UVMapping2D *>(im->mapping);
+        if (!uv || !im->mipmap) return false;
+        o = pmcuda::TexOperand();
+        o.image = true;
+        o.w = im->mipmap->Width(); o.h = im->mipmap->Height();
+        o.wrap = im->mipmap->wrapMode == TEXTURE_BLACK ? PM_TEX_WRAP_BLACK
+                 : im->mipmap->wrapMode == TEXTURE_CLAMP ? PM_TEX_WRAP_CLAMP : PM_TEX_WRAP_REPEAT;
+        o.map[0] = uv->su; o.map[1] = uv->sv; o.map[2] = uv->du; o.map[3] = uv->dv;
+        o.texels.resize(3 * (size_t)o.w * (size_t)o.h);
+        for (int y = 0; y < o.h; ++y)
+            for (int x = 0; x < o.w; ++x) im->mipmap->Texel(0, x, y).ToRGB(&o.texels[3 * ((size_t)y * o.w + x)]);
+        return true; /* pbrt-v2 bakes the imagemap's scale into the texels: rgb stays 1 */
+    }
+    return false;
+}
+
+/* the Kd texture of a matte, for the classes the device evaluates per hit:
+ * imagemap, checkerboard (2-D; its antialiasing is not reproduced) and scale,
+ * over constant or image operands; null: the reference's single evaluation */
+static std::shared_ptr<const pmcuda::TextureDesc> toPmTexture(const Texture<Spectrum> *t) {
+    auto d = std::make_shared<pmcuda::TextureDesc>();
+    if (const Checkerboard2DTexture<Spectrum> *c = dynamic_cast<const Checkerboard2DTexture<Spectrum> *>(t)) {
+        const UVMapping2D *uv = dynamic_cast<const UVMapping2D *>(c->mapping);
+        if (!uv || !toPmOperand(c->tex1.GetPtr(), d->op[0]) || !toPmOperand(c->tex2.GetPtr(), d->op[1])) return nullptr;
+        d->kind = pmcuda::TextureDesc::Checker;
+        d->map[0] = uv->su; d->map[1] = uv->sv; d->map[2] = uv->du; d->map[3] = uv->dv;
+        return d;
+    }
+    if (const ScaleTexture<Spectrum, Spectrum> *s = dynamic_cast<const ScaleTexture<Spectrum, Spectrum> *>(t)) {
+        if (!toPmOperand(s->tex1.GetPtr(), d->op[0]) || !toPmOperand(s->tex2.GetPtr(), d->op[1])) return nullptr;
+        d->kind = pmcuda::TextureDesc::Scale;
+        return d;
+    }
+    if (dynamic_cast<const ImageTexture<RGBSpectrum, Spectrum> *>(t) && toPmOperand(t, d->op[0])) return d;
+    return nullptr; /* any other texture class: as today */
+}
+
 /* CudaMaterial::createCudaMeteral (cudamaterial.cpp:8-21): Kd / Kr evaluated
  * at a default DifferentialGeometry; anything else is matte 0.5 */
 const pmcuda::Material *CudaRender::material(const Material *m) {
@@ -98,6 +148,7 @@ const pmcuda::Material *CudaRender::material(const Material *m) {
     if (const MatteMaterial *mm = dynamic_cast<const MatteMaterial *>(m)) {
         d.kind = pmcuda::Material::Matte;
         d.k = toPm(mm->Kd->Evaluate(dg));
+        d.kd_tex = toPmTexture(mm->Kd.GetPtr());
     } else if (const MirrorMaterial *mi = dynamic_cast<const MirrorMaterial *>(m)) {
         d.kind = pmcuda::Material::Mirror;
         d.k = toPm(mi->Kr->Evaluate(dg));

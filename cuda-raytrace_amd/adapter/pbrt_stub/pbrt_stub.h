@@ -194,6 +194,60 @@ public:
 private:
     T value;
 };
+/* core/texture.h TextureMapping2D / UVMapping2D; core/mipmap.h MIPMap (level 0
+ * only: its size, wrap mode and texels); textures/{imagemap,checkerboard,scale}.h
+ * with the members the plugin reads. Texel row 0 is t = 0, as pbrt-v2's
+ * imagemap leaves it after flipping the file's rows. */
+class TextureMapping2D {
+public:
+    virtual ~TextureMapping2D() {}
+};
+class UVMapping2D : public TextureMapping2D {
+public:
+    UVMapping2D(float ssu = 1, float ssv = 1, float ddu = 0, float ddv = 0) : su(ssu), sv(ssv), du(ddu), dv(ddv) {}
+    float su, sv, du, dv;
+};
+enum ImageWrap { TEXTURE_REPEAT, TEXTURE_BLACK, TEXTURE_CLAMP };
+template <typename T> class MIPMap {
+public:
+    MIPMap(int w, int h, const T *img, ImageWrap wm = TEXTURE_REPEAT) : width(w), height(h), wrapMode(wm), texels(img, img + (size_t)w * h) {}
+    int Width() const { return width; }
+    int Height() const { return height; }
+    const T &Texel(int level, int s, int t) const { (void)level; return texels[(size_t)t * width + s]; }
+    int width, height;
+    ImageWrap wrapMode;
+    std::vector<T> texels;
+};
+template <typename Tmemory, typename Treturn> class ImageTexture : public Texture<Treturn> {
+public:
+    ImageTexture(TextureMapping2D *m, int w, int h, const Tmemory *img, ImageWrap wm) : mipmap(new MIPMap<Tmemory>(w, h, img, wm)), mapping(m) {}
+    ~ImageTexture() { delete mipmap; delete mapping; }
+    Treturn Evaluate(const DifferentialGeometry &) const { return Treturn(mipmap->Texel(0, 0, 0)); }
+    MIPMap<Tmemory> *mipmap;
+    TextureMapping2D *mapping;
+};
+template <typename T> class Checkerboard2DTexture : public Texture<T> {
+public:
+    enum { NONE, CLOSEDFORM } aaMethod;
+    Checkerboard2DTexture(TextureMapping2D *m, Reference<Texture<T> > c1, Reference<Texture<T> > c2, const std::string &aa)
+        : aaMethod(aa == "none" ? NONE : CLOSEDFORM), mapping(m), tex1(c1), tex2(c2) {}
+    ~Checkerboard2DTexture() { delete mapping; }
+    T Evaluate(const DifferentialGeometry &dg) const { return tex1->Evaluate(dg); }
+    TextureMapping2D *mapping;
+    Reference<Texture<T> > tex1, tex2;
+};
+template <typename T1, typename T2> class ScaleTexture : public Texture<T2> {
+public:
+    ScaleTexture(Reference<Texture<T1> > t1, Reference<Texture<T2> > t2) : tex1(t1), tex2(t2) {}
+    T2 Evaluate(const DifferentialGeometry &dg) const {
+        const T1 a = tex1->Evaluate(dg); const T2 b = tex2->Evaluate(dg);
+        float x[3], y[3]; a.ToRGB(x); b.ToRGB(y);
+        const float p[3] = {x[0] * y[0], x[1] * y[1], x[2] * y[2]};
+        return T2::FromRGB(p);
+    }
+    Reference<Texture<T1> > tex1;
+    Reference<Texture<T2> > tex2;
+};
 
 /* ---- core/shape.h, shapes/{trianglemesh,sphere,disk}.h ---------------------------------------------- */
 class Shape : public ReferenceCounted {

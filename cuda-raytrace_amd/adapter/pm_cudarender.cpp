@@ -150,8 +150,34 @@ int CudaRender::materialId(const Material *m) {
         rgb[0] = m->k.r; rgb[1] = m->k.g; rgb[2] = m->k.b;
     }
     int id = -1;
-    check(ctx_, pm_add_material(ctx_, type, rgb, &id), "pm_add_material");
+    if (m && m->kind == Material::Matte && m->kd_tex)
+        check(ctx_, pm_add_material_textured(ctx_, PM_MATTE, textureId(*m->kd_tex), &id), "pm_add_material_textured");
+    else
+        check(ctx_, pm_add_material(ctx_, type, rgb, &id), "pm_add_material");
     materials_[m] = id;
+    return id;
+}
+
+int CudaRender::textureId(const TextureDesc &t) {
+    int op_id[2] = {-1, -1};
+    float rgb[2][3];
+    const int nops = t.kind == TextureDesc::Single ? 1 : 2;
+    for (int k = 0; k < nops; ++k) {
+        const TexOperand &o = t.op[k];
+        rgb[k][0] = o.rgb.r; rgb[k][1] = o.rgb.g; rgb[k][2] = o.rgb.b;
+        if (o.image)
+            check(ctx_, pm_add_texture_image(ctx_, o.texels.data(), o.w, o.h, o.wrap, o.map, rgb[k], &op_id[k]),
+                  "pm_add_texture_image");
+    }
+    int id = op_id[0];
+    if (t.kind == TextureDesc::Checker)
+        check(ctx_, pm_add_texture_checker(ctx_, t.map, op_id[0], rgb[0], op_id[1], rgb[1], &id), "pm_add_texture_checker");
+    else if (t.kind == TextureDesc::Scale)
+        check(ctx_, pm_add_texture_scale(ctx_, op_id[0], rgb[0], op_id[1], rgb[1], &id), "pm_add_texture_scale");
+    else if (id < 0) { /* a single constant: a scale by white */
+        const float one[3] = {1.f, 1.f, 1.f};
+        check(ctx_, pm_add_texture_scale(ctx_, -1, rgb[0], -1, one, &id), "pm_add_texture_scale");
+    }
     return id;
 }
 

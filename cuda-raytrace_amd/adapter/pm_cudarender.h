@@ -32,6 +32,7 @@
 
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -62,9 +63,28 @@ struct RGB { float r, g, b; };
 
 /* what CudaMaterial::createCudaMeteral reads (cudamaterial.cpp:8-75): the
  * Kd / Kr texture evaluated at a default DifferentialGeometry */
+/* a Kd texture (pm_add_texture_*): an operand is a constant rgb, or an image
+ * (texels: 3 * w * h floats, row 0 at v = 0; rgb = its scale; its own
+ * UVMapping2D map = (su, sv, du, dv); wrap = PM_TEX_WRAP_*) */
+struct TexOperand {
+    bool image = false;
+    RGB rgb = {1.f, 1.f, 1.f};
+    std::vector<float> texels;
+    int w = 0, h = 0, wrap = PM_TEX_WRAP_REPEAT;
+    float map[4] = {1.f, 1.f, 0.f, 0.f};
+};
+struct TextureDesc {
+    enum Kind { Single, Checker, Scale } kind = Single; /* Single: op[0]; Checker: its own map; Scale: op[0] * op[1] */
+    float map[4] = {1.f, 1.f, 0.f, 0.f};
+    TexOperand op[2];
+};
+
 struct Material {
     enum Kind { Matte, Mirror, Glass, Unknown } kind = Matte;
     RGB k = {0.5f, 0.5f, 0.5f};
+    /* optional (Matte only): Kd is this texture, looked up per hit; k is then
+     * what the reference would use (the texture at a default point) */
+    std::shared_ptr<const TextureDesc> kd_tex;
 };
 
 /* what CudaShape::CreateCudaShape reads from a pbrt Shape:
@@ -188,6 +208,7 @@ public:
 
     void *context() const { return ctx_; }
     CudaRenderer *subRenderer() const { return renderer_; }
+    int textureId(const TextureDesc &t);     /* the texture through pm_add_texture_* */
     int materialId(const Material *m); /* dedupe per pbrt Material* (cudarender.cpp:181-192) */
     /* lights must be added before the first render; called by the renderer */
     void addLights(const std::vector<Light> &lights);

@@ -3,6 +3,8 @@
  */
 #include "pm_pbrt.h"
 
+#include "pm_image.h"
+
 #include <cctype>
 #include <cmath>
 #include <cstdarg>
@@ -263,7 +265,11 @@ struct PbrtParser::Impl {
     std::map<std::string, Transform> coord_sys;
     std::deque<Material> materials; /* stable addresses: CudaRender keys materials by pointer */
     std::map<std::string, const Material *> named_materials;
-    std::map<std::string, RGB> textures; /* constant spectrum textures */
+    /* spectrum textures by name: a constant (value), or desc: an imagemap, a
+     * checkerboard or a scale for the Kd of a matte (value: what the
+     * reference would see, the texture at a default point) */
+    struct Tex { RGB value; std::shared_ptr<const TextureDesc> desc; };
+    std::map<std::string, Tex> textures;
     std::map<std::string, int> instances; /* node addresses are the instance keys */
     const void *current_instance = nullptr;
     bool in_world = false;
@@ -360,11 +366,15 @@ struct PbrtParser::Impl {
     }
     /* GetSpectrumTexture evaluated at a default DifferentialGeometry
      * (cudamaterial.cpp:35-38): constant textures only */
-    RGB spectrum_tex(Lexer &lx, int line, const ParamSet &ps, const std::string &name, RGB dflt) {
+    RGB spectrum_tex(Lexer &lx, int line, const ParamSet &ps, const std::string &name, RGB dflt,
+                     std::shared_ptr<const TextureDesc> *desc = nullptr) {
         const Param *p = ps.find(name);
         if (p && p->type == "texture") {
             auto it = textures.find(p->strs.empty() ? "" : p->strs[0]);
-            if (it != textures.end()) return it->second;
+            if (it != textures.end() && (!it->second.desc || desc)) {
+                if (desc) *desc = it->second.desc;
+                return it->second.value;
+            }
             warn(lx, line, "texture \"%s\" is not a constant spectrum texture; using the default",
                  p->strs.empty() ? std::string() : p->strs[0]);
             return dflt;
@@ -372,11 +382,85 @@ struct PbrtParser::Impl {
         return spectrum(lx, line, ps, name, dflt);
     }
 
+    /* the TextureMapping2D of a texture's parameters: "uv" only */
+    bool mapping(Lexer &lx, int line, const ParamSet &ps, float map[4]) {
+        const std::string m = ps.oneString("mapping", "uv");
+        if (m != "uv") { warn(lx, line, "texture mapping \"%s\" not supported (uv only)", m); return false; }
+        map[0] = ps.oneFloat("uscale", 1.f); map[1] = ps.oneFloat("vscale", 1.f);
+        map[2] = ps.oneFloat("udelta", 0.f); map[3] = ps.oneFloat("vdelta", 0.f);
+        return true;
+    }
+    /* tex1 / tex2 of a checkerboard or scale: an rgb (or float), a constant
+     * texture or an imagemap; deeper nesting is refused */
+    bool operand(Lexer &lx, int line, const ParamSet &ps, const std::string &name, float dflt, TexOperand &o) {
+        const Param *p = ps.find(name);
+        o = TexOperand();
+        o.rgb = RGB{dflt, dflt, dflt};
+        if (!p) return true;
+        if (p->type != "texture") { o.rgb = spectrum(lx, line, ps, name, o.rgb); return true; }
+        const std::string n = p->strs.empty() ? std::string() : p->strs[0];
+        auto it = textures.find(n);
+        if (it == textures.end()) { warn(lx, line, "texture \"%s\" not defined", n); return false; }
+        if (!it->second.desc) { o.rgb = it->second.value; return true; }
+        if (it->second.desc->kind != TextureDesc::Single) {
+            warn(lx, line, "texture \"%s\" is a checkerboard or a scale: an operand is an imagemap or a constant", n);
+            return false;
+        }
+        o = it->second.desc->op[0];
+        return true;
+    }
+    static RGB operand_value(const TexOperand &o) { /* an image's stand-in at a default point: its first texel */
+        if (!o.image || o.texels.size() < 3) return o.rgb;
+        return RGB{o.texels[0] * o.rgb.r, o.texels[1] * o.rgb.g, o.texels[2] * o.rgb.b};
+    }
+    /* Texture "name" "color"|"spectrum" "imagemap"|"checkerboard"|"scale";
+     * false (after a warning): the texture stays undefined and a material
+     * that names it falls back to its default Kd */
+    bool make_texture(Lexer &lx, int line, const std::string &cls, const ParamSet &ps, const std::string &dir, Tex &out) {
+        auto d = std::make_shared<TextureDesc>();
+        if (cls == "imagemap") {
+            TexOperand &o = d->op[0];
+            if (!mapping(lx, line, ps, o.map)) return false;
+            std::string f = ps.oneString("filename", "");
+            if (f.empty()) { warn(lx, line, "imagemap without a \"string filename\"%s", ""); return false; }
+            if (f[0] != '/') f = dir + "/" + f;
+            const std::string w = ps.oneString("wrap", "repeat");
+            if (w == "repeat") o.wrap = PM_TEX_WRAP_REPEAT;
+            else if (w == "black") o.wrap = PM_TEX_WRAP_BLACK;
+            else if (w == "clamp") o.wrap = PM_TEX_WRAP_CLAMP;
+            else { warn(lx, line, "imagemap wrap \"%s\" unknown; using repeat", w); o.wrap = PM_TEX_WRAP_REPEAT; }
+            Image img;
+            std::string err;
+            if (!read_image(f, img, err)) lx.fail(line, "%s", err.c_str());
+            const float s = ps.oneFloat("scale", 1.f);
+            o.image = true; o.rgb = RGB{s, s, s};
+            o.w = img.w; o.h = img.h; o.texels.swap(img.rgb);
+            d->kind = TextureDesc::Single;
+        } else if (cls == "checkerboard") {
+            if (ps.oneInt("dimension", 2) != 2) { warn(lx, line, "checkerboard dimension %s not supported (2 only)", std::to_string(ps.oneInt("dimension", 2))); return false; }
+            const std::string aa = ps.oneString("aamode", "closedform"); /* pbrt-v2's default */
+            if (aa != "none") warn(lx, line, "checkerboard aamode \"%s\" not supported; using none", aa);
+            if (!mapping(lx, line, ps, d->map)) return false;
+            if (!operand(lx, line, ps, "tex1", 1.f, d->op[0]) || !operand(lx, line, ps, "tex2", 0.f, d->op[1])) return false;
+            d->kind = TextureDesc::Checker;
+        } else if (cls == "scale") {
+            if (!operand(lx, line, ps, "tex1", 1.f, d->op[0]) || !operand(lx, line, ps, "tex2", 1.f, d->op[1])) return false;
+            d->kind = TextureDesc::Scale;
+        } else {
+            warn(lx, line, "texture class \"%s\" not supported (constant, imagemap, checkerboard, scale)", cls);
+            return false;
+        }
+        const RGB a = operand_value(d->op[0]), b = operand_value(d->op[1]);
+        out.value = d->kind == TextureDesc::Scale ? RGB{a.r * b.r, a.g * b.g, a.b * b.b} : a;
+        out.desc = d;
+        return true;
+    }
+
     const Material *make_material(Lexer &lx, int line, const std::string &type, const ParamSet &ps) {
         Material m;
         if (type == "matte") {
             m.kind = Material::Matte;
-            m.k = spectrum_tex(lx, line, ps, "Kd", RGB{0.5f, 0.5f, 0.5f});
+            m.k = spectrum_tex(lx, line, ps, "Kd", RGB{0.5f, 0.5f, 0.5f}, &m.kd_tex); /* a texture of any kind for Kd */
         } else if (type == "mirror") {
             m.kind = Material::Mirror;
             m.k = spectrum_tex(lx, line, ps, "Kr", RGB{0.9f, 0.9f, 0.9f});
@@ -669,9 +753,13 @@ struct PbrtParser::Impl {
                 const std::string n = str(lx), type = str(lx), cls = str(lx);
                 const ParamSet ps = params(lx);
                 if ((type == "spectrum" || type == "color") && cls == "constant")
-                    textures[n] = spectrum(lx, line, ps, "value", RGB{1.f, 1.f, 1.f});
-                else if (type == "spectrum" || type == "color")
-                    warn(lx, line, "texture class \"%s\" not supported (constant only)", cls);
+                    textures[n] = Tex{spectrum(lx, line, ps, "value", RGB{1.f, 1.f, 1.f}), nullptr};
+                else if (type == "spectrum" || type == "color") {
+                    Tex t;
+                    if (make_texture(lx, line, cls, ps, dir, t)) textures[n] = t;
+                    else textures.erase(n);
+                } else
+                    warn(lx, line, "\"%s\" textures are not supported (color / spectrum only)", type);
             } else if (d == "LightSource") {
                 const std::string n = str(lx);
                 const ParamSet ps = params(lx);

@@ -9,7 +9,16 @@
  *   transforms   Identity Translate Scale Rotate LookAt Transform ConcatTransform
  *                CoordinateSystem CoordSysTransform TransformBegin/End
  *   state        WorldBegin/End AttributeBegin/End ReverseOrientation
- *                Material MakeNamedMaterial NamedMaterial Texture (constant)
+ *                Material MakeNamedMaterial NamedMaterial
+ *                Texture "name" "color"|"spectrum": "constant" (value);
+ *                "imagemap" (filename: PFM / TGA relative to the scene file,
+ *                wrap repeat|black|clamp, float scale, uscale vscale udelta
+ *                vdelta); "checkerboard" (tex1, tex2: rgb or a constant /
+ *                imagemap texture; the mapping; dimension 2; aamode other
+ *                than "none" warns and uses none); "scale" (tex1, tex2).
+ *                Material "matte" "texture Kd" takes any of them; a float
+ *                texture, a mapping other than "uv", dimension 3 or a nested
+ *                operand warns and leaves the texture undefined (default Kd)
  *   lights       LightSource "point" (I, scale, from), "distant" (L, scale,
  *                from, to; towards the light = CTM (from - to)), AreaLightSource "diffuse"
  *                (L, scale, nsamples) on the following "disk" and

@@ -42,6 +42,7 @@ struct Opts {
     int W = 64, H = 48, paths = 16384, nsamples = 1;
     std::string photonmap = "grid", renderer = "photonmap", out;
     bool instanced = false, quad_light = false, two_lights = false, sun = false;
+    bool checker = false; /* --checker (scenes/cornell-checker.pbrt): the floor's Kd is a checkerboard */
     int lightsource = 0;
     bool lightsource_set = false;
     /* --devicecamera: the Renderer "cuda" ParamSet's device camera + film */
@@ -137,7 +138,7 @@ Reference<Texture<Spectrum> > constant(float r, float g, float b) {
     return Reference<Texture<Spectrum> >(new ConstantTexture<Spectrum>(RGBSpectrum::FromRGB(c)));
 }
 
-Reference<Shape> quads(const Transform *o2w, const std::vector<std::vector<float> > &qs) {
+Reference<Shape> quads(const Transform *o2w, const std::vector<std::vector<float> > &qs, const float *uv = NULL) {
     std::vector<Point> P;
     std::vector<int> idx;
     for (const std::vector<float> &q : qs) {
@@ -146,7 +147,7 @@ Reference<Shape> quads(const Transform *o2w, const std::vector<std::vector<float
         idx.insert(idx.end(), {b, b + 1, b + 2, b, b + 2, b + 3});
     }
     return Reference<Shape>(new TriangleMesh(o2w, o2w, false, (int)idx.size() / 3, (int)P.size(), idx.data(), P.data(),
-                                             NULL, NULL, NULL));
+                                             NULL, NULL, uv));
 }
 
 int run(const Opts &o) {
@@ -159,6 +160,17 @@ int run(const Opts &o) {
     Reference<Material> black(new MatteMaterial(constant(0.f, 0.f, 0.f), NULL, NULL));
     /* WorldBegin ... Shape directives (pmrender/scenes.py cornell_box order) */
     Reference<Shape> s;
+    Reference<Material> checks; /* lives as long as the scene: materials are keyed by address */
+    if (o.checker) { /* Texture "checks" "color" "checkerboard" uscale 8 vscale 8 aamode none; the floor a mesh of its own with uvs */
+        checks = Reference<Material>(new MatteMaterial(
+            Reference<Texture<Spectrum> >(new Checkerboard2DTexture<Spectrum>(new UVMapping2D(8.f, 8.f, 0.f, 0.f), constant(0.73f, 0.73f, 0.73f),
+                                                                             constant(0.15f, 0.17f, 0.25f), "none")), NULL, NULL));
+        const float uv[8] = {0, 0, 1, 0, 1, 1, 0, 1};
+        s = quads(&identity, {{552.8f, 0, 0, 0, 0, 0, 0, 0, 559.2f, 549.6f, 0, 559.2f}}, uv);
+        CreateCudaShape("trianglemesh", s, NULL, checks.GetPtr(), -1);
+        s = quads(&identity, {{556.0f, 548.8f, 0, 556.0f, 548.8f, 559.2f, 0, 548.8f, 559.2f, 0, 548.8f, 0},
+                              {549.6f, 0, 559.2f, 0, 0, 559.2f, 0, 548.8f, 559.2f, 556.0f, 548.8f, 559.2f}});
+    } else
     s = quads(&identity, {{552.8f, 0, 0, 0, 0, 0, 0, 0, 559.2f, 549.6f, 0, 559.2f},
                           {556.0f, 548.8f, 0, 556.0f, 548.8f, 559.2f, 0, 548.8f, 559.2f, 0, 548.8f, 0},
                           {549.6f, 0, 559.2f, 0, 0, 559.2f, 0, 548.8f, 559.2f, 556.0f, 548.8f, 559.2f}});
@@ -270,6 +282,7 @@ int main(int argc, char **argv) {
         else if (a == "--quad-light") o.quad_light = true;
         else if (a == "--two-lights") o.two_lights = true;
         else if (a == "--sun") o.sun = true;
+        else if (a == "--checker") o.checker = true;
         else if (a == "--lightsource") { o.lightsource = std::stoi(val()); o.lightsource_set = true; }
         else if (a == "--out") o.out = val();
         else if (a == "--devicecamera") o.devicecamera = 1;

@@ -175,6 +175,25 @@ struct DumpSink : PbrtSink {
         std::snprintf(b, sizeof b, "\"material\": %d, \"k\": ", kind);
         out += b;
         arr(out, k, 3);
+        if (m && m->kd_tex) { /* the Kd texture: kind 0 single, 1 checkerboard, 2 scale */
+            const TextureDesc &t = *m->kd_tex;
+            out += ", \"kd_tex\": {\"kind\": " + std::to_string((int)t.kind) + ", \"map\": ";
+            arr(out, t.map, 4);
+            out += ", \"ops\": [";
+            for (int q = 0; q < (t.kind == TextureDesc::Single ? 1 : 2); ++q) {
+                const TexOperand &o = t.op[q];
+                const float c[3] = {o.rgb.r, o.rgb.g, o.rgb.b};
+                out += std::string(q ? ", " : "") + "{\"image\": " + (o.image ? "1" : "0") + ", \"rgb\": ";
+                arr(out, c, 3);
+                out += ", \"w\": " + std::to_string(o.w) + ", \"h\": " + std::to_string(o.h) + ", \"wrap\": " +
+                       std::to_string(o.wrap) + ", \"map\": ";
+                arr(out, o.map, 4);
+                out += ", \"texels\": ";
+                arr(out, o.texels.data(), o.texels.size());
+                out += "}";
+            }
+            out += "]}";
+        }
         out += ", \"P\": "; arr(out, s.P.data(), s.P.size());
         out += ", \"N\": "; arr(out, s.N.data(), s.N.size());
         out += ", \"uv\": "; arr(out, s.uv.data(), s.uv.size());

@@ -149,6 +149,10 @@ struct Ctx {
     LightSummary lsum;
     DevBuf d_light_cdf;
     DevBuf d_tripairs;                /* brute-force scenes: triangle pairs interleaved (SceneDev::tri_pairs_g) */
+    /* textured scenes only (SceneDev::tex_recs, texels, mat_tex, tri_uv), and
+     * the records' albedo factors (EyeParams::kd), sized like the records */
+    DevBuf d_tex_recs, d_texels, d_mat_tex, d_tri_uv, d_rkd;
+    bool textured = false;            /* the committed scene has a textured material */
     SceneDev S{};
     float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};
     bool slots_nonneg = true;  /* the slot buffer holds no negative flux (uploaded slots are checked) */
@@ -410,6 +414,13 @@ int ensure_records(Ctx *c) {
     HIPCHK(c, c->d_state.ensure(n * sizeof(float4)));
     HIPCHK(c, c->d_n.ensure(n * sizeof(float)));
     HIPCHK(c, c->d_dl.ensure(n * sizeof(float4)));
+    /* the albedo factors, only for a textured scene; a new buffer starts as
+     * all ones (records uploaded without an eye pass keep their flux as it is) */
+    if (c->textured && !(c->d_rkd.p && (size_t)n * sizeof(float4) <= c->d_rkd.bytes)) {
+        HIPCHK(c, c->d_rkd.ensure(n * sizeof(float4)));
+        const std::vector<float4> ones((size_t)n, f4(1.f, 1.f, 1.f, 0.f));
+        HIPCHK(c, hipMemcpy(c->d_rkd.p, ones.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
+    }
     c->nrec = n;
     c->tiles.invalidate();
     c->grid_plan.invalidate();
@@ -478,6 +489,7 @@ FinalParams final_params(Ctx *c, double emitted, int64_t begin, int64_t count, f
     F.knn = c->rec_estimator == PM_ESTIMATOR_KNN; F.materials = c->S.materials;
     F.emitted = (float)emitted; /* gContext["emittingPhotons"]->setFloat((float)totalPhotons) */
     F.rec_begin = begin; F.rec_count = count; F.out = out; F.raster = 0; F.W = c->W;
+    F.kd = c->textured ? c->d_rkd.as<float4>() : nullptr;
     return F;
 }
 
@@ -777,7 +789,8 @@ void pm_destroy(void *ptr) {
     DevBuf *bufs[] = {&c->d_scene, &c->d_rays, &c->d_rand2d, &c->d_pos, &c->d_nrm, &c->d_state, &c->d_n,
                       &c->d_dl, &c->d_slots, &c->d_count, &c->d_scratch, &c->d_vflags, &c->d_vrank, &c->d_vlist, &c->d_vsums,
                       &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times,
-                      &c->d_kd, &c->d_out, &c->d_counters, &c->d_hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf, &c->d_film_table, &c->d_img};
+                      &c->d_kd, &c->d_out, &c->d_counters, &c->d_hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf, &c->d_film_table, &c->d_img,
+                      &c->d_tex_recs, &c->d_texels, &c->d_mat_tex, &c->d_tri_uv, &c->d_rkd};
     for (DevBuf *b : bufs) b->release();
     c->tiles.release();
     if (c->hist_event) (void)hipEventDestroy(c->hist_event);
@@ -821,6 +834,57 @@ int pm_add_material(void *ptr, int type, const float rgb[3], int *out_id) {
     float r = rgb ? rgb[0] : 0.f, g = rgb ? rgb[1] : 0.f, b = rgb ? rgb[2] : 0.f;
     c->hs.materials.push_back(f4(r, g, b, ibits(type)));
     if (out_id) *out_id = (int)c->hs.materials.size() - 1;
+    c->committed = false;
+    return PM_OK;
+}
+
+/* textures: the arguments are checked, and the records built, in the
+ * host-only unit (pm_scene.cpp); what needs no context is checked before the
+ * context is looked at */
+int pm_add_texture_image(void *ptr, const float *rgb, int w, int h, int wrap, const float mapping[4], const float scale[3],
+                         int *out_tex) {
+    std::string err;
+    if (!out_tex) FAIL((Ctx *)nullptr, PM_ERR_INVALID, "pm_add_texture_image: null pointer");
+    if (int rc = check_texture_image(rgb, w, h, wrap, mapping, scale, err)) FAIL((Ctx *)nullptr, rc, "%s", err.c_str());
+    GROUP_FWD(ptr, pm_add_texture_image(sub, rgb, w, h, wrap, mapping, scale, out_tex));
+    GETCTX(ptr);
+    if (int rc = add_texture_image(c->hs, rgb, w, h, wrap, mapping, scale, out_tex, err)) FAIL(c, rc, "%s", err.c_str());
+    c->committed = false;
+    return PM_OK;
+}
+
+int pm_add_texture_checker(void *ptr, const float mapping[4], int tex1, const float rgb1[3], int tex2, const float rgb2[3],
+                           int *out_tex) {
+    std::string err;
+    if (!out_tex) FAIL((Ctx *)nullptr, PM_ERR_INVALID, "pm_add_texture_checker: null pointer");
+    if (int rc = check_texture_operands("pm_add_texture_checker", mapping, true, tex1, rgb1, tex2, rgb2, err))
+        FAIL((Ctx *)nullptr, rc, "%s", err.c_str());
+    GROUP_FWD(ptr, pm_add_texture_checker(sub, mapping, tex1, rgb1, tex2, rgb2, out_tex));
+    GETCTX(ptr);
+    if (int rc = add_texture_checker(c->hs, mapping, tex1, rgb1, tex2, rgb2, out_tex, err)) FAIL(c, rc, "%s", err.c_str());
+    c->committed = false;
+    return PM_OK;
+}
+
+int pm_add_texture_scale(void *ptr, int tex1, const float rgb1[3], int tex2, const float rgb2[3], int *out_tex) {
+    std::string err;
+    if (!out_tex) FAIL((Ctx *)nullptr, PM_ERR_INVALID, "pm_add_texture_scale: null pointer");
+    if (int rc = check_texture_operands("pm_add_texture_scale", nullptr, false, tex1, rgb1, tex2, rgb2, err))
+        FAIL((Ctx *)nullptr, rc, "%s", err.c_str());
+    GROUP_FWD(ptr, pm_add_texture_scale(sub, tex1, rgb1, tex2, rgb2, out_tex));
+    GETCTX(ptr);
+    if (int rc = add_texture_scale(c->hs, tex1, rgb1, tex2, rgb2, out_tex, err)) FAIL(c, rc, "%s", err.c_str());
+    c->committed = false;
+    return PM_OK;
+}
+
+int pm_add_material_textured(void *ptr, int type, int kd_tex, int *out_id) {
+    std::string err;
+    if (int rc = check_material_textured(type, err)) FAIL((Ctx *)nullptr, rc, "%s", err.c_str());
+    if (!out_id) FAIL((Ctx *)nullptr, PM_ERR_INVALID, "pm_add_material_textured: null pointer");
+    GROUP_FWD(ptr, pm_add_material_textured(sub, type, kd_tex, out_id));
+    GETCTX(ptr);
+    if (int rc = add_material_textured(c->hs, type, kd_tex, out_id, err)) FAIL(c, rc, "%s", err.c_str());
     c->committed = false;
     return PM_OK;
 }
@@ -1221,6 +1285,10 @@ static void fill_scene_dev(Ctx *c) {
     S.tri_geo_g = S.tri_geo; S.tri_id_g = S.tri_id;
     S.tri_pairs_g = L.id_order ? c->d_tripairs.as<float>() : nullptr;
     S.light_tris = c->d_light_tris.as<LightTri>();
+    S.tex_recs = c->textured ? c->d_tex_recs.as<TexRec>() : nullptr;
+    S.texels = c->textured ? c->d_texels.as<float4>() : nullptr;
+    S.mat_tex = c->textured ? c->d_mat_tex.as<int>() : nullptr;
+    S.tri_uv = c->textured ? c->d_tri_uv.as<float4>() : nullptr;
     S.n_inst = (int)ni;
     S.insts = ni ? (const float4 *)(base + L.off[SEC_INSTS]) : nullptr;
     S.obj_v = ni ? (const float4 *)(base + L.off[SEC_OBJV]) : nullptr;
@@ -1258,9 +1326,21 @@ int pm_commit(void *ptr) {
     if ((rc = finish_lights(c->hs, c->bbox_lo, c->bbox_hi, c->world_sphere, err))) FAIL(c, rc, "%s", err.c_str());
 
     bool built = false;
+    c->textured = scene_textured(c->hs);
+    std::vector<float4> tri_uv; /* textured scenes: SceneDev::tri_uv */
     if (c->hs.insts.empty() && !opt.bvh8 && gpu_bvh_wanted(opt, (int64_t)prims.size())) {
         if ((rc = commit_gpu_bvh(c, prims, opt, c->L, built))) return rc;
         if (opt.times && built) fprintf(stderr, "pm_commit: device build, total %.1f ms\n", since(t_commit0));
+        if (built && c->textured) {
+            /* the device chose the storage order: without instances a triangle's
+             * global id (SEC_TID, per storage slot) is its index */
+            std::vector<uint32_t> order((size_t)c->L.n_tris);
+            HIPCHK(c, hipMemcpy(order.data(), c->d_scene.as<char>() + c->L.off[SEC_TID], order.size() * sizeof(uint32_t),
+                                hipMemcpyDeviceToHost));
+            for (uint32_t t : order)
+                if (t >= c->hs.tris.size()) FAIL(c, PM_ERR_INVALID, "device build: triangle id %u out of range", t);
+            tri_uv = triangle_uvs(c->hs, order.data(), (int64_t)order.size());
+        }
     }
     if (!built) {
         SceneBlob blob;
@@ -1273,8 +1353,15 @@ int pm_commit(void *ptr) {
         c->L = blob.layout;
         c->bvh_depth = blob.bvh_depth;
         if (blob.layout.wide) { c->bvh4_nodes = blob.bvh4_nodes; c->bvh4_depth = blob.bvh4_depth; }
+        tri_uv.swap(blob.tri_uv);
     }
     if ((rc = upload(c, c->d_light_tris, c->hs.light_tris))) return rc;
+    if (c->textured) {
+        if ((rc = upload(c, c->d_tex_recs, c->hs.textures))) return rc;
+        if ((rc = upload(c, c->d_texels, c->hs.texels))) return rc;
+        if ((rc = upload(c, c->d_mat_tex, material_textures(c->hs)))) return rc;
+        if ((rc = upload(c, c->d_tri_uv, tri_uv))) return rc;
+    }
     fill_scene_dev(c);
 
     if ((rc = light_summary(c->hs, c->lsum, err))) FAIL(c, rc, "%s", err.c_str());
@@ -1299,6 +1386,7 @@ int pm_eye_pass(void *ptr, const pm_render_params *p, void *stream) {
     E.rays = c->d_rays.as<float>(); E.rand2d = c->d_rand2d.as<float>();
     E.eps = p->scene_epsilon; E.r2init = p->initial_radius2; E.max_spec = p->max_specular_depth;
     E.light_seed = p->light_rng_seed;
+    E.kd = c->textured ? c->d_rkd.as<float4>() : nullptr;
     timer_begin(c, "eye", s);
     HIPCHK(c, launch_eye(E, s));
     timer_end(c, "eye", s);
@@ -2261,6 +2349,34 @@ int pm_upload_records(void *ptr, const pm_record *in, int64_t n) {
     return PM_OK;
 }
 
+int pm_download_record_albedo(void *ptr, float *out_rgb, int64_t n) {
+    GETCTX(ptr);
+    if (!out_rgb) FAIL(c, PM_ERR_INVALID, "pm_download_record_albedo: null pointer");
+    if (!c->committed || !c->textured) FAIL(c, PM_ERR_INVALID, "pm_download_record_albedo: the committed scene has no textured material");
+    if (n < 0 || n > c->nrec || !c->d_rkd.p) FAIL(c, PM_ERR_INVALID, "bad record range");
+    if (int rc = materialize_reset(c, c->stream)) return rc; /* as pm_download_records does */
+    HIPCHK(c, hipDeviceSynchronize());
+    std::vector<float4> kd((size_t)n);
+    HIPCHK(c, hipMemcpy(kd.data(), c->d_rkd.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) { out_rgb[3 * i] = kd[i].x; out_rgb[3 * i + 1] = kd[i].y; out_rgb[3 * i + 2] = kd[i].z; }
+    return PM_OK;
+}
+
+int pm_upload_record_albedo(void *ptr, const float *in_rgb, int64_t n) {
+    GETCTX(ptr);
+    if (!in_rgb) FAIL(c, PM_ERR_INVALID, "pm_upload_record_albedo: null pointer");
+    if (!c->committed || !c->textured) FAIL(c, PM_ERR_INVALID, "pm_upload_record_albedo: the committed scene has no textured material");
+    /* no record changes: the tile list and the grid plan stay (ensure_records would drop them) */
+    if (n != c->nrec || !c->d_rkd.p || (size_t)n * sizeof(float4) > c->d_rkd.bytes)
+        FAIL(c, PM_ERR_INVALID, "pm_upload_record_albedo: %lld values for %lld records (run pm_eye_pass or pm_upload_records first)",
+             (long long)n, (long long)c->nrec);
+    std::vector<float4> kd((size_t)n);
+    for (int64_t i = 0; i < n; ++i) kd[i] = f4(in_rgb[3 * i], in_rgb[3 * i + 1], in_rgb[3 * i + 2], 0.f);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(c->d_rkd.p, kd.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    return PM_OK;
+}
+
 int64_t pm_kdtree_nodes(void *ptr) {
     Ctx *c = (Ctx *)ptr;
     return c ? c->kd_count : -1;
@@ -2343,6 +2459,8 @@ int pm_scene_section(void *ptr, int section, void *out, int64_t max_bytes, int64
     case PM_SCENE_OBJ_TRIS: src = S.obj_v; n = (int64_t)L.size[SEC_OBJV]; break;
     case PM_SCENE_LIGHT_TRIS: src = S.light_tris; n = (int64_t)(c->hs.light_tris.size() * sizeof(LightTri)); break;
     case PM_SCENE_LIGHT_CDF: src = c->d_light_cdf.p; n = (int64_t)(c->lsum.cdf.size() * sizeof(float)); break;
+    case PM_SCENE_TEXTURES: src = S.tex_recs; n = c->textured ? (int64_t)(c->hs.textures.size() * sizeof(TexRec)) : 0; break;
+    case PM_SCENE_MAT_TEX: src = S.mat_tex; n = c->textured ? (int64_t)(c->hs.materials.size() * sizeof(int)) : 0; break;
     case PM_SCENE_WORLD_SPHERE: /* a host value */
         if (bytes) *bytes = (int64_t)sizeof c->world_sphere;
         if (out) {

@@ -119,7 +119,18 @@ struct SceneDev {
      * light's cdf diverges, so it is read with plain vector loads (L2 / TCP
      * keep the small read-only table) */
     const LightTri *light_tris;
-    /* all arrays above but light_tris are 16-B aligned sections of one blob in HBM */
+    /* textures (pm_texture.h), buffers of their own in HBM like light_tris, so
+     * a small scene stays LDS-resident whatever its images' size: the records,
+     * the texels (float4: rgb, 0) of every image, per material the index of
+     * its Kd texture (-1: none), and per triangle storage slot its corners'
+     * uvs, 2 float4 (uv0, uv1) (uv2, 0, 0). All null unless the committed
+     * scene has a textured material: that selects the TEX instantiations of
+     * the trace, eye and simple kernels; the others never read them */
+    const TexRec *tex_recs;
+    const float4 *texels;
+    const int *mat_tex;
+    const float4 *tri_uv;
+    /* all arrays above but light_tris and the textures' are 16-B aligned sections of one blob in HBM */
     const char *blob;
     uint32_t blob_bytes;
     uint32_t lds_bytes; /* = blob_bytes when the blob fits LDS_SCENE_MAX (LDS-resident mode), else 0 */
@@ -1484,3 +1495,5 @@ PMD void rec_to_pixel(int64_t r, int W, int *px, int *py) {
 }
 
 } // namespace pm
+
+#include "pm_texture.h"

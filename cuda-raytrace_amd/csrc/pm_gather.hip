@@ -2742,9 +2742,11 @@ __global__ __launch_bounds__(256) void k_final(FinalParams P) {
         if (P.knn) { /* LPhoton: Lr * rho / pi with Lr's 1/nPaths = 1/emitted (passes averaged) */
             const float4 m = P.materials[__float_as_int(P.R.nrm[r].w)];
             const v3 fv = __float_as_int(m.w) == PM_MATTE ? xyz(m) * INV_PI : mk(0.f, 0.f, 0.f);
-            IDL = (xyz(st) / P.emitted) * fv;
+            if (P.kd) IDL = (xyz(st) / P.emitted) * (fv * xyz(P.kd[r])); /* the texel, factored out of the gather */
+            else IDL = (xyz(st) / P.emitted) * fv;
         } else if (N != 0) {
-            IDL = xyz(st) * INV_PI / (st.w * P.emitted);
+            if (P.kd) IDL = (xyz(P.kd[r]) * xyz(st)) * INV_PI / (st.w * P.emitted);
+            else IDL = xyz(st) * INV_PI / (st.w * P.emitted);
         }
         out = xyz(dl) + IDL;
         float y = 0.212671f * out.x + 0.715160f * out.y + 0.072169f * out.z;

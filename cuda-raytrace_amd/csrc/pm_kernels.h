@@ -85,6 +85,11 @@ struct EyeParams {
      * itself is the pinhole's */
     int camera;
     CameraDev cam;
+    /* textured scenes (S.tex_recs != null) only: per record the factor
+     * pm_final applies to its indirect term (float4, SoA like R's arrays):
+     * the texel of a textured matte hit, (1, 1, 1) on any other surface,
+     * 0 for an inactive record. Null otherwise, and never read then */
+    float4 *kd;
 };
 
 /* the jitter and lens randoms of sample q (pm_api.h pm_set_camera) */
@@ -287,6 +292,10 @@ struct FinalParams {
     int raster;     /* 1: out indexed by pixel (pinhole), 0: by record - rec_begin */
     int W;
     const uint32_t *view; /* non-null: [rec_begin, rec_begin + rec_count) index the active-record view */
+    /* non-null (a textured scene): the records' albedo factors (EyeParams::kd).
+     * A textured matte's Kd is 1 in the materials table, so every gather sums
+     * with f = 1 / pi, and the texel multiplies the indirect term here */
+    const float4 *kd;
 };
 
 /* traversal mode of a scene: LDS-resident blob (brute force when tiny) or HBM */

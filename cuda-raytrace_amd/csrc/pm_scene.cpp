@@ -402,6 +402,7 @@ int assemble_scene(const HostScene &hs, std::vector<BuildPrim> &prims, const Bui
             tri_id[k] = hs.tris[tri_order[k]].gid;
         }
     });
+    if (scene_textured(hs)) out.tri_uv = triangle_uvs(hs, tri_order.data(), nst);
     if (ptimes) fprintf(stderr, "pm_commit: triangle records done at %.1f ms\n", tms(t0, tnow()));
     const std::vector<float4> norms = vertex_normals(hs);
 
@@ -580,6 +581,173 @@ int finish_lights(HostScene &hs, const float blo[3], const float bhi[3], float s
     return PM_OK;
 }
 
+/* --------------------------------------------------------------- textures */
+namespace {
+
+bool finite_n(const float *v, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+/* operand k of a checkerboard or scale: a constant rgb, or a copy of the
+ * TEX_SINGLE record `tex` names */
+int resolve_operand(const HostScene &hs, const char *who, int k, int tex, const float *rgb, TexOperand &o, std::string &err) {
+    if (tex < 0) {
+        o = TexOperand{};
+        o.rgb[0] = rgb[0]; o.rgb[1] = rgb[1]; o.rgb[2] = rgb[2];
+        o.texel0 = -1;
+        return PM_OK;
+    }
+    if (tex >= (int)hs.textures.size()) return fail(err, "%s: tex%d = %d is out of range (%zu textures)", who, k, tex, hs.textures.size());
+    if (hs.textures[(size_t)tex].kind != TEX_SINGLE)
+        return fail(err, "%s: tex%d = %d is a checkerboard or a scale; an operand is an image or a constant", who, k, tex);
+    o = hs.textures[(size_t)tex].op[0];
+    return PM_OK;
+}
+
+} // namespace
+
+int check_texture_image(const float *rgb, int w, int h, int wrap, const float *mapping, const float *scale, std::string &err) {
+    if (!rgb || !mapping || !scale) return fail(err, "pm_add_texture_image: null pointer");
+    if (w <= 0 || h <= 0) return fail(err, "pm_add_texture_image: image size %d x %d", w, h);
+    /* 16 B per stored texel; texel offsets are ints */
+    if ((int64_t)w > (INT64_MAX / 16) / (int64_t)h || (int64_t)w * (int64_t)h >= ((int64_t)1 << 31))
+        return fail(err, "pm_add_texture_image: %d x %d texels are too many", w, h);
+    if (wrap != TEX_WRAP_REPEAT && wrap != TEX_WRAP_BLACK && wrap != TEX_WRAP_CLAMP)
+        return fail(err, "pm_add_texture_image: unknown wrap mode %d", wrap);
+    if (!finite_n(mapping, 4) || !finite_n(scale, 3)) return fail(err, "pm_add_texture_image: a mapping or scale value is not finite");
+    const int64_t n = 3 * (int64_t)w * (int64_t)h;
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(rgb[i])) return fail(err, "pm_add_texture_image: texel value %lld is not finite", (long long)i);
+    return PM_OK;
+}
+
+int check_texture_operands(const char *who, const float *mapping, bool need_mapping, int tex1, const float *rgb1, int tex2,
+                           const float *rgb2, std::string &err) {
+    if (need_mapping && !mapping) return fail(err, "%s: null pointer", who);
+    if ((tex1 < 0 && !rgb1) || (tex2 < 0 && !rgb2)) return fail(err, "%s: null pointer", who);
+    if (need_mapping && !finite_n(mapping, 4)) return fail(err, "%s: a mapping value is not finite", who);
+    if ((tex1 < 0 && !finite_n(rgb1, 3)) || (tex2 < 0 && !finite_n(rgb2, 3))) return fail(err, "%s: a colour is not finite", who);
+    return PM_OK;
+}
+
+int add_texture_image(HostScene &hs, const float *rgb, int w, int h, int wrap, const float *mapping, const float *scale,
+                      int *out_tex, std::string &err) {
+    if (!out_tex) return fail(err, "pm_add_texture_image: null pointer");
+    if (int rc = check_texture_image(rgb, w, h, wrap, mapping, scale, err)) return rc;
+    const size_t n = (size_t)w * (size_t)h;
+    if (hs.texels.size() + n >= ((size_t)1 << 31)) return fail(err, "pm_add_texture_image: too many texels in the scene");
+    TexRec T{};
+    T.kind = TEX_SINGLE;
+    TexOperand &o = T.op[0];
+    for (int a = 0; a < 3; ++a) o.rgb[a] = scale[a];
+    o.texel0 = (int)hs.texels.size();
+    o.w = w; o.h = h; o.wrap = wrap;
+    for (int a = 0; a < 4; ++a) o.map[a] = mapping[a];
+    T.op[1].texel0 = -1;
+    hs.texels.reserve(hs.texels.size() + n);
+    for (size_t i = 0; i < n; ++i) hs.texels.push_back(f4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.f));
+    hs.textures.push_back(T);
+    *out_tex = (int)hs.textures.size() - 1;
+    return PM_OK;
+}
+
+int add_texture_checker(HostScene &hs, const float *mapping, int tex1, const float *rgb1, int tex2, const float *rgb2,
+                        int *out_tex, std::string &err) {
+    const char *who = "pm_add_texture_checker";
+    if (!out_tex) return fail(err, "%s: null pointer", who);
+    if (int rc = check_texture_operands(who, mapping, true, tex1, rgb1, tex2, rgb2, err)) return rc;
+    TexRec T{};
+    T.kind = TEX_CHECKER;
+    for (int a = 0; a < 4; ++a) T.map[a] = mapping[a];
+    if (int rc = resolve_operand(hs, who, 1, tex1, rgb1, T.op[0], err)) return rc;
+    if (int rc = resolve_operand(hs, who, 2, tex2, rgb2, T.op[1], err)) return rc;
+    hs.textures.push_back(T);
+    *out_tex = (int)hs.textures.size() - 1;
+    return PM_OK;
+}
+
+int add_texture_scale(HostScene &hs, int tex1, const float *rgb1, int tex2, const float *rgb2, int *out_tex, std::string &err) {
+    const char *who = "pm_add_texture_scale";
+    if (!out_tex) return fail(err, "%s: null pointer", who);
+    if (int rc = check_texture_operands(who, nullptr, false, tex1, rgb1, tex2, rgb2, err)) return rc;
+    TexRec T{};
+    T.kind = TEX_SCALE;
+    if (int rc = resolve_operand(hs, who, 1, tex1, rgb1, T.op[0], err)) return rc;
+    if (int rc = resolve_operand(hs, who, 2, tex2, rgb2, T.op[1], err)) return rc;
+    hs.textures.push_back(T);
+    *out_tex = (int)hs.textures.size() - 1;
+    return PM_OK;
+}
+
+int check_material_textured(int type, std::string &err) {
+    if (type != PM_MATTE) return fail(err, "pm_add_material_textured: only PM_MATTE takes a Kd texture (type %d)", type);
+    return PM_OK;
+}
+
+int add_material_textured(HostScene &hs, int type, int kd_tex, int *out_id, std::string &err) {
+    if (int rc = check_material_textured(type, err)) return rc;
+    if (!out_id) return fail(err, "pm_add_material_textured: null pointer");
+    if (kd_tex < 0 || kd_tex >= (int)hs.textures.size())
+        return fail(err, "pm_add_material_textured: texture id %d is out of range (%zu textures)", kd_tex, hs.textures.size());
+    hs.materials.push_back(f4(1.f, 1.f, 1.f, ibits(PM_MATTE)));
+    hs.mat_tex.resize(hs.materials.size(), -1);
+    hs.mat_tex.back() = kd_tex;
+    *out_id = (int)hs.materials.size() - 1;
+    return PM_OK;
+}
+
+bool scene_textured(const HostScene &hs) {
+    for (size_t m = 0; m < hs.mat_tex.size() && m < hs.materials.size(); ++m)
+        if (hs.mat_tex[m] >= 0) return true;
+    return false;
+}
+
+std::vector<int> material_textures(const HostScene &hs) {
+    std::vector<int> t(hs.materials.size(), -1);
+    for (size_t m = 0; m < t.size() && m < hs.mat_tex.size(); ++m) t[m] = hs.mat_tex[m];
+    return t;
+}
+
+std::vector<float4> triangle_uvs(const HostScene &hs, const uint32_t *tri_order, int64_t n) {
+    std::vector<float4> uv(2 * (size_t)n);
+    for (int64_t k = 0; k < n; ++k) {
+        const HTri &tr = hs.tris[tri_order[k]];
+        float c[6] = {0.f, 0.f, 1.f, 0.f, 0.f, 1.f}; /* tri_frame's default corners */
+        if (hs.meshes[tr.mesh].has_uv)
+            for (int q = 0; q < 3; ++q) { c[2 * q] = hs.UV[2 * (size_t)tr.v[q]]; c[2 * q + 1] = hs.UV[2 * (size_t)tr.v[q] + 1]; }
+        uv[2 * k] = f4(c[0], c[1], c[2], c[3]);
+        uv[2 * k + 1] = f4(c[4], c[5], 0.f, 0.f);
+    }
+    return uv;
+}
+
+double texture_bound(const HostScene &hs, int t, bool *negative) {
+    const TexRec &T = hs.textures[(size_t)t];
+    bool neg = false;
+    auto operand = [&](const TexOperand &o) {
+        double c = 0.0;
+        for (int a = 0; a < 3; ++a) { c = std::max(c, std::fabs((double)o.rgb[a])); neg = neg || o.rgb[a] < 0.f; }
+        if (o.texel0 < 0) return c;
+        /* the bilinear blend stays between its texels (f in [0, 1)), black adds 0 */
+        double m = 0.0;
+        const size_t n = (size_t)o.w * (size_t)o.h;
+        for (size_t i = 0; i < n; ++i) {
+            const float4 &x = hs.texels[(size_t)o.texel0 + i];
+            m = std::max({m, std::fabs((double)x.x), std::fabs((double)x.y), std::fabs((double)x.z)});
+            neg = neg || x.x < 0.f || x.y < 0.f || x.z < 0.f;
+        }
+        return m * c;
+    };
+    const double a = operand(T.op[0]);
+    double r = a;
+    if (T.kind == TEX_CHECKER) r = std::max(a, operand(T.op[1]));
+    else if (T.kind == TEX_SCALE) r = a * operand(T.op[1]);
+    if (negative) *negative = neg;
+    return r * (1.0 + 1e-6); /* the blend's and the products' rounding */
+}
+
 /* --------------------------------------------------------- light summary */
 int light_selection_cdf(const int *types, const float *le_rgb, const float *areas, int n, float *cdf_out, std::string &err) {
     if (!types || !le_rgb || !areas || !cdf_out) return fail(err, "pm_light_selection_cdf: null pointer");
@@ -663,6 +831,15 @@ int light_summary(const HostScene &hs, LightSummary &out, std::string &err) {
     for (const LightDev &L : hs.lights) nn = nn && L.le.x >= 0.f && L.le.y >= 0.f && L.le.z >= 0.f && L.n_area.w >= 0.f;
     for (const float4 &m : hs.materials)
         if (fbits_h(m.w) == PM_MATTE) nn = nn && m.x >= 0.f && m.y >= 0.f && m.z >= 0.f;
+    /* a textured matte's Kd is its texture, not the table's (1, 1, 1): the
+     * largest value the texture can return bounds it, and a negative texel,
+     * scale or colour ends the non-negative guarantee */
+    for (size_t m = 0; m < hs.mat_tex.size() && m < hs.materials.size(); ++m) {
+        if (hs.mat_tex[m] < 0) continue;
+        bool neg = false;
+        out.kd_max = std::max(out.kd_max, texture_bound(hs, hs.mat_tex[m], &neg));
+        nn = nn && !neg;
+    }
     out.scene_nonneg = nn;
     return PM_OK;
 }

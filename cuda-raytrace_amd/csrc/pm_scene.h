@@ -51,6 +51,12 @@ struct HostScene {
     std::vector<float> sphere_o2w;
     std::vector<LightDev> lights;
     std::vector<LightTri> light_tris; /* the mesh lights' emitting triangles, light after light (SceneDev::light_tris) */
+    /* textures (pm_add_texture_*): the records, every image's texels (rgb, 0),
+     * and per material its Kd texture (-1: none; may be shorter than
+     * materials, the missing entries meaning none) */
+    std::vector<TexRec> textures;
+    std::vector<float4> texels;
+    std::vector<int> mat_tex;
 };
 
 /* Everything below that can fail returns PM_OK or an error code with its
@@ -140,6 +146,7 @@ struct SceneBlob {
     int64_t bvh4_nodes = 0; /* nodes of the wide tree (0: binary traversal) */
     int bvh4_depth = 0;
     int64_t obj_tris_stored = 0; /* object triangles in the blob (each mesh once) */
+    std::vector<float4> tri_uv;  /* textured scenes: SceneDev::tri_uv in storage order (triangle_uvs); else empty */
 };
 /* The blob with every tree built on the host. prims: scene_boxes' (the
  * builder reorders them); t0: the commit's start, for the PM_COMMIT_TIMES lines. */
@@ -161,6 +168,35 @@ void world_sphere(const float blo[3], const float bhi[3], float sphere[4]);
 /* a commit's last word on the lights, before either builder copies them:
  * the world sphere, and every distant light's record filled from it */
 int finish_lights(HostScene &hs, const float blo[3], const float bhi[3], float sphere[4], std::string &err);
+
+/* --------------------------------------------------------------- textures */
+/* The pm_add_texture_* calls of pm_api.h. The check_* functions look at the
+ * arguments alone (pm_api.cpp runs them before it touches the context); the
+ * add_* ones repeat them, resolve operand ids against the scene and append
+ * the record. An operand id names a TEX_SINGLE record (an image or a
+ * constant); a checkerboard or a scale as an operand is refused. */
+int check_texture_image(const float *rgb, int w, int h, int wrap, const float *mapping, const float *scale, std::string &err);
+int check_texture_operands(const char *who, const float *mapping, bool need_mapping, int tex1, const float *rgb1, int tex2,
+                           const float *rgb2, std::string &err);
+int add_texture_image(HostScene &hs, const float *rgb, int w, int h, int wrap, const float *mapping, const float *scale,
+                      int *out_tex, std::string &err);
+int add_texture_checker(HostScene &hs, const float *mapping, int tex1, const float *rgb1, int tex2, const float *rgb2,
+                        int *out_tex, std::string &err);
+int add_texture_scale(HostScene &hs, int tex1, const float *rgb1, int tex2, const float *rgb2, int *out_tex, std::string &err);
+/* a matte whose Kd is texture kd_tex: (1, 1, 1) in the materials table (the
+ * gathers sum with f = 1 / pi; pm_final applies the texel), kd_tex in mat_tex */
+int check_material_textured(int type, std::string &err);
+int add_material_textured(HostScene &hs, int type, int kd_tex, int *out_id, std::string &err);
+/* does a material of the scene carry a texture? */
+bool scene_textured(const HostScene &hs);
+/* SceneDev::mat_tex: one entry per material */
+std::vector<int> material_textures(const HostScene &hs);
+/* SceneDev::tri_uv: per storage slot k the uvs of triangle tri_order[k]'s
+ * corners, (uv0, uv1) (uv2, 0, 0); tri_frame's default corners for a mesh
+ * without uvs, so a surface's frame and its texture coordinates agree */
+std::vector<float4> triangle_uvs(const HostScene &hs, const uint32_t *tri_order, int64_t n);
+/* the largest |component| texture t can return, and whether one can be negative */
+double texture_bound(const HostScene &hs, int t, bool *negative);
 
 /* --------------------------------------------------------- light summary */
 /* pm_light_selection_cdf (pm_api.h) */

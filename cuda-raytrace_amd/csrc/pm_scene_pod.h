@@ -56,6 +56,28 @@ struct LightTri {
 };
 static_assert(sizeof(LightDev) == 80 && sizeof(LightTri) == 64, "light records as the kernels load them");
 
+/* Textures of a matte Kd (pm_add_texture_*, pm_api.h). One operand is a
+ * constant rgb (texel0 < 0) or an image: w x h float4 texels (rgb, 0) from
+ * texel0 of SceneDev::texels, row 0 at v = 0, its own UVMapping2D map =
+ * (su, sv, du, dv), a wrap mode, and rgb = the image's scale. */
+enum : int { TEX_SINGLE = 0, TEX_CHECKER = 1, TEX_SCALE = 2 };
+enum : int { TEX_WRAP_REPEAT = 0, TEX_WRAP_BLACK = 1, TEX_WRAP_CLAMP = 2 };
+struct TexOperand {    /* 48 B */
+    float rgb[3];
+    int texel0;
+    int w, h, wrap, pad;
+    float map[4];
+};
+/* kind TEX_SINGLE: op[0]; TEX_CHECKER: op[0] / op[1] picked through map (the
+ * checkerboard's own mapping); TEX_SCALE: op[0] * op[1]. No nesting: an
+ * operand is never a checkerboard or a scale, so there is no evaluation stack */
+struct TexRec {        /* 128 B */
+    int kind, pad[3];
+    float map[4];
+    TexOperand op[2];
+};
+static_assert(sizeof(TexOperand) == 48 && sizeof(TexRec) == 128, "texture records as the kernels load them");
+
 /* Scenes up to this size are copied into each block's LDS and traversed from
  * there (Cornell C2: ~4 KB); larger ones are traversed from HBM/L2. */
 constexpr uint32_t LDS_SCENE_MAX = 16384;

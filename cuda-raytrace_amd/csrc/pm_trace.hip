@@ -23,7 +23,11 @@ namespace pm {
 /* CAM: the rays of pm_set_camera (camera_ray, pm_kernels.h) over the sample
  * raster P.W x P.H; uniform per launch, so the pinhole / host-ray
  * instantiations (CAM = false) carry none of it */
-template <int MODE, bool CAM = false>
+/* TEX: the committed scene has a textured material (SceneDev::tex_recs): the
+ * direct light's f takes Kd from the texture at the hit, and the record's
+ * albedo factor goes to P.kd (pm_kernels.h EyeParams::kd). The other
+ * instantiations hold none of it. */
+template <int MODE, bool CAM = false, bool TEX = false>
 __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
     extern __shared__ __attribute__((aligned(16))) int stk[]; /* [stack_depth x EYE_BLOCK][scene blob (LDS)] */
     int *stack = stk + threadIdx.x;
@@ -42,6 +46,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
         if (px >= P.W || py >= P.H) {
             P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float(PM_REC_INVALID));
             P.R.nrm[r] = zero4; P.R.state[r] = zero4; P.R.n[r] = 0.f; P.R.dl[r] = zero4;
+            if (TEX) P.kd[r] = zero4;
             return;
         }
         pixel = (int64_t)py * P.W + px; /* the sample index q: keys the light samples below */
@@ -53,6 +58,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
         if (px >= P.W || py >= P.H) {
             P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float(PM_REC_INVALID));
             P.R.nrm[r] = zero4; P.R.state[r] = zero4; P.R.n[r] = 0.f; P.R.dl[r] = zero4;
+            if (TEX) P.kd[r] = zero4;
             return;
         }
         pixel = (int64_t)py * P.W + px;
@@ -93,9 +99,18 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
     if (flags) {
         P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float((int)flags));
         P.R.nrm[r] = zero4; P.R.state[r] = zero4; P.R.n[r] = 0.f; P.R.dl[r] = zero4;
+        if (TEX) P.kd[r] = zero4;
         return;
     }
     const v3 point = ray.o, ns = g.ns, dir = ray.d;
+    /* the factor pm_final applies to the record's indirect term: the texel of
+     * a textured matte (whose table Kd is 1), else 1 */
+    v3 kdf = mk(1.f, 1.f, 1.f);
+    bool textured = false;
+    if (TEX) { /* looked up for every hit, whatever the light guard below decides */
+        textured = fbits(S.materials[g.material].w) == PM_MATTE && S.mat_tex[g.material] >= 0;
+        if (textured) kdf = hit_kd<MODE == MODE_INST>(S, h, point, g.material, kdf);
+    }
 
     /* directLight (raytracing.cu:49-84) */
     v3 L = mk(0.f, 0.f, 0.f);
@@ -103,7 +118,9 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
     if (g.light < total) {
         if (g.light >= 0) L = L + light_le(S.lights[g.light], -dir, g.ng);
         float4 m = S.materials[g.material];
-        v3 fv = fbits(m.w) == PM_MATTE ? xyz(m) * INV_PI : mk(0.f, 0.f, 0.f);
+        v3 kd = xyz(m);
+        if (TEX && textured) kd = kdf;
+        v3 fv = fbits(m.w) == PM_MATTE ? kd * INV_PI : mk(0.f, 0.f, 0.f);
         for (int i = 0; i < total; ++i) {
             const LightDev Lt = S.lights[i];
             const int nS = fbits(Lt.p1_ns.w);
@@ -140,27 +157,29 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
     P.R.state[r] = make_float4(0.f, 0.f, 0.f, P.r2init);
     P.R.n[r] = 0.f;
     P.R.dl[r] = make_float4(L.x, L.y, L.z, 0.f);
+    if (TEX) P.kd[r] = make_float4(kdf.x, kdf.y, kdf.z, 0.f);
+}
+
+template <bool CAM, bool TEX>
+static void launch_eye_mode(const EyeParams &p, unsigned grid, size_t lds, hipStream_t s) {
+    switch (scene_mode(p.S)) {
+    case MODE_BRUTE: pm_launch((k_eye<MODE_BRUTE, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    case MODE_LDS: pm_launch((k_eye<MODE_LDS, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    case MODE_INST: pm_launch((k_eye<MODE_INST, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    default: pm_launch((k_eye<MODE_GLOBAL, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    }
 }
 
 hipError_t launch_eye(const EyeParams &p, hipStream_t s) {
     if (p.R.count <= 0) return hipSuccess;
     unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
     const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
-    if (p.camera) {
-        switch (scene_mode(p.S)) {
-        case MODE_BRUTE: pm_launch(k_eye<MODE_BRUTE, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-        case MODE_LDS: pm_launch(k_eye<MODE_LDS, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-        case MODE_INST: pm_launch(k_eye<MODE_INST, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-        default: pm_launch(k_eye<MODE_GLOBAL, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-        }
-        return hipGetLastError();
-    }
-    switch (scene_mode(p.S)) {
-    case MODE_BRUTE: pm_launch(k_eye<MODE_BRUTE>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_LDS: pm_launch(k_eye<MODE_LDS>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_INST: pm_launch(k_eye<MODE_INST>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    default: pm_launch(k_eye<MODE_GLOBAL>, dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    }
+    if (p.S.tex_recs) { /* a textured scene: the TEX instantiations, which write the records' albedo */
+        if (!p.kd) return hipErrorInvalidValue;
+        if (p.camera) launch_eye_mode<true, true>(p, grid, lds, s);
+        else launch_eye_mode<false, true>(p, grid, lds, s);
+    } else if (p.camera) launch_eye_mode<true, false>(p, grid, lds, s);
+    else launch_eye_mode<false, false>(p, grid, lds, s);
     return hipGetLastError();
 }
 
@@ -173,7 +192,7 @@ hipError_t launch_eye(const EyeParams &p, hipStream_t s) {
  * a miss is black (:75-79). The host's NaN / negative / infinite check
  * (simplerender.cpp:70-87) is fused into the store. Output: raster order
  * (pinhole) or sample order (host rays), float3 per sample. */
-template <int MODE, bool CAM = false>
+template <int MODE, bool CAM = false, bool TEX = false>
 __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
     extern __shared__ __attribute__((aligned(16))) int stk[];
     int *stack = stk + threadIdx.x;
@@ -217,7 +236,9 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
         const Geo g = shade<MODE == MODE_INST>(S, ray, h);
         const v3 point = ray.o + ray.d * h.t;
         const float4 m = S.materials[g.material];
-        const v3 fv = fbits(m.w) == PM_MATTE ? xyz(m) * INV_PI : mk(0.f, 0.f, 0.f); /* f(wo, wi) */
+        v3 kd = xyz(m);
+        if (TEX && fbits(m.w) == PM_MATTE) kd = hit_kd<MODE == MODE_INST>(S, h, point, g.material, kd);
+        const v3 fv = fbits(m.w) == PM_MATTE ? kd * INV_PI : mk(0.f, 0.f, 0.f); /* f(wo, wi) */
         for (int i = 0; i < S.n_lights; ++i) {
             const LightDev Lt = S.lights[i];
             float u1 = 0.f, u2 = 0.f;
@@ -249,25 +270,25 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
     out[3 * pixel + 2] = L.z;
 }
 
+template <bool CAM, bool TEX>
+static void launch_simple_mode(const EyeParams &p, float *out, unsigned grid, size_t lds, hipStream_t s) {
+    switch (scene_mode(p.S)) {
+    case MODE_BRUTE: pm_launch((k_simple<MODE_BRUTE, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
+    case MODE_LDS: pm_launch((k_simple<MODE_LDS, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
+    case MODE_INST: pm_launch((k_simple<MODE_INST, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
+    default: pm_launch((k_simple<MODE_GLOBAL, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
+    }
+}
+
 hipError_t launch_simple(const EyeParams &p, float *out, hipStream_t s) {
     if (p.R.count <= 0) return hipSuccess;
     unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
     const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
-    if (p.camera) {
-        switch (scene_mode(p.S)) {
-        case MODE_BRUTE: pm_launch(k_simple<MODE_BRUTE, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-        case MODE_LDS: pm_launch(k_simple<MODE_LDS, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-        case MODE_INST: pm_launch(k_simple<MODE_INST, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-        default: pm_launch(k_simple<MODE_GLOBAL, true>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-        }
-        return hipGetLastError();
-    }
-    switch (scene_mode(p.S)) {
-    case MODE_BRUTE: pm_launch(k_simple<MODE_BRUTE>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-    case MODE_LDS: pm_launch(k_simple<MODE_LDS>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-    case MODE_INST: pm_launch(k_simple<MODE_INST>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-    default: pm_launch(k_simple<MODE_GLOBAL>, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-    }
+    if (p.S.tex_recs) {
+        if (p.camera) launch_simple_mode<true, true>(p, out, grid, lds, s);
+        else launch_simple_mode<false, true>(p, out, grid, lds, s);
+    } else if (p.camera) launch_simple_mode<true, false>(p, out, grid, lds, s);
+    else launch_simple_mode<false, false>(p, out, grid, lds, s);
     return hipGetLastError();
 }
 
@@ -483,23 +504,25 @@ PMD bool emit_path(const TraceParams &P, const SceneDev &S, const uint32_t *perm
 
 /* one ray of a path: trace, then specular continuation or diffuse deposit +
  * Lambert bounce (photontracing.cu:119-183); false when the path ends */
-template <int HOLD, bool INST = false>
+template <int HOLD, bool INST = false, bool TEX = false>
 PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, const Hit &h, TProf &prof, Held &held);
 
-template <int MODE, int HOLD, class C>
+template <int MODE, int HOLD, bool TEX, class C>
 PMD bool path_step(const TraceParams &P, const SceneDev &S, int *stack, PathState &st, C &cen, TProf &prof,
                    Held &held) {
     Hit h;
     const bool hit = traverse<false, MODE>(S, st.ray, h, stack, TRACE_BLOCK, cen);
     prof.mark(1);
     if (!hit) return false;
-    return path_shade<HOLD, MODE == MODE_INST>(P, S, st, h, prof, held);
+    return path_shade<HOLD, MODE == MODE_INST, TEX>(P, S, st, h, prof, held);
 }
 
 /* the hit of a path's ray: specular continuation, or diffuse deposit +
  * Lambert bounce (photontracing.cu:119-183); false when the path ends.
- * HOLD: the deposit goes to `held` (written at path end, held_write) */
-template <int HOLD, bool INST>
+ * HOLD: the deposit goes to `held` (written at path end, held_write).
+ * TEX (a scene with a textured material): the Lambert bounce takes Kd from
+ * the texture at the hit, so a photon off a red texel carries red */
+template <int HOLD, bool INST, bool TEX>
 PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, const Hit &h, TProf &prof, Held &held) {
     const uint32_t mpc = (uint32_t)P.mpc;
     Geo g = shade<INST>(S, st.ray, h);
@@ -545,7 +568,9 @@ PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, cons
     pmdm_philox4x32_10(pm_index + st.nI, (uint32_t)P.pass, 0u, 0u, P.seed, 0u, o4);
     float u1 = pmdm_u01(o4[0]), u2 = pmdm_u01(o4[1]);
     v3 wiw; float bpdf;
-    v3 fr = sample_f(xyz(m), g, wo, u1, u2, &wiw, &bpdf);
+    v3 kd = xyz(m);
+    if (TEX) kd = hit_kd<INST>(S, h, hit_point, g.material, kd);
+    v3 fr = sample_f(kd, g, wo, u1, u2, &wiw, &bpdf);
     if (is_black(fr) || bpdf == 0.f) return false;
     v3 anew = st.alpha * fr * absdot(wiw, g.ns) / bpdf;
     st.alpha = anew;
@@ -583,7 +608,7 @@ PMD void finish_path(const TraceParams &P, PathState &st, const Held *held = nul
  * §5) and removed. HOLD: deposits held in LDS and written per path.
  * COUNT: census [rays traced, BVH nodes entered, primitive tests, photons
  * deposited], one atomic per wave (counting launches only, never timed). */
-template <int COUNT, int MODE, int HOLD, int ALL = 0>
+template <int COUNT, int MODE, int HOLD, int ALL = 0, bool TEX = false>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
     extern __shared__ __attribute__((aligned(16))) int stk[];
     __shared__ uint32_t perm[28];
@@ -608,7 +633,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
         prof.mark(0);
         while (alive) {
             ++rays;
-            alive = path_step<MODE, HOLD>(P, S, stack, st, cen, prof, held);
+            alive = path_step<MODE, HOLD, TEX>(P, S, stack, st, cen, prof, held);
             prof.mark(2);
         }
         if (COUNT) deposits += st.stored;
@@ -641,8 +666,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
 constexpr int POOL_STEPS = PM_POOL_STEPS, POOL_SHADE_MIN = PM_POOL_SHADE_MIN;
 enum { PHASE_DEAD = 0, PHASE_TRAV = 1, PHASE_SHADE = 2 };
 
-/* W8: the 8-wide tree (S.wide == 3, TravState8); ALL: emit_path's */
-template <int COUNT, int HOLD, int W8, int ALL>
+/* W8: the 8-wide tree (S.wide == 3, TravState8); ALL: emit_path's; TEX: path_shade's */
+template <int COUNT, int HOLD, int W8, int ALL, bool TEX>
 /* 5 waves/SIMD: 96 VGPRs (102 unconstrained -> 4 waves), no scratch; with
  * the LDS stacks capped at 31 entries (PM_POOL_STACK, the rest spilled) five
  * 256-thread blocks fit a CU. C3 trace (same box): 4.59-4.61 ms at 4 waves,
@@ -693,7 +718,7 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
         if (travm == 0ull || waiting >= POOL_SHADE_MIN) {
             if (phase == PHASE_SHADE) {
                 ++rays;
-                const bool alive = tr.best.ref != 0xffffffffu && path_shade<HOLD>(P, S, st, tr.best, prof, held);
+                const bool alive = tr.best.ref != 0xffffffffu && path_shade<HOLD, false, TEX>(P, S, st, tr.best, prof, held);
                 if (alive) {
                     trav_begin(st.ray, tr);
                     phase = PHASE_TRAV;
@@ -730,11 +755,11 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
     }
 }
 
-template <int COUNT, int HOLD, int ALL = 0>
-__global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool(TraceParams P) { trace_pool_body<COUNT, HOLD, 0, ALL>(P); }
-template <int COUNT, int HOLD, int ALL = 0>
+template <int COUNT, int HOLD, int ALL = 0, bool TEX = false>
+__global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool(TraceParams P) { trace_pool_body<COUNT, HOLD, 0, ALL, TEX>(P); }
+template <int COUNT, int HOLD, int ALL = 0, bool TEX = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
-void k_trace_pool8(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL>(P); }
+void k_trace_pool8(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, TEX>(P); }
 
 /* resident waves of the pooled kernel per CU at this LDS size (0 if unknown) */
 int trace_pool_waves_per_cu(size_t lds, int hold, int w8) { /* lds: the stacks */
@@ -779,44 +804,44 @@ static bool trace_hold(const TraceParams &p) {
     return p.hold && p.mpc == HOLD_MPC && ((uintptr_t)p.slots & 15u) == 0u;
 }
 
-template <int HOLD, int ALL>
+template <int HOLD, int ALL, bool TEX>
 static void launch_lane(const TraceParams &p, dim3 grid, size_t lds, int count, hipStream_t s) {
     switch (scene_mode(p.S)) {
     case MODE_BRUTE:
-        if (count) pm_launch((k_trace_lane<1, MODE_BRUTE, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_BRUTE, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((k_trace_lane<1, MODE_BRUTE, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((k_trace_lane<0, MODE_BRUTE, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     case MODE_LDS:
-        if (count) pm_launch((k_trace_lane<1, MODE_LDS, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_LDS, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((k_trace_lane<1, MODE_LDS, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((k_trace_lane<0, MODE_LDS, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     case MODE_INST: /* instances: the per-lane kernel (the pooled one walks only one level) */
-        if (count) pm_launch((k_trace_lane<1, MODE_INST, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_INST, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((k_trace_lane<1, MODE_INST, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((k_trace_lane<0, MODE_INST, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     default:
-        if (count) pm_launch((k_trace_lane<1, MODE_GLOBAL, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_GLOBAL, HOLD, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((k_trace_lane<1, MODE_GLOBAL, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((k_trace_lane<0, MODE_GLOBAL, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     }
 }
 
 /* the pooled kernels (4-wide: k_trace_pool; 8-wide: k_trace_pool8) */
-template <int ALL>
+template <int ALL, bool TEX>
 static void launch_pool(const TraceParams &p, dim3 grid, size_t lds, size_t lds_h, bool hold, int count, hipStream_t s) {
     if (p.S.wide == 3) {
-        if (count && hold) pm_launch((k_trace_pool8<1, 1, ALL>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-        else if (count) pm_launch((k_trace_pool8<1, 0, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else if (hold) pm_launch((k_trace_pool8<0, 1, ALL>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-        else pm_launch((k_trace_pool8<0, 0, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
-    } else if (count && hold) pm_launch((k_trace_pool<1, 1, ALL>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-    else if (count) pm_launch((k_trace_pool<1, 0, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
-    else if (hold) pm_launch((k_trace_pool<0, 1, ALL>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-    else pm_launch((k_trace_pool<0, 0, ALL>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count && hold) pm_launch((k_trace_pool8<1, 1, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+        else if (count) pm_launch((k_trace_pool8<1, 0, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else if (hold) pm_launch((k_trace_pool8<0, 1, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+        else pm_launch((k_trace_pool8<0, 0, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+    } else if (count && hold) pm_launch((k_trace_pool<1, 1, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+    else if (count) pm_launch((k_trace_pool<1, 0, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+    else if (hold) pm_launch((k_trace_pool<0, 1, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+    else pm_launch((k_trace_pool<0, 0, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
 }
 
-hipError_t launch_trace(const TraceParams &p, int count, hipStream_t s) {
-    if (p.path_count <= 0) return hipSuccess;
+template <bool TEX>
+static hipError_t launch_trace_tex(const TraceParams &p, int count, hipStream_t s) {
     /* PM_ALL_LIGHTS: the ALL instantiations; a fixed light is an index into S.lights */
     const bool all = p.light_index == PM_ALL_LIGHTS;
     if (all ? !p.light_cdf : p.light_index < 0 || p.light_index >= p.S.n_lights) return hipErrorInvalidValue;
@@ -828,8 +853,8 @@ hipError_t launch_trace(const TraceParams &p, int count, hipStream_t s) {
         const unsigned grid = (unsigned)((waves + TRACE_BLOCK / 64 - 1) / (TRACE_BLOCK / 64));
         const bool hold = trace_hold(p);
         const size_t lds_h = lds + (hold ? (size_t)HOLD_WORDS * TRACE_BLOCK * 4 : 0);
-        if (all) launch_pool<1>(p, dim3(grid), lds, lds_h, hold, count, s);
-        else launch_pool<0>(p, dim3(grid), lds, lds_h, hold, count, s);
+        if (all) launch_pool<1, TEX>(p, dim3(grid), lds, lds_h, hold, count, s);
+        else launch_pool<0, TEX>(p, dim3(grid), lds, lds_h, hold, count, s);
         return hipGetLastError();
     }
     /* one path per lane */
@@ -837,11 +862,18 @@ hipError_t launch_trace(const TraceParams &p, int count, hipStream_t s) {
     const unsigned grid = (unsigned)((p.path_count + TRACE_BLOCK - 1) / TRACE_BLOCK);
     const size_t lds_h = lds + ((size_t)p.S.lds_bytes + 15u) / 16u * 16u - p.S.lds_bytes + (size_t)HOLD_WORDS * TRACE_BLOCK * 4;
     if (trace_hold(p)) {
-        if (all) launch_lane<1, 1>(p, dim3(grid), lds_h, count, s);
-        else launch_lane<1, 0>(p, dim3(grid), lds_h, count, s);
-    } else if (all) launch_lane<0, 1>(p, dim3(grid), lds, count, s);
-    else launch_lane<0, 0>(p, dim3(grid), lds, count, s);
+        if (all) launch_lane<1, 1, TEX>(p, dim3(grid), lds_h, count, s);
+        else launch_lane<1, 0, TEX>(p, dim3(grid), lds_h, count, s);
+    } else if (all) launch_lane<0, 1, TEX>(p, dim3(grid), lds, count, s);
+    else launch_lane<0, 0, TEX>(p, dim3(grid), lds, count, s);
     return hipGetLastError();
+}
+
+/* a scene with a textured material (SceneDev::tex_recs) runs the TEX
+ * instantiations; every other scene the kernels it ran before textures existed */
+hipError_t launch_trace(const TraceParams &p, int count, hipStream_t s) {
+    if (p.path_count <= 0) return hipSuccess;
+    return p.S.tex_recs ? launch_trace_tex<true>(p, count, s) : launch_trace_tex<false>(p, count, s);
 }
 
 } // namespace pm

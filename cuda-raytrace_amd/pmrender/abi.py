@@ -15,6 +15,11 @@ PM_LIGHT_POINT, PM_LIGHT_AREA_DISK = 1, 3
 PM_LIGHT_AREA_MESH = 4  # ours: an emitting triangle mesh (pm_add_light_mesh)
 PM_LIGHT_DISTANT = 6  # ours: pbrt-v2's distant light (pm_add_light_distant); 5 is kept for a spot light
 PM_SCENE_WORLD_SPHERE = 10  # pm_scene_section: centre xyz, radius of the last commit's world sphere
+PM_SCENE_TEXTURES, PM_SCENE_MAT_TEX = 11, 12  # pm_scene_section: the texture records, per material its Kd texture
+# wrap modes of an image texture (pm_add_texture_image)
+PM_TEX_WRAP_REPEAT, PM_TEX_WRAP_BLACK, PM_TEX_WRAP_CLAMP = 0, 1, 2
+TEX_WRAPS = {"repeat": PM_TEX_WRAP_REPEAT, "black": PM_TEX_WRAP_BLACK, "clamp": PM_TEX_WRAP_CLAMP}
+TEX_SINGLE, TEX_CHECKER, TEX_SCALE = 0, 1, 2  # TexRec::kind
 PM_REC_EXCEPTION, PM_REC_MISS, PM_REC_INVALID, PM_REC_BACKFACE = 0x1, 0x2, 0x4, 0x8
 PM_REC_INACTIVE = PM_REC_EXCEPTION | PM_REC_MISS | PM_REC_INVALID
 PM_GATHER_GRID, PM_GATHER_KDTREE = 0, 1
@@ -40,6 +45,12 @@ assert RECORD_DTYPE.itemsize == 64
 # one emitting triangle of a mesh light (PM_SCENE_LIGHT_TRIS; pm_device.h LightTri), 64 B
 LIGHT_TRI_DTYPE = np.dtype([("p0", "<f4", 3), ("cdf", "<f4"), ("e1", "<f4", 4), ("e2", "<f4", 4), ("n", "<f4", 4)])
 assert LIGHT_TRI_DTYPE.itemsize == 64
+# one texture record (PM_SCENE_TEXTURES; pm_scene_pod.h TexRec), 128 B: an operand is a constant rgb
+# (texel0 < 0) or an image (rgb = its scale, texel0 = its first texel, w, h, wrap, its mapping)
+TEX_OPERAND_DTYPE = np.dtype([("rgb", "<f4", 3), ("texel0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("wrap", "<i4"),
+                              ("pad", "<i4"), ("map", "<f4", 4)])
+TEX_REC_DTYPE = np.dtype([("kind", "<i4"), ("pad", "<i4", 3), ("map", "<f4", 4), ("op", TEX_OPERAND_DTYPE, 2)])
+assert TEX_OPERAND_DTYPE.itemsize == 48 and TEX_REC_DTYPE.itemsize == 128
 
 
 class PMConfig(ctypes.Structure):

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .abi import (LIGHT_TRI_DTYPE, PM_SCENE_WORLD_SPHERE, PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PM_FILM_TABLE, PM_FILTER_NONE, Camera,
+from .abi import (LIGHT_TRI_DTYPE, PM_SCENE_MAT_TEX, PM_SCENE_TEXTURES, PM_SCENE_WORLD_SPHERE, TEX_REC_DTYPE, TEX_WRAPS, PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PM_FILM_TABLE, PM_FILTER_NONE, Camera,
                   Filter, PMConfig, RenderParams, Stats, f32, fptr, iptr, record_pixels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,6 +46,12 @@ def load_library(path=None):
         "pm_last_error": (ctypes.c_char_p, [vp]),
         "pm_version": (ctypes.c_char_p, []),
         "pm_add_material": (c_int, [vp, c_int, P_f, P_i]),
+        "pm_add_texture_image": (c_int, [vp, P_f, c_int, c_int, c_int, P_f, P_f, P_i]),
+        "pm_add_texture_checker": (c_int, [vp, P_f, c_int, P_f, c_int, P_f, P_i]),
+        "pm_add_texture_scale": (c_int, [vp, c_int, P_f, c_int, P_f, P_i]),
+        "pm_add_material_textured": (c_int, [vp, c_int, c_int, P_i]),
+        "pm_download_record_albedo": (c_int, [vp, P_f, i64]),
+        "pm_upload_record_albedo": (c_int, [vp, P_f, i64]),
         "pm_add_trimesh": (c_int, [vp, P_f, c_int, P_i, c_int, P_f, P_f, c_int, c_int]),
         "pm_add_object_mesh": (c_int, [vp, P_f, c_int, P_i, c_int, P_f, P_f, c_int, c_int, P_i]),
         "pm_add_mesh_instance": (c_int, [vp, c_int, P_f, P_f]),
@@ -209,6 +215,53 @@ class Context:
         out = ctypes.c_int()
         self._chk(self.lib.pm_add_material(self.h, int(mtype), fptr(f32(rgb, 3)), ctypes.byref(out)))
         return out.value
+
+    # textures (pm_add_texture_*): an operand is a texture id (int) or an rgb
+    @staticmethod
+    def _operand(op):
+        if isinstance(op, (int, np.integer)):
+            return int(op), None
+        return -1, f32(op, 3)
+
+    def add_texture_image(self, image, wrap="repeat", mapping=(1.0, 1.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0)):
+        """An image texture: image is (h, w, 3) float RGB, row 0 at v = 0; wrap a name of TEX_WRAPS or a
+        PM_TEX_WRAP_* value; mapping = (su, sv, du, dv). Returns the texture id."""
+        img = np.ascontiguousarray(np.asarray(image, dtype=np.float32))
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"expected an (h, w, 3) image, got shape {img.shape}")
+        out = ctypes.c_int()
+        w = TEX_WRAPS[wrap] if isinstance(wrap, str) else int(wrap)
+        self._chk(self.lib.pm_add_texture_image(self.h, fptr(img), img.shape[1], img.shape[0], w, fptr(f32(mapping, 4)),
+                                                fptr(f32(scale, 3)), ctypes.byref(out)))
+        return out.value
+
+    def add_texture_checker(self, tex1, tex2, mapping=(1.0, 1.0, 0.0, 0.0)):
+        (t1, c1), (t2, c2) = self._operand(tex1), self._operand(tex2)
+        out = ctypes.c_int()
+        self._chk(self.lib.pm_add_texture_checker(self.h, fptr(f32(mapping, 4)), t1, fptr(c1), t2, fptr(c2), ctypes.byref(out)))
+        return out.value
+
+    def add_texture_scale(self, tex1, tex2):
+        (t1, c1), (t2, c2) = self._operand(tex1), self._operand(tex2)
+        out = ctypes.c_int()
+        self._chk(self.lib.pm_add_texture_scale(self.h, t1, fptr(c1), t2, fptr(c2), ctypes.byref(out)))
+        return out.value
+
+    def add_material_textured(self, mtype, kd_tex):
+        out = ctypes.c_int()
+        self._chk(self.lib.pm_add_material_textured(self.h, int(mtype), int(kd_tex), ctypes.byref(out)))
+        return out.value
+
+    def record_albedo(self):
+        """(n_records, 3): the factor pm_final applies to each record's indirect term
+        (pm_download_record_albedo; textured scenes only)."""
+        out = np.zeros((self.num_records(), 3), np.float32)
+        self._chk(self.lib.pm_download_record_albedo(self.h, fptr(out), len(out)))
+        return out
+
+    def upload_record_albedo(self, rgb):
+        rgb = f32(rgb, 3 * self.num_records())
+        self._chk(self.lib.pm_upload_record_albedo(self.h, fptr(rgb), rgb.size // 3))
 
     def add_trimesh(self, P, idx, N=None, uv=None, material=0, light=-1):
         P = f32(P)
@@ -496,10 +549,13 @@ class Context:
                       "tri_id": (3, np.uint32), "tri_info": (4, np.int32), "bvh4": (5, np.uint32),
                       "instances": (6, np.float32), "obj_tris": (7, np.float32),
                       "light_tris": (8, LIGHT_TRI_DTYPE), "light_cdf": (9, np.float32)}
+    # textured scenes (empty otherwise): the texture records and per material its Kd texture; buffers of
+    # their own, kept apart from the sections every scene has
+    TEXTURE_SECTIONS = {"textures": (PM_SCENE_TEXTURES, TEX_REC_DTYPE), "mat_tex": (PM_SCENE_MAT_TEX, np.int32)}
 
     def scene_section(self, name):
         """One section of the committed scene blob as the kernels read it (pm_scene_section)."""
-        sec, dt = self.SCENE_SECTIONS[name]
+        sec, dt = self.SCENE_SECTIONS[name] if name in self.SCENE_SECTIONS else self.TEXTURE_SECTIONS[name]
         n = ctypes.c_int64()
         self._chk(self.lib.pm_scene_section(self.h, sec, None, 0, ctypes.byref(n)))
         out = np.zeros(n.value // np.dtype(dt).itemsize, dtype=dt)

@@ -33,6 +33,12 @@ RED = (0.63, 0.065, 0.05)
 GREEN = (0.14, 0.45, 0.091)
 
 
+@dataclass(frozen=True)
+class Tex:
+    """Handle of a texture of a Scene (Scene.texture_*): index into Scene.textures."""
+    index: int
+
+
 @dataclass
 class Scene:
     materials: list = field(default_factory=list)   # (type, rgb)
@@ -45,10 +51,46 @@ class Scene:
     objects: list = field(default_factory=list)     # object meshes (as meshes), placed by `instances` only
     instances: list = field(default_factory=list)   # (object index, o2w 4x4, w2o 4x4), affine
     camera: tuple = None                            # ("pinhole", eye, fwd, right, up, W, H) | ("rays", rays, rand2d, n2d)
+    # ("image", (h, w, 3) array, wrap, mapping, scale) | ("checker", op1, op2, mapping) | ("scale", op1, op2);
+    # an operand is a Tex (an image) or an rgb
+    textures: list = field(default_factory=list)
 
     def material(self, mtype, rgb):
-        self.materials.append((mtype, np.asarray(rgb, np.float32)))
+        """rgb: a colour, or a Tex handle for the Kd of a PM_MATTE (pm_add_material_textured)."""
+        self.materials.append((mtype, rgb if isinstance(rgb, Tex) else np.asarray(rgb, np.float32)))
         return len(self.materials) - 1
+
+    def texture_image(self, array, wrap="repeat", mapping=(1.0, 1.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0)):
+        """An image texture from an (h, w, 3) array, row 0 at v = 0 (pm_add_texture_image)."""
+        self.textures.append(("image", np.asarray(array, np.float32), wrap, np.asarray(mapping, np.float32),
+                              np.asarray(scale, np.float32)))
+        return Tex(len(self.textures) - 1)
+
+    @staticmethod
+    def _operand(op):
+        return op if isinstance(op, Tex) else np.asarray(op, np.float32)
+
+    def texture_checker(self, tex1, tex2, mapping=(1.0, 1.0, 0.0, 0.0)):
+        """pbrt-v2's 2-D checkerboard, aamode none: even squares tex1, odd tex2 (an rgb or an image Tex)."""
+        self.textures.append(("checker", self._operand(tex1), self._operand(tex2), np.asarray(mapping, np.float32)))
+        return Tex(len(self.textures) - 1)
+
+    def texture_scale(self, tex1, tex2):
+        self.textures.append(("scale", self._operand(tex1), self._operand(tex2)))
+        return Tex(len(self.textures) - 1)
+
+    def _load_textures(self, api):
+        """The textures through `api`; returns the api's id per Scene texture."""
+        ids = []
+        op = lambda o: ids[o.index] if isinstance(o, Tex) else o
+        for t in self.textures:
+            if t[0] == "image":
+                ids.append(api.add_texture_image(t[1], t[2], t[3], t[4]))
+            elif t[0] == "checker":
+                ids.append(api.add_texture_checker(op(t[1]), op(t[2]), t[3]))
+            else:
+                ids.append(api.add_texture_scale(op(t[1]), op(t[2])))
+        return ids
 
     def add_mesh_light(self, P, idx, Le, nsamples=1, reverse_orientation=False, material=None):
         """A triangle-mesh area light (pm_add_light_mesh) and its visible mesh; returns the light index.
@@ -68,14 +110,18 @@ class Scene:
         self.lights.append(("distant", w, np.asarray(L, np.float32)))
         return len(self.lights) - 1
 
-    def add_quads(self, quads, material, light=-1):
+    def add_quads(self, quads, material, light=-1, uvs=None):
+        """uvs: per quad the (u, v) of its four corners (None: the mesh has no uvs)."""
         P, idx = [], []
         for q in quads:
             b = len(P)
             P.extend(q)
             idx.append((b, b + 1, b + 2))
             idx.append((b, b + 2, b + 3))
-        self.meshes.append(dict(P=np.asarray(P, np.float32), idx=np.asarray(idx, np.int32), N=None, uv=None,
+        uv = None if uvs is None else np.asarray(uvs, np.float32).reshape(-1, 2)
+        if uv is not None and len(uv) != len(P):
+            raise ValueError(f"{len(quads)} quads need {len(P)} uvs, got {len(uv)}")
+        self.meshes.append(dict(P=np.asarray(P, np.float32), idx=np.asarray(idx, np.int32), N=None, uv=uv,
                                 material=material, light=light))
 
     @property
@@ -111,8 +157,15 @@ class Scene:
         if any(L[0] == "distant" for L in self.lights) and not hasattr(api, "add_light_distant"):
             raise NotImplementedError(f"{type(api).__name__} has no distant lights (pm_add_light_distant); "
                                       "only point and disk lights exist there, as in the reference")
+        if self.textures and not hasattr(api, "add_texture_image"):
+            raise NotImplementedError(f"{type(api).__name__} has no textures (pm_add_texture_*); every material "
+                                      "is one constant colour there, as in the reference")
+        tex_ids = self._load_textures(api) if self.textures else []
         for mtype, rgb in self.materials:
-            api.add_material(mtype, rgb)
+            if isinstance(rgb, Tex):
+                api.add_material_textured(mtype, tex_ids[rgb.index])
+            else:
+                api.add_material(mtype, rgb)
         for m in self.meshes:
             api.add_trimesh(m["P"], m["idx"], m.get("N"), m.get("uv"), m["material"], m["light"])
         if self.instances and instancing and hasattr(api, "add_mesh_instance"):
@@ -272,6 +325,66 @@ def cornell_sun(W=256, H=256, blocks=True, nsamples=1):
     through the open front, slightly downwards (scenes/cornell-sun.pbrt)."""
     s = cornell_box(W, H, blocks=blocks, nsamples=nsamples)
     s.add_distant_light((0.0, 120.0, -400.0), (0.0, 0.0, 0.0), (3.0, 2.7, 2.1))
+    return s
+
+
+FLOOR = [(552.8, 0, 0), (0, 0, 0), (0, 0, 559.2), (549.6, 0, 559.2)]
+CEILING = [(556.0, 548.8, 0), (556.0, 548.8, 559.2), (0, 548.8, 559.2), (0, 548.8, 0)]
+BACK = [(549.6, 0, 559.2), (0, 0, 559.2), (0, 548.8, 559.2), (556.0, 548.8, 559.2)]
+QUAD_UV = [(0.0, 0.0), (1.0, 0.0), (1.0, 1.0), (0.0, 1.0)]  # the corners of a quad, in its vertex order
+
+
+def procedural_image(w=8, h=8):
+    """A small smooth RGB image built in code (no file): two ramps and a ripple, in [0.1, 0.9]."""
+    x, y = np.meshgrid((np.arange(w) + 0.5) / w, (np.arange(h) + 0.5) / h)
+    img = np.stack([0.1 + 0.8 * x, 0.1 + 0.8 * y, 0.5 + 0.4 * np.sin(6.0 * x) * np.cos(5.0 * y)], -1)
+    return img.astype(np.float32)
+
+
+def cornell_textured(W=256, H=256, blocks=True, nsamples=1):
+    """The Cornell box with a checkerboard floor (8 x 8 squares, white and a
+    dark blue-grey) and procedural_image() on the back wall; every other
+    surface as cornell_box."""
+    s = Scene()
+    white = s.material(PM_MATTE, WHITE)
+    red = s.material(PM_MATTE, RED)
+    green = s.material(PM_MATTE, GREEN)
+    checker = s.material(PM_MATTE, s.texture_checker(WHITE, (0.15, 0.17, 0.25), mapping=(8.0, 8.0, 0.0, 0.0)))
+    picture = s.material(PM_MATTE, s.texture_image(procedural_image(), wrap="clamp"))
+    s.add_quads([FLOOR], checker, uvs=[QUAD_UV])
+    s.add_quads([CEILING], white)
+    s.add_quads([BACK], picture, uvs=[QUAD_UV])
+    s.add_quads([[(0, 0, 559.2), (0, 0, 0), (0, 548.8, 0), (0, 548.8, 559.2)]], green)
+    s.add_quads([[(552.8, 0, 0), (549.6, 0, 559.2), (556.0, 548.8, 559.2), (556.0, 548.8, 0)]], red)
+    if blocks:
+        box = cornell_box(W, H, blocks=True)
+        for m in box.meshes[3:]:  # the two blocks, white
+            s.meshes.append(dict(m, material=white))
+    _ceiling_light(s, nsamples=nsamples)
+    s.camera = pinhole(W, H)
+    return s
+
+
+CHECKER_DARK = (0.15, 0.17, 0.25)
+
+
+def cornell_checker(W=256, H=256, blocks=True, nsamples=1):
+    """The Cornell box with a checkerboard floor, 8 x 8 squares of the wall white and a dark blue-grey
+    (scenes/cornell-checker.pbrt): the floor is a mesh of its own with uvs, then ceiling and back wall."""
+    s = Scene()
+    checker = s.material(PM_MATTE, s.texture_checker(WHITE, CHECKER_DARK, mapping=(8.0, 8.0, 0.0, 0.0)))
+    white = s.material(PM_MATTE, WHITE)
+    green = s.material(PM_MATTE, GREEN)
+    red = s.material(PM_MATTE, RED)
+    s.add_quads([FLOOR], checker, uvs=[QUAD_UV])
+    s.add_quads([CEILING, BACK], white)
+    s.add_quads([[(0, 0, 559.2), (0, 0, 0), (0, 548.8, 0), (0, 548.8, 559.2)]], green)
+    s.add_quads([[(552.8, 0, 0), (549.6, 0, 559.2), (556.0, 548.8, 559.2), (556.0, 548.8, 0)]], red)
+    if blocks:
+        for m in cornell_box(W, H, blocks=True).meshes[3:]:
+            s.meshes.append(dict(m, material=white))
+    _ceiling_light(s, nsamples=nsamples)
+    s.camera = pinhole(W, H)
     return s
 
 

@@ -106,7 +106,10 @@ typedef struct pm_photon {
  * device keeps it as SoA. Under PM_ESTIMATOR_KNN,
  * flux accumulates the per-pass sums, radius2 holds the last pass's r_k^2
  * (pbrt's shrunk maxDistSquared) and photon_count its number of photons
- * found. */
+ * found. In a scene with textures, the flux of a record on a textured matte
+ * is the sum with Kd = 1: the gathers run with f = 1 / pi for it, and
+ * pm_final multiplies its indirect term by the record's albedo factor
+ * (pm_download_record_albedo). dl already contains the texel. */
 typedef struct pm_record {
     float pos[3];
     uint32_t flags;
@@ -176,6 +179,45 @@ const char *pm_version(void);
 /* returns material id in *out_id. rgb = Kd (matte) / Kr (mirror, ignored by
  * the device as in cudamaterial.cu.h:101-105) / unused (glass). */
 int pm_add_material(void *ctx, int type, const float rgb[3], int *out_id);
+/* Textures for the Kd of a PM_MATTE (ours: the reference evaluates a texture
+ * once, at a default point).
+ * Surface (u, v) of a triangle hit (flattened or instanced mesh): b0 uv0 +
+ * b1 uv1 + b2 uv2 from the hit's barycentrics, summed left to right in fp32; a
+ * mesh without uvs has the corners (0,0) (1,0) (0,1) its shading frame uses.
+ * A disk: pbrt-v2's u = phi / phiMax, v = 1 - (r - r_i) / (R - r_i). A (full)
+ * sphere: pbrt-v2's u = phi / 2 pi, v = (theta - pi) / (0 - pi), theta =
+ * acos(z / r) evaluated as atan2(sqrt(x^2 + y^2), z) in object space.
+ *   image: w x h float RGB texels, row 0 at v = 0, a UVMapping2D mapping =
+ *     (su, sv, du, dv): s = su u + du, t = sv v + dv,
+ *     a wrap mode and an rgb scale. Level 0 only (pbrt-v2's
+ *     MIPMap::triangle(0, s, t)), in fp32 without contraction:
+ *       x = s w - 0.5, y = t h - 0.5 (each held to [-1e9, 1e9]),
+ *       x0 = floorf(x), fx = x - x0, likewise y; the texels (x0, y0),
+ *       (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) through the wrap mode
+ *       (repeat: pbrt's Mod; clamp; black: 0 outside); blended as
+ *       a + f (b - a) along x on both rows, then along y; times scale.
+ *     Four equal texels return that texel (times scale) bit for bit.
+ *   checker: pbrt-v2's Checkerboard2DTexture, dimension 2, aamode "none", with
+ *     its own mapping: ((int)floorf(s) + (int)floorf(t)) % 2 == 0 picks
+ *     operand 1, else operand 2.
+ *   scale: operand 1 times operand 2 per channel.
+ * An operand is rgbN when texN < 0, else the image (or constant) texture
+ * texN; a checker or scale as an operand is refused, so nothing nests.
+ * pm_add_material_textured makes a matte whose Kd is kd_tex; the photon
+ * bounce, the direct light and pm_render_simple look the texel up at the hit.
+ * PM_ERR_INVALID: a null pointer; w or h <= 0 or too many texels; a texel,
+ * mapping, scale or colour value that is not finite; an unknown wrap mode; an
+ * operand or texture id that is out of range or not an image; type !=
+ * PM_MATTE. What needs no context is checked before the context is. */
+#define PM_TEX_WRAP_REPEAT 0
+#define PM_TEX_WRAP_BLACK 1
+#define PM_TEX_WRAP_CLAMP 2
+int pm_add_texture_image(void *ctx, const float *rgb, int w, int h, int wrap, const float mapping[4],
+                         const float scale[3], int *out_tex);
+int pm_add_texture_checker(void *ctx, const float mapping[4], int tex1, const float rgb1[3], int tex2,
+                           const float rgb2[3], int *out_tex);
+int pm_add_texture_scale(void *ctx, int tex1, const float rgb1[3], int tex2, const float rgb2[3], int *out_tex);
+int pm_add_material_textured(void *ctx, int type, int kd_tex, int *out_id);
 /* World-space mesh (pbrt TriangleMesh::p is already world space,
  * cudatrianglemesh.cpp:24-30). N and uv may be NULL. light_index = index of
  * the area light this shape emits for, -1 otherwise. */
@@ -448,7 +490,15 @@ int pm_set_slot_buffer(void *ctx, void *d_slots, int64_t n_slots);
 int pm_download_slots(void *ctx, pm_photon *out, int64_t n);
 int pm_upload_slots(void *ctx, const pm_photon *in, int64_t n);
 int pm_download_records(void *ctx, pm_record *out, int64_t n);
-int pm_upload_records(void *ctx, const pm_record *in, int64_t n);
+int pm_upload_records(void *ctx, const pm_record *in, int64_t n); /* leaves the albedo factors below as they are */
+/* Scenes with a textured material only (else PM_ERR_INVALID): per record the
+ * rgb factor pm_final applies to the indirect term, written by pm_eye_pass:
+ * the texel at a textured matte hit, (1, 1, 1) on any other surface (whose Kd
+ * the gather already applied), 0 for an inactive record. Final radiance:
+ * PPM dl + (factor flux) (1 / pi) / (radius2 emitted), kNN dl + flux / emitted
+ * (Kd / pi factor). Upload takes n = pm_num_records values. */
+int pm_download_record_albedo(void *ctx, float *out_rgb, int64_t n);
+int pm_upload_record_albedo(void *ctx, const float *in_rgb, int64_t n);
 /* kd-tree nodes of the last PM_GATHER_KDTREE build (reference layout) */
 int64_t pm_kdtree_nodes(void *ctx);
 int pm_download_kdtree(void *ctx, pm_photon *out, int64_t n);
@@ -492,6 +542,12 @@ int pm_scene_info(void *ctx, int64_t out[7]);
 /* 16 B, host values: the world sphere of the last pm_commit, centre x y z and
  * radius (float), as pm_add_light_distant states it */
 #define PM_SCENE_WORLD_SPHERE 10
+/* textured scenes (else empty): the texture records, 128 B each (pm_scene_pod.h
+ * TexRec: kind, the checkerboard's mapping, two operands of 48 B: rgb or
+ * scale, first texel or -1, w, h, wrap, 0, the image's mapping), and per
+ * material the int index of its Kd texture (-1: none) */
+#define PM_SCENE_TEXTURES 11
+#define PM_SCENE_MAT_TEX 12
 int pm_scene_section(void *ctx, int section, void *out, int64_t max_bytes, int64_t *bytes);
 /* the current photon map (pm_build_photon_map; the reference's
  * CreatePhotonMap, photonmappingrenderer.cpp:150-180): [0] structure
