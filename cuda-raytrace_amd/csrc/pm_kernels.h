@@ -1,6 +1,7 @@
 /*
  * pm_kernels.h — kernel parameter blocks and launcher declarations shared by
- * the host orchestration (pm_api.cpp) and the HIP kernels (pm_trace.hip, pm_bucket.hip, pm_gather.hip).
+ * the host orchestration (pm_api.cpp) and the HIP kernels (pm_trace.hip, pm_bucket.hip, pm_gather.hip,
+ * pm_gather_knn.hip, pm_records.hip).
  */
 #pragma once
 #include <hip/hip_ext.h>

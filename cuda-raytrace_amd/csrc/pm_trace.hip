@@ -5,7 +5,8 @@
  *                direct light with shadow rays   (raytracing.cu:19-147)
  *   k_trace      photon emission + bounce, <= max_photon_count deposits per
  *                path into owner-written slots   (photontracing.cu:80-185)
- * (photon buckets: pm_bucket.hip; gather/PPM/final: pm_gather.hip)
+ * (photon buckets: pm_bucket.hip; gathers: pm_gather.hip, pm_gather_knn.hip;
+ * PPM update of partials / final: pm_records.hip)
  */
 #include <hip/hip_runtime.h>
 
