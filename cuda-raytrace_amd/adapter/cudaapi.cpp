@@ -152,9 +152,13 @@ const pmcuda::Material *CudaRender::material(const Material *m) {
     } else if (const MirrorMaterial *mi = dynamic_cast<const MirrorMaterial *>(m)) {
         d.kind = pmcuda::Material::Mirror;
         d.k = toPm(mi->Kr->Evaluate(dg));
-    } else if (dynamic_cast<const GlassMaterial *>(m)) {
+        d.kr = d.k; /* the physical model's parameters (flush decides whether they are used) */
+    } else if (const GlassMaterial *gl = dynamic_cast<const GlassMaterial *>(m)) {
         d.kind = pmcuda::Material::Glass;
         d.k = pmcuda::RGB{1.f, 1.f, 1.f};
+        d.kr = toPm(gl->Kr->Evaluate(dg));
+        d.kt = toPm(gl->Kt->Evaluate(dg));
+        d.index = gl->index->Evaluate(dg);
     } else {
         d.kind = pmcuda::Material::Unknown;
     }
@@ -169,19 +173,32 @@ void CudaRender::createCudaShape(const std::string &name, Reference<Shape> &shap
         Warning("shape:%s not implemented yet", name.c_str()); /* cudarender.cpp:141-144 */
         return;
     }
+    /* kept until Render: pbrt hands over the Renderer's ParamSet (its "specular"
+     * key decides how mirrors and glass go in) after the shapes */
+    Pending p;
+    p.name = name; p.shape = d; p.key = currentInstance; p.material = material(kMaterial); p.light = lightIndex;
+    pending_.push_back(p);
+}
+
+/* the kept scene calls, in their order, once the specular model is known */
+void CudaRender::flush() {
+    for (auto &m : materials_)
+        if (m.second.kind == pmcuda::Material::Mirror || m.second.kind == pmcuda::Material::Glass) m.second.physical = physical_;
     try {
-        impl_.createCudaShape(name, d, currentInstance, material(kMaterial), lightIndex);
+        for (const Pending &p : pending_) {
+            if (p.instance) impl_.objectInstance(p.key, p.tr);
+            else impl_.createCudaShape(p.name, p.shape, p.key, p.material, p.light);
+        }
     } catch (const pmcuda::Error &e) {
         Severe("%s", e.what());
     }
+    pending_.clear();
 }
 
 void CudaRender::objectInstance(std::vector<Reference<Primitive> > *instance, const Transform &tr) {
-    try {
-        impl_.objectInstance(instance, toPm(tr));
-    } catch (const pmcuda::Error &e) {
-        Severe("%s", e.what());
-    }
+    Pending p;
+    p.instance = true; p.key = instance; p.tr = toPm(tr);
+    pending_.push_back(p);
 }
 
 void CudaRender::createSubRenderer(Sampler *sampler, Camera *camera, const ParamSet &params,
@@ -196,6 +213,12 @@ void CudaRender::createSubRenderer(Sampler *sampler, Camera *camera, const Param
     if (params.FindOneString("photonmap", "grid") == "kdtree") s.params.gather_structure = PM_GATHER_KDTREE;
     /* the light the photon paths start on; -1 (PM_ALL_LIGHTS): every light, picked per path by power */
     s.params.light_source_index = params.FindOneInt("lightsource", s.params.light_source_index);
+    /* "string specular" "pbrt": MirrorMaterial's Kr and GlassMaterial's Kr, Kt,
+     * index go into the physical model (pm_add_material_specular); "reference"
+     * (the default): the reference's mirror and glass */
+    const std::string spec = params.FindOneString("specular", "reference");
+    if (spec != "pbrt" && spec != "reference") Warning("Renderer \"specular\" \"%s\" unknown: using \"reference\"", spec.c_str());
+    physical_ = spec == "pbrt";
     /* the device camera + film (pm_set_camera): "integer devicecamera" [1]
      * hands the camera to the device (strata "integer xsamples" / "ysamples",
      * "integer jitter" [0|1], "integer sampleseed"; thin lens "float
@@ -256,6 +279,7 @@ struct PbrtFilm : pmcuda::Film {
 
 void CudaRender::Render(const Scene *scene) {
     if (!camera_ || !sampler_) Severe("CreateCudaRenderer must precede Render");
+    flush();
     /* lights (CudaLight::preLaunch, cudalight.cpp:105-120): point lights, and
      * the disks and triangle meshes of diffuse area lights, each with its 2D light samples
      * registered in sampler order (CudaSample::Add2D rounds the count) */

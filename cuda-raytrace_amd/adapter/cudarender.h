@@ -5,6 +5,9 @@
  * calls (createCudaShape, objectInstance, createSubRenderer) convert pbrt
  * objects into the plain descriptors of the host layer (pm_cudarender.h),
  * reading the members the reference reads.
+ * The converted shape and instance calls are kept until Render, because the
+ * ParamSet (createSubRenderer) comes after them and its "specular" key decides
+ * how mirror and glass materials go in.
  */
 #ifndef cudarender_h__
 #define cudarender_h__
@@ -54,6 +57,20 @@ public:
 
 private:
     const pmcuda::Material *material(const Material *m);
+    /* createCudaShape / objectInstance calls, converted and kept in order until
+     * Render: the ParamSet's "specular" key arrives after them */
+    struct Pending {
+        bool instance = false;
+        std::string name;
+        pmcuda::Shape shape;
+        const void *key = NULL;
+        const pmcuda::Material *material = NULL;
+        int light = -1;
+        pmcuda::Transform tr;
+    };
+    void flush();
+    std::vector<Pending> pending_;
+    bool physical_ = false; /* Renderer "cuda" "string specular" "pbrt" */
     pmcuda::CudaRender impl_;
     std::map<const Material *, pmcuda::Material> materials_; /* cudarender.h:74-76 */
     Sampler *sampler_;

@@ -150,9 +150,12 @@ int CudaRender::materialId(const Material *m) {
         rgb[0] = m->k.r; rgb[1] = m->k.g; rgb[2] = m->k.b;
     }
     int id = -1;
-    if (m && m->kind == Material::Matte && m->kd_tex)
+    if (m && m->kind == Material::Matte && m->kd_tex) {
         check(ctx_, pm_add_material_textured(ctx_, PM_MATTE, textureId(*m->kd_tex), &id), "pm_add_material_textured");
-    else
+    } else if (m && m->physical && (m->kind == Material::Mirror || m->kind == Material::Glass)) {
+        const float kr[3] = {m->kr.r, m->kr.g, m->kr.b}, kt[3] = {m->kt.r, m->kt.g, m->kt.b};
+        check(ctx_, pm_add_material_specular(ctx_, type, kr, kt, m->index, &id), "pm_add_material_specular");
+    } else
         check(ctx_, pm_add_material(ctx_, type, rgb, &id), "pm_add_material");
     materials_[m] = id;
     return id;

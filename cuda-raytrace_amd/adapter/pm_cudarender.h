@@ -85,6 +85,13 @@ struct Material {
     /* optional (Matte only): Kd is this texture, looked up per hit; k is then
      * what the reference would use (the texture at a default point) */
     std::shared_ptr<const TextureDesc> kd_tex;
+    /* Mirror / Glass: pbrt's parameters (mirror Kr; glass Kr, Kt, index),
+     * used when `physical` is set: the material then goes in through
+     * pm_add_material_specular (the Fresnel model of pm_api.h), else through
+     * pm_add_material as the reference's, which ignores them */
+    bool physical = false;
+    RGB kr = {1.f, 1.f, 1.f}, kt = {1.f, 1.f, 1.f};
+    float index = 1.5f;
 };
 
 /* what CudaShape::CreateCudaShape reads from a pbrt Shape:

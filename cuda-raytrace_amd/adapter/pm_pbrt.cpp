@@ -456,6 +456,9 @@ struct PbrtParser::Impl {
         return true;
     }
 
+    /* the specular model of the materials that follow: PbrtOptions::specular_override, else the Renderer's */
+    bool physical() const { return (opts->specular_override.empty() ? opts->specular : opts->specular_override) == "pbrt"; }
+
     const Material *make_material(Lexer &lx, int line, const std::string &type, const ParamSet &ps) {
         Material m;
         if (type == "matte") {
@@ -464,9 +467,25 @@ struct PbrtParser::Impl {
         } else if (type == "mirror") {
             m.kind = Material::Mirror;
             m.k = spectrum_tex(lx, line, ps, "Kr", RGB{0.9f, 0.9f, 0.9f});
+            m.physical = physical(); /* Renderer "string specular" "pbrt": Kr reflects (pm_add_material_specular) */
+            m.kr = m.k;
         } else if (type == "glass") {
-            m.kind = Material::Glass; /* Kr / Kt / index unused by the device (cudamaterial.cpp:69-75) */
+            /* the reference's glass reads none of Kr / Kt / index (cudamaterial.cpp:69-75);
+             * with Renderer "string specular" "pbrt" they are pbrt's, defaults 1, 1, 1.5 */
+            m.kind = Material::Glass;
             m.k = RGB{1.f, 1.f, 1.f};
+            m.physical = physical();
+            if (m.physical) {
+                m.kr = spectrum_tex(lx, line, ps, "Kr", RGB{1.f, 1.f, 1.f});
+                m.kt = spectrum_tex(lx, line, ps, "Kt", RGB{1.f, 1.f, 1.f});
+                const Param *ix = ps.find("index");
+                if (ix && ix->type == "texture")
+                    warn(lx, line, "texture \"%s\" for the glass index is not supported; using the default",
+                         ix->strs.empty() ? std::string() : ix->strs[0]);
+                else
+                    m.index = ps.oneFloat("index", 1.5f);
+                if (!(m.index > 0.f) || !std::isfinite(m.index)) lx.fail(line, "glass \"index\" %g: expected a finite value above 0", (double)m.index);
+            }
         } else {
             warn(lx, line, "material \"%s\" has no MI355X equivalent; using the fallback matte 0.5", type);
             m.kind = Material::Unknown; /* -> matte 0.5 in CudaRender::materialId */
@@ -661,6 +680,9 @@ struct PbrtParser::Impl {
                 pm_render_params &p = opts->settings.params;
                 p.paths_per_pass = ps.oneInt("paths", (int)p.paths_per_pass);
                 p.passes = ps.oneInt("passes", p.passes);
+                opts->specular = ps.oneString("specular", "reference");
+                if (opts->specular != "pbrt" && opts->specular != "reference")
+                    lx.fail(line, "Renderer \"specular\": \"%s\" is not \"pbrt\" or \"reference\"", opts->specular.c_str());
                 const std::string g = ps.oneString("gather", "grid");
                 p.gather_structure = g == "kdtree" || g == "kd" ? PM_GATHER_KDTREE : PM_GATHER_GRID;
                 /* the light the photon paths start on: "integer lightsource" [k],

@@ -33,7 +33,11 @@
  *                Film (xresolution, yresolution, filename), Renderer
  *                ("photonmapping" | "simple" | "cuda" + "string rendername";
  *                extension params "integer paths", "integer passes",
- *                "string gather" = "grid" | "kdtree")
+ *                "string gather" = "grid" | "kdtree", "string specular" =
+ *                "reference" | "pbrt": with "pbrt" Material "mirror" takes Kr
+ *                (0.9) and "glass" Kr, Kt, index (1, 1, 1.5) into the
+ *                physical model of pm_add_material_specular; a non-constant
+ *                texture on one of them warns and leaves the default)
  *                Camera "float lensradius" / "float focaldistance" (thin lens),
  *                Sampler "stratified" (xsamples, ysamples, jitter) or
  *                "lowdiscrepancy" | "bestcandidate" | "random" (pixelsamples N,
@@ -88,6 +92,11 @@ struct PbrtOptions {
     std::string renderer = "photonmapping";
     RenderSettings settings;     /* params from the Renderer directive */
     std::string film_filename = "pbrt.pfm";
+    /* Renderer "string specular": "reference" (the reference's mirror and
+     * glass) or "pbrt" (pm_add_material_specular with the materials' Kr, Kt,
+     * index). specular_override, when the caller sets it before parsing to
+     * either word, wins over the file (pm_render_cli --specular) */
+    std::string specular = "reference", specular_override;
     int warnings = 0;
 };
 

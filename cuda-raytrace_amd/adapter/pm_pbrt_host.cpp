@@ -19,6 +19,8 @@
  *        [--two-lights]  (scenes/cornell-two-lights.pbrt: the disk, then a blue quad light on the green wall)
  *        [--sun]         (scenes/cornell-sun.pbrt: a DistantLight through the open front, the last light)
  *        [--lightsource K]  (Renderer "cuda" "integer lightsource" [K]; -1: photons from every light)
+ *        [--caustic]     (scenes/caustic-fresnel.pbrt: a GlassMaterial sphere and a MirrorMaterial sphere instead of the blocks)
+ *        [--specular pbrt|reference]  (Renderer "cuda" "string specular": pbrt = the Fresnel model with the materials' Kr, Kt, index)
  * The header's third word is the number of light 2D samples per ray
  * (nsamples per area light).
  */
@@ -32,8 +34,11 @@
 #include "cudaapi.h"
 #include "lights/diffuse.h"
 #include "lights/distant.h"
+#include "materials/glass.h"
 #include "materials/matte.h"
+#include "materials/mirror.h"
 #include "shapes/disk.h"
+#include "shapes/sphere.h"
 #include "shapes/trianglemesh.h"
 
 namespace {
@@ -42,6 +47,8 @@ struct Opts {
     int W = 64, H = 48, paths = 16384, nsamples = 1;
     std::string photonmap = "grid", renderer = "photonmap", out;
     bool instanced = false, quad_light = false, two_lights = false, sun = false;
+    bool caustic = false; /* --caustic (scenes/caustic-fresnel.pbrt): a glass and a mirror sphere instead of the blocks */
+    std::string specular; /* --specular pbrt|reference: the Renderer "cuda" ParamSet's "string specular" */
     bool checker = false; /* --checker (scenes/cornell-checker.pbrt): the floor's Kd is a checkerboard */
     int lightsource = 0;
     bool lightsource_set = false;
@@ -179,6 +186,17 @@ int run(const Opts &o) {
     CreateCudaShape("trianglemesh", s, NULL, green.GetPtr(), -1);
     s = quads(&identity, {{552.8f, 0, 0, 549.6f, 0, 559.2f, 556.0f, 548.8f, 559.2f, 556.0f, 548.8f, 0}});
     CreateCudaShape("trianglemesh", s, NULL, red.GetPtr(), -1);
+    /* --caustic: Material "glass" Kr 1 Kt 1 index 1.5 on a sphere r 100 at (370, 100, 250),
+     * Material "mirror" Kr 0.9 on a sphere r 90 at (150, 90, 380) (pmrender/scenes.py caustic_fresnel) */
+    Reference<Material> glass(new GlassMaterial(constant(1.f, 1.f, 1.f), constant(1.f, 1.f, 1.f),
+                                                Reference<Texture<float> >(new ConstantTexture<float>(1.5f)), NULL));
+    Reference<Material> mirror(new MirrorMaterial(constant(0.9f, 0.9f, 0.9f), NULL));
+    float g[4][4] = {{1, 0, 0, 370.f}, {0, 1, 0, 100.f}, {0, 0, 1, 250.f}, {0, 0, 0, 1}};
+    float gi[4][4] = {{1, 0, 0, -370.f}, {0, 1, 0, -100.f}, {0, 0, 1, -250.f}, {0, 0, 0, 1}};
+    float r[4][4] = {{1, 0, 0, 150.f}, {0, 1, 0, 90.f}, {0, 0, 1, 380.f}, {0, 0, 0, 1}};
+    float ri[4][4] = {{1, 0, 0, -150.f}, {0, 1, 0, -90.f}, {0, 0, 1, -380.f}, {0, 0, 0, 1}};
+    static const Transform g2w{Matrix4x4(g), Matrix4x4(gi)}, w2g{Matrix4x4(gi), Matrix4x4(g)};
+    static const Transform r2w{Matrix4x4(r), Matrix4x4(ri)}, w2r{Matrix4x4(ri), Matrix4x4(r)};
     std::vector<Reference<Primitive> > blocks; /* RenderOptions::instances["blocks"] */
     std::vector<Reference<Primitive> > *inst = o.instanced ? &blocks : NULL;
     s = quads(&identity, {{130, 165, 65, 82, 165, 225, 240, 165, 272, 290, 165, 114},
@@ -186,14 +204,20 @@ int run(const Opts &o) {
                           {130, 0, 65, 130, 165, 65, 290, 165, 114, 290, 0, 114},
                           {82, 0, 225, 82, 165, 225, 130, 165, 65, 130, 0, 65},
                           {240, 0, 272, 240, 165, 272, 82, 165, 225, 82, 0, 225}});
-    CreateCudaShape("trianglemesh", s, inst, white.GetPtr(), -1);
+    if (!o.caustic) CreateCudaShape("trianglemesh", s, inst, white.GetPtr(), -1);
     s = quads(&identity, {{423, 330, 247, 265, 330, 296, 314, 330, 456, 472, 330, 406},
                           {423, 0, 247, 423, 330, 247, 472, 330, 406, 472, 0, 406},
                           {472, 0, 406, 472, 330, 406, 314, 330, 456, 314, 0, 456},
                           {314, 0, 456, 314, 330, 456, 265, 330, 296, 265, 0, 296},
                           {265, 0, 296, 265, 330, 296, 423, 330, 247, 423, 0, 247}});
-    CreateCudaShape("trianglemesh", s, inst, white.GetPtr(), -1);
-    if (o.instanced) CudaObjectInstance(&blocks, identity); /* ObjectInstance "blocks" */
+    if (!o.caustic) CreateCudaShape("trianglemesh", s, inst, white.GetPtr(), -1);
+    if (o.instanced && !o.caustic) CudaObjectInstance(&blocks, identity); /* ObjectInstance "blocks" */
+    if (o.caustic) {
+        s = Reference<Shape>(new Sphere(&g2w, &w2g, false, 100.f, -100.f, 100.f, 360.f));
+        CreateCudaShape("sphere", s, NULL, glass.GetPtr(), -1);
+        s = Reference<Shape>(new Sphere(&r2w, &w2r, false, 90.f, -90.f, 90.f, 360.f));
+        CreateCudaShape("sphere", s, NULL, mirror.GetPtr(), -1);
+    }
     /* AttributeBegin; Translate 278 548.7 279.5; Rotate 90 1 0 0;
      * AreaLightSource "diffuse" "rgb L" [17 17 17]; Shape "disk" "float radius" 65 */
     float m[4][4] = {{1, 0, 0, 278.f}, {0, 0, -1, 548.7f}, {0, 1, 0, 279.5f}, {0, 0, 0, 1}};
@@ -235,6 +259,7 @@ int run(const Opts &o) {
     params.AddInt("photonpaths", &o.paths, 1);
     params.AddString("photonmap", &o.photonmap, 1);
     if (o.lightsource_set) params.AddInt("lightsource", &o.lightsource, 1);
+    if (!o.specular.empty()) params.AddString("specular", &o.specular, 1);
     if (o.devicecamera) {
         params.AddInt("devicecamera", &o.devicecamera, 1);
         params.AddInt("xsamples", &o.xsamples, 1);
@@ -283,6 +308,8 @@ int main(int argc, char **argv) {
         else if (a == "--two-lights") o.two_lights = true;
         else if (a == "--sun") o.sun = true;
         else if (a == "--checker") o.checker = true;
+        else if (a == "--caustic") o.caustic = true;
+        else if (a == "--specular") o.specular = val();
         else if (a == "--lightsource") { o.lightsource = std::stoi(val()); o.lightsource_set = true; }
         else if (a == "--out") o.out = val();
         else if (a == "--devicecamera") o.devicecamera = 1;

@@ -194,6 +194,19 @@ struct DumpSink : PbrtSink {
             }
             out += "]}";
         }
+        if (m && m->physical && (m->kind == Material::Mirror || m->kind == Material::Glass)) {
+            /* Renderer "string specular" "pbrt": the parameters of pm_add_material_specular */
+            const float kr[3] = {m->kr.r, m->kr.g, m->kr.b}, kt[3] = {m->kt.r, m->kt.g, m->kt.b};
+            out += ", \"specular\": {\"kr\": ";
+            arr(out, kr, 3);
+            if (m->kind == Material::Glass) {
+                out += ", \"kt\": ";
+                arr(out, kt, 3);
+                out += ", \"index\": ";
+                arr(out, &m->index, 1);
+            }
+            out += "}";
+        }
         out += ", \"P\": "; arr(out, s.P.data(), s.P.size());
         out += ", \"N\": "; arr(out, s.N.data(), s.N.size());
         out += ", \"uv\": "; arr(out, s.uv.data(), s.uv.size());
@@ -301,9 +314,13 @@ void apply_camera_flags(const CameraFlags &f, Camera &c) {
     if (!c.device_camera) c.filter = pm_filter{PM_FILTER_NONE, 0.f, 0.f, 0.f, 0.f};
 }
 
+/* --specular pbrt|reference: overrides the file's Renderer "string specular" */
+std::string g_specular;
+
 int dump(const std::string &path, const CameraFlags &cflags) {
     DumpSink sink;
     PbrtOptions o;
+    o.specular_override = g_specular;
     PbrtParser parser;
     parser.parseFile(path, sink, o);
     apply_camera_flags(cflags, o.camera);
@@ -414,6 +431,7 @@ int render_pbrt(const std::string &path, std::string out, const std::string &ren
                 const std::string &structure, const std::string &light, const CameraFlags &cflags = CameraFlags()) {
     CudaRenderInit(0);
     PbrtOptions o;
+    o.specular_override = g_specular;
     CudaApiSink sink;
     PbrtParser parser;
     parser.parseFile(path, sink, o);
@@ -470,6 +488,13 @@ int main(int argc, char **argv) {
         else if (a == "--renderer") renderer = next();
         else if (a == "--pbrt") pbrt = next();
         else if (a == "--dump") dump_only = true;
+        else if (a == "--specular") {
+            g_specular = next();
+            if (g_specular != "pbrt" && g_specular != "reference") {
+                std::fprintf(stderr, "--specular %s: expected pbrt or reference\n", g_specular.c_str());
+                return 2;
+            }
+        }
         else if (a == "--out") out = next();
         else if (a == "--spp") cflags.spp = next();
         else if (a == "--filter") cflags.filter = next();

@@ -153,6 +153,12 @@ struct Ctx {
      * the records' albedo factors (EyeParams::kd), sized like the records */
     DevBuf d_tex_recs, d_texels, d_mat_tex, d_tri_uv, d_rkd;
     bool textured = false;            /* the committed scene has a textured material */
+    /* the physical specular model (SceneDev::mat_spec): the table, and whether
+     * the committed scene has such a material. Such a scene also gets d_mat_tex
+     * (all -1 without textures) and the albedo factors d_rkd */
+    DevBuf d_mat_spec;
+    bool specular = false;
+    bool albedo() const { return textured || specular; } /* the records carry albedo factors (d_rkd) */
     SceneDev S{};
     float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};
     bool slots_nonneg = true;  /* the slot buffer holds no negative flux (uploaded slots are checked) */
@@ -414,9 +420,9 @@ int ensure_records(Ctx *c) {
     HIPCHK(c, c->d_state.ensure(n * sizeof(float4)));
     HIPCHK(c, c->d_n.ensure(n * sizeof(float)));
     HIPCHK(c, c->d_dl.ensure(n * sizeof(float4)));
-    /* the albedo factors, only for a textured scene; a new buffer starts as
+    /* the albedo factors, only for a textured or physically specular scene; a new buffer starts as
      * all ones (records uploaded without an eye pass keep their flux as it is) */
-    if (c->textured && !(c->d_rkd.p && (size_t)n * sizeof(float4) <= c->d_rkd.bytes)) {
+    if (c->albedo() && !(c->d_rkd.p && (size_t)n * sizeof(float4) <= c->d_rkd.bytes)) {
         HIPCHK(c, c->d_rkd.ensure(n * sizeof(float4)));
         const std::vector<float4> ones((size_t)n, f4(1.f, 1.f, 1.f, 0.f));
         HIPCHK(c, hipMemcpy(c->d_rkd.p, ones.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
@@ -441,6 +447,14 @@ int grid_span(const GridDesc &g, float radius2) {
     const double rq = sqrt((double)radius2) * 1.0001 + 1e-4;
     const double w = 2.0 * rq * (double)g.inv_cs * (1.0 + 1e-6);
     return std::max(2, std::min(5, (int)std::floor(w) + 2));
+}
+
+/* the largest alpha a deposit can carry: the emission, max_photon_count
+ * Lambert weights and max_specular_depth lobe colours of the physical specular
+ * model (spec_max is 1, and the factor exactly 1, without such a material) */
+double flux_bound(Ctx *c, const pm_render_params *p) {
+    return emission_bound(c, p) * std::pow(c->lsum.kd_max, (double)p->max_photon_count) *
+           std::pow(c->lsum.spec_max, (double)std::max(p->max_specular_depth, 0));
 }
 
 GatherParams gather_params(Ctx *c, const pm_render_params *p) {
@@ -473,7 +487,7 @@ GatherParams gather_params(Ctx *c, const pm_render_params *p) {
      * alpha_max * Kd_max / pi with alpha_max = emission * Kd_max^mpc (Lambert
      * weight ~Kd, specular weight 1); x4 headroom; 2^40 per contribution
      * leaves 2^23 contributions per record before int64 overflow */
-    double cmax = emission_bound(c, p) * std::pow(c->lsum.kd_max, (double)p->max_photon_count) * (c->lsum.kd_max / M_PI) * 4.0;
+    double cmax = flux_bound(c, p) * (c->lsum.kd_max / M_PI) * 4.0;
     int S = (int)std::floor(std::log2(std::ldexp(1.0, 40) / std::max(cmax, 1e-30)));
     S = std::max(-60, std::min(60, S));
     G.fx_scale = (float)std::ldexp(1.0, S);
@@ -489,7 +503,7 @@ FinalParams final_params(Ctx *c, double emitted, int64_t begin, int64_t count, f
     F.knn = c->rec_estimator == PM_ESTIMATOR_KNN; F.materials = c->S.materials;
     F.emitted = (float)emitted; /* gContext["emittingPhotons"]->setFloat((float)totalPhotons) */
     F.rec_begin = begin; F.rec_count = count; F.out = out; F.raster = 0; F.W = c->W;
-    F.kd = c->textured ? c->d_rkd.as<float4>() : nullptr;
+    F.kd = c->albedo() ? c->d_rkd.as<float4>() : nullptr;
     return F;
 }
 
@@ -790,7 +804,7 @@ void pm_destroy(void *ptr) {
                       &c->d_dl, &c->d_slots, &c->d_count, &c->d_scratch, &c->d_vflags, &c->d_vrank, &c->d_vlist, &c->d_vsums,
                       &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times,
                       &c->d_kd, &c->d_out, &c->d_counters, &c->d_hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf, &c->d_film_table, &c->d_img,
-                      &c->d_tex_recs, &c->d_texels, &c->d_mat_tex, &c->d_tri_uv, &c->d_rkd};
+                      &c->d_tex_recs, &c->d_texels, &c->d_mat_tex, &c->d_tri_uv, &c->d_rkd, &c->d_mat_spec};
     for (DevBuf *b : bufs) b->release();
     c->tiles.release();
     if (c->hist_event) (void)hipEventDestroy(c->hist_event);
@@ -885,6 +899,17 @@ int pm_add_material_textured(void *ptr, int type, int kd_tex, int *out_id) {
     GROUP_FWD(ptr, pm_add_material_textured(sub, type, kd_tex, out_id));
     GETCTX(ptr);
     if (int rc = add_material_textured(c->hs, type, kd_tex, out_id, err)) FAIL(c, rc, "%s", err.c_str());
+    c->committed = false;
+    return PM_OK;
+}
+
+int pm_add_material_specular(void *ptr, int type, const float kr[3], const float kt[3], float index, int *out_id) {
+    std::string err;
+    if (int rc = check_material_specular(type, kr, kt, index, err)) FAIL((Ctx *)nullptr, rc, "%s", err.c_str());
+    if (!out_id) FAIL((Ctx *)nullptr, PM_ERR_INVALID, "pm_add_material_specular: null pointer");
+    GROUP_FWD(ptr, pm_add_material_specular(sub, type, kr, kt, index, out_id));
+    GETCTX(ptr);
+    if (int rc = add_material_specular(c->hs, type, kr, kt, index, out_id, err)) FAIL(c, rc, "%s", err.c_str());
     c->committed = false;
     return PM_OK;
 }
@@ -1287,7 +1312,8 @@ static void fill_scene_dev(Ctx *c) {
     S.light_tris = c->d_light_tris.as<LightTri>();
     S.tex_recs = c->textured ? c->d_tex_recs.as<TexRec>() : nullptr;
     S.texels = c->textured ? c->d_texels.as<float4>() : nullptr;
-    S.mat_tex = c->textured ? c->d_mat_tex.as<int>() : nullptr;
+    S.mat_tex = c->albedo() ? c->d_mat_tex.as<int>() : nullptr;
+    S.mat_spec = c->specular ? c->d_mat_spec.as<float4>() : nullptr;
     S.tri_uv = c->textured ? c->d_tri_uv.as<float4>() : nullptr;
     S.n_inst = (int)ni;
     S.insts = ni ? (const float4 *)(base + L.off[SEC_INSTS]) : nullptr;
@@ -1327,6 +1353,7 @@ int pm_commit(void *ptr) {
 
     bool built = false;
     c->textured = scene_textured(c->hs);
+    c->specular = scene_specular(c->hs);
     std::vector<float4> tri_uv; /* textured scenes: SceneDev::tri_uv */
     if (c->hs.insts.empty() && !opt.bvh8 && gpu_bvh_wanted(opt, (int64_t)prims.size())) {
         if ((rc = commit_gpu_bvh(c, prims, opt, c->L, built))) return rc;
@@ -1359,9 +1386,10 @@ int pm_commit(void *ptr) {
     if (c->textured) {
         if ((rc = upload(c, c->d_tex_recs, c->hs.textures))) return rc;
         if ((rc = upload(c, c->d_texels, c->hs.texels))) return rc;
-        if ((rc = upload(c, c->d_mat_tex, material_textures(c->hs)))) return rc;
         if ((rc = upload(c, c->d_tri_uv, tri_uv))) return rc;
     }
+    if (c->albedo() && (rc = upload(c, c->d_mat_tex, material_textures(c->hs)))) return rc;
+    if (c->specular && (rc = upload(c, c->d_mat_spec, material_specular_table(c->hs)))) return rc;
     fill_scene_dev(c);
 
     if ((rc = light_summary(c->hs, c->lsum, err))) FAIL(c, rc, "%s", err.c_str());
@@ -1386,7 +1414,7 @@ int pm_eye_pass(void *ptr, const pm_render_params *p, void *stream) {
     E.rays = c->d_rays.as<float>(); E.rand2d = c->d_rand2d.as<float>();
     E.eps = p->scene_epsilon; E.r2init = p->initial_radius2; E.max_spec = p->max_specular_depth;
     E.light_seed = p->light_rng_seed;
-    E.kd = c->textured ? c->d_rkd.as<float4>() : nullptr;
+    E.kd = c->albedo() ? c->d_rkd.as<float4>() : nullptr;
     timer_begin(c, "eye", s);
     HIPCHK(c, launch_eye(E, s));
     timer_end(c, "eye", s);
@@ -1721,7 +1749,7 @@ static int gather_knn_setup(Ctx *c, const pm_render_params *p, GatherParams &G) 
      * the per-record scale per term (x4 headroom in amax), exact as a float
      * and as an int32, and <= PM_KNN_MAX = 2^6 terms sum below 2^28 —
      * exact in int32 */
-    const double amax = emission_bound(c, p) * std::pow(c->lsum.kd_max, (double)p->max_photon_count) * 4.0;
+    const double amax = flux_bound(c, p) * 4.0;
     G.knn_fx = (float)(std::ldexp(1.0, 24) / std::max(amax, 1e-30));
     G.slots = c->d_slots.as<pm_photon>();
     if (c->knn_ss && !c->counting && c->gather_kernel == PM_GK_TILE) {
@@ -2352,7 +2380,8 @@ int pm_upload_records(void *ptr, const pm_record *in, int64_t n) {
 int pm_download_record_albedo(void *ptr, float *out_rgb, int64_t n) {
     GETCTX(ptr);
     if (!out_rgb) FAIL(c, PM_ERR_INVALID, "pm_download_record_albedo: null pointer");
-    if (!c->committed || !c->textured) FAIL(c, PM_ERR_INVALID, "pm_download_record_albedo: the committed scene has no textured material");
+    if (!c->committed || !c->albedo())
+        FAIL(c, PM_ERR_INVALID, "pm_download_record_albedo: the committed scene has no textured material and none of the physical specular model");
     if (n < 0 || n > c->nrec || !c->d_rkd.p) FAIL(c, PM_ERR_INVALID, "bad record range");
     if (int rc = materialize_reset(c, c->stream)) return rc; /* as pm_download_records does */
     HIPCHK(c, hipDeviceSynchronize());
@@ -2365,7 +2394,8 @@ int pm_download_record_albedo(void *ptr, float *out_rgb, int64_t n) {
 int pm_upload_record_albedo(void *ptr, const float *in_rgb, int64_t n) {
     GETCTX(ptr);
     if (!in_rgb) FAIL(c, PM_ERR_INVALID, "pm_upload_record_albedo: null pointer");
-    if (!c->committed || !c->textured) FAIL(c, PM_ERR_INVALID, "pm_upload_record_albedo: the committed scene has no textured material");
+    if (!c->committed || !c->albedo())
+        FAIL(c, PM_ERR_INVALID, "pm_upload_record_albedo: the committed scene has no textured material and none of the physical specular model");
     /* no record changes: the tile list and the grid plan stay (ensure_records would drop them) */
     if (n != c->nrec || !c->d_rkd.p || (size_t)n * sizeof(float4) > c->d_rkd.bytes)
         FAIL(c, PM_ERR_INVALID, "pm_upload_record_albedo: %lld values for %lld records (run pm_eye_pass or pm_upload_records first)",
@@ -2460,7 +2490,8 @@ int pm_scene_section(void *ptr, int section, void *out, int64_t max_bytes, int64
     case PM_SCENE_LIGHT_TRIS: src = S.light_tris; n = (int64_t)(c->hs.light_tris.size() * sizeof(LightTri)); break;
     case PM_SCENE_LIGHT_CDF: src = c->d_light_cdf.p; n = (int64_t)(c->lsum.cdf.size() * sizeof(float)); break;
     case PM_SCENE_TEXTURES: src = S.tex_recs; n = c->textured ? (int64_t)(c->hs.textures.size() * sizeof(TexRec)) : 0; break;
-    case PM_SCENE_MAT_TEX: src = S.mat_tex; n = c->textured ? (int64_t)(c->hs.materials.size() * sizeof(int)) : 0; break;
+    case PM_SCENE_MAT_TEX: src = S.mat_tex; n = c->albedo() ? (int64_t)(c->hs.materials.size() * sizeof(int)) : 0; break;
+    case PM_SCENE_MAT_SPEC: src = S.mat_spec; n = c->specular ? (int64_t)(c->hs.materials.size() * 2 * sizeof(float4)) : 0; break;
     case PM_SCENE_WORLD_SPHERE: /* a host value */
         if (bytes) *bytes = (int64_t)sizeof c->world_sphere;
         if (out) {

@@ -130,7 +130,15 @@ struct SceneDev {
     const float4 *texels;
     const int *mat_tex;
     const float4 *tri_uv;
-    /* all arrays above but light_tris and the textures' are 16-B aligned sections of one blob in HBM */
+    /* the physical specular model (pm_add_material_specular): 2 float4 per
+     * material, (Kr.xyz, index) (Kt.xyz, flag as int bits: 1 = the material
+     * uses the model, 0 = it keeps the reference's), a buffer of its own in
+     * HBM like the textures'. Null unless the committed scene has such a
+     * material: that selects the SPEC instantiations of the trace and eye
+     * kernels, which also hold the texture code; mat_tex is then non-null too
+     * (all -1 in a scene without textures) */
+    const float4 *mat_spec;
+    /* all arrays above but light_tris, the textures' and mat_spec are 16-B aligned sections of one blob in HBM */
     const char *blob;
     uint32_t blob_bytes;
     uint32_t lds_bytes; /* = blob_bytes when the blob fits LDS_SCENE_MAX (LDS-resident mode), else 0 */
@@ -1333,6 +1341,56 @@ PMD bool material_specular(int type, const Geo &g, v3 wow, v3 *wiw) {
         float cost = sqrtf(fmaxf(0.f, 1.f - sint2));
         if (entering) cost = -cost;
         wi = mk(eta * -wo.x, eta * -wo.y, cost);
+    }
+    *wiw = local_to_world(wi, nn, sn, tn);
+    return true;
+}
+
+/* The physical specular model of pm_add_material_specular (pm_api.h states
+ * it): a mirror reflects with weight Kr and reads no u; glass is pbrt-v2's
+ * FresnelDielectric(1, index) with a reflection lobe Kr and a transmission
+ * lobe Kt, one of which u picks. a = (Kr, index), b = (Kt, flag) of
+ * SceneDev::mat_spec. Returns false when both lobes are black (the path or
+ * chain ends); else *wiw, the weight of the step and *eta2 = eta * eta for a
+ * transmitted step (what an eye chain's radiance scales by), 1 otherwise. */
+PMD bool material_specular_pbrt(int type, float4 a, float4 b, const Geo &g, v3 wow, float u, v3 *wiw, v3 *weight,
+                                float *eta2) {
+    const v3 nn = g.ns, sn = g.dpdu, tn = cross(nn, sn);
+    const v3 wo = world_to_local(wow, nn, sn, tn);
+    const v3 kr = xyz(a);
+    v3 wi = mk(-wo.x, -wo.y, wo.z);
+    *eta2 = 1.0f;
+    if (type == PM_MIRROR) {
+        if (is_black(kr)) return false;
+        *weight = kr;
+    } else {
+        const v3 kt = xyz(b);
+        const bool entering = wo.z > 0.f;
+        const float ei = entering ? 1.0f : a.w, et = entering ? a.w : 1.0f;
+        const float eta = ei / et;
+        const float sini2 = fmaxf(0.f, 1.f - wo.z * wo.z);
+        const float sint2 = eta * eta * sini2;
+        float F = 1.0f, cost = 0.0f;
+        if (!(sint2 >= 1.0f)) {
+            cost = sqrtf(fmaxf(0.f, 1.f - sint2));
+            const float ci = fabsf(wo.z);
+            const float rpar = (et * ci - ei * cost) / (et * ci + ei * cost);
+            const float rper = (ei * ci - et * cost) / (ei * ci + et * cost);
+            F = 0.5f * (rpar * rpar + rper * rper);
+        }
+        const v3 wr = F * kr, wt = (1.0f - F) * kt;
+        const bool rb = is_black(wr), tb = is_black(wt);
+        if (rb && tb) return false;
+        const float q = tb ? 1.0f : (rb ? 0.0f : F);
+        const bool reflect = u < q;
+        const bool both = q > 0.0f && q < 1.0f; /* the probability cancels: the lobe's colour itself */
+        if (reflect) {
+            *weight = both ? kr : wr;
+        } else {
+            *weight = both ? kt : wt;
+            wi = mk(eta * -wo.x, eta * -wo.y, entering ? -cost : cost);
+            *eta2 = eta * eta;
+        }
     }
     *wiw = local_to_world(wi, nn, sn, tn);
     return true;

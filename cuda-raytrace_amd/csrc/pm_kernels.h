@@ -86,10 +86,12 @@ struct EyeParams {
      * itself is the pinhole's */
     int camera;
     CameraDev cam;
-    /* textured scenes (S.tex_recs != null) only: per record the factor
-     * pm_final applies to its indirect term (float4, SoA like R's arrays):
-     * the texel of a textured matte hit, (1, 1, 1) on any other surface,
-     * 0 for an inactive record. Null otherwise, and never read then */
+    /* scenes with a textured material (S.tex_recs != null) or one of the
+     * physical specular model (S.mat_spec != null) only: per record the
+     * factor pm_final applies to its indirect term (float4, SoA like R's
+     * arrays): the texel of a textured matte hit, (1, 1, 1) on any other
+     * surface, times the throughput of the record's specular chain; 0 for
+     * an inactive record. Null otherwise, and never read then */
     float4 *kd;
 };
 

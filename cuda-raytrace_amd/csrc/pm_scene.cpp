@@ -748,6 +748,46 @@ double texture_bound(const HostScene &hs, int t, bool *negative) {
     return r * (1.0 + 1e-6); /* the blend's and the products' rounding */
 }
 
+/* ------------------------------------------------------ specular materials */
+int check_material_specular(int type, const float *kr, const float *kt, float index, std::string &err) {
+    const char *who = "pm_add_material_specular";
+    if (type != PM_MIRROR && type != PM_GLASS) return fail(err, "%s: type %d is neither PM_MIRROR nor PM_GLASS", who, type);
+    if (!kr) return fail(err, "%s: null pointer", who);
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(kr[a]) || kr[a] < 0.f) return fail(err, "%s: Kr component %d is %g (negative or not finite)", who, a, (double)kr[a]);
+    if (type == PM_MIRROR) return PM_OK;
+    if (!kt) return fail(err, "%s: null pointer", who);
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(kt[a]) || kt[a] < 0.f) return fail(err, "%s: Kt component %d is %g (negative or not finite)", who, a, (double)kt[a]);
+    if (!std::isfinite(index) || !(index > 0.f)) return fail(err, "%s: index %g is not finite or not above 0", who, (double)index);
+    return PM_OK;
+}
+
+int add_material_specular(HostScene &hs, int type, const float *kr, const float *kt, float index, int *out_id,
+                          std::string &err) {
+    if (int rc = check_material_specular(type, kr, kt, index, err)) return rc;
+    if (!out_id) return fail(err, "pm_add_material_specular: null pointer");
+    hs.materials.push_back(f4(0.f, 0.f, 0.f, ibits(type)));
+    hs.mat_spec.resize(2 * hs.materials.size(), f4(0.f, 0.f, 0.f, 0.f));
+    const bool glass = type == PM_GLASS;
+    hs.mat_spec[hs.mat_spec.size() - 2] = f4(kr[0], kr[1], kr[2], glass ? index : 0.f);
+    hs.mat_spec[hs.mat_spec.size() - 1] = f4(glass ? kt[0] : 0.f, glass ? kt[1] : 0.f, glass ? kt[2] : 0.f, ibits(1));
+    *out_id = (int)hs.materials.size() - 1;
+    return PM_OK;
+}
+
+bool scene_specular(const HostScene &hs) {
+    for (size_t m = 0; 2 * m + 1 < hs.mat_spec.size() && m < hs.materials.size(); ++m)
+        if (fbits_h(hs.mat_spec[2 * m + 1].w) != 0) return true;
+    return false;
+}
+
+std::vector<float4> material_specular_table(const HostScene &hs) {
+    std::vector<float4> t(2 * hs.materials.size(), f4(0.f, 0.f, 0.f, 0.f));
+    for (size_t i = 0; i < t.size() && i < hs.mat_spec.size(); ++i) t[i] = hs.mat_spec[i];
+    return t;
+}
+
 /* --------------------------------------------------------- light summary */
 int light_selection_cdf(const int *types, const float *le_rgb, const float *areas, int n, float *cdf_out, std::string &err) {
     if (!types || !le_rgb || !areas || !cdf_out) return fail(err, "pm_light_selection_cdf: null pointer");
@@ -839,6 +879,15 @@ int light_summary(const HostScene &hs, LightSummary &out, std::string &err) {
         bool neg = false;
         out.kd_max = std::max(out.kd_max, texture_bound(hs, hs.mat_tex[m], &neg));
         nn = nn && !neg;
+    }
+    /* a step through a material of the physical specular model scales a
+     * photon's flux by Kr or Kt (at most: F Kr, (1 - F) Kt), both >= 0; a
+     * path takes up to max_specular_depth such steps, so the bound is kept
+     * apart from kd_max, which counts max_photon_count Lambert bounces */
+    for (size_t m = 0; 2 * m + 1 < hs.mat_spec.size() && m < hs.materials.size(); ++m) {
+        const float4 &a = hs.mat_spec[2 * m], &b = hs.mat_spec[2 * m + 1];
+        if (fbits_h(b.w) == 0) continue;
+        out.spec_max = std::max({out.spec_max, (double)a.x, (double)a.y, (double)a.z, (double)b.x, (double)b.y, (double)b.z});
     }
     out.scene_nonneg = nn;
     return PM_OK;

@@ -57,6 +57,10 @@ struct HostScene {
     std::vector<TexRec> textures;
     std::vector<float4> texels;
     std::vector<int> mat_tex;
+    /* the physical specular model (pm_add_material_specular): per material 2
+     * float4, (Kr, index) (Kt, 1 as int bits); may be shorter than materials,
+     * the missing entries and all-zero ones meaning the reference's model */
+    std::vector<float4> mat_spec;
 };
 
 /* Everything below that can fail returns PM_OK or an error code with its
@@ -198,6 +202,19 @@ std::vector<float4> triangle_uvs(const HostScene &hs, const uint32_t *tri_order,
 /* the largest |component| texture t can return, and whether one can be negative */
 double texture_bound(const HostScene &hs, int t, bool *negative);
 
+/* ------------------------------------------------------ specular materials */
+/* pm_add_material_specular (pm_api.h): check_ looks at the arguments alone
+ * (a mirror's kt and index are not looked at), add_ repeats it and appends
+ * the material: (0, 0, 0, type) in the materials table, as pm_add_material
+ * stores a specular type, and its parameters in mat_spec */
+int check_material_specular(int type, const float *kr, const float *kt, float index, std::string &err);
+int add_material_specular(HostScene &hs, int type, const float *kr, const float *kt, float index, int *out_id,
+                          std::string &err);
+/* does a material of the scene use the physical model? */
+bool scene_specular(const HostScene &hs);
+/* SceneDev::mat_spec: two entries per material, zero for the others */
+std::vector<float4> material_specular_table(const HostScene &hs);
+
 /* --------------------------------------------------------- light summary */
 /* pm_light_selection_cdf (pm_api.h) */
 int light_selection_cdf(const int *types, const float *le_rgb, const float *areas, int n, float *cdf_out, std::string &err);
@@ -208,6 +225,9 @@ struct LightSummary {
      * weight: max_l(bound_l / pmf_l) over the lights with pmf_l > 0 of the
      * float table */
     double emit_max = 1.0, emit_max_all = 1.0, kd_max = 1.0;
+    /* the largest lobe colour (>= 1) of the materials of the physical specular
+     * model: a photon's flux grows by at most spec_max^max_specular_depth */
+    double spec_max = 1.0;
     bool scene_nonneg = true; /* no negative emission / albedo component (fixed-point sums in double) */
     /* PM_ALL_LIGHTS: the selection table over the scene's lights; all zero
      * and cdf_ok false when their total selection weight is 0 or not finite */

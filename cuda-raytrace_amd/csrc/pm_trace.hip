@@ -28,8 +28,14 @@ namespace pm {
  * direct light's f takes Kd from the texture at the hit, and the record's
  * albedo factor goes to P.kd (pm_kernels.h EyeParams::kd). The other
  * instantiations hold none of it. */
-template <int MODE, bool CAM = false, bool TEX = false>
-__global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
+/* SPEC: the committed scene has a material of the physical specular model
+ * (SceneDev::mat_spec; always with TEX): the chain follows one branch per
+ * sample, picked with a Philox draw keyed like the light samples (word 2 = 2,
+ * word 3 = the depth), and carries an rgb throughput T that multiplies what
+ * the record contributes: dl = T L, P.kd = T x (the texel, or 1). A material
+ * of the reference's model in such a scene steps as it always did. */
+template <int MODE, bool CAM, bool TEX, bool SPEC>
+PMD void eye_body(const EyeParams &P) {
     extern __shared__ __attribute__((aligned(16))) int stk[]; /* [stack_depth x EYE_BLOCK][scene blob (LDS)] */
     int *stack = stk + threadIdx.x;
     const SceneDev S = scene_view<mode_lds(MODE)>(P.S, reinterpret_cast<uint4 *>(stk + P.S.stack_depth * EYE_BLOCK),
@@ -81,6 +87,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
     Hit h;
     Geo g;
     uint32_t flags = 0;
+    v3 T = mk(1.f, 1.f, 1.f); /* SPEC: the chain's throughput */
     while (true) {
         if (!traverse<false, MODE>(S, ray, h, stack, EYE_BLOCK)) { flags = PM_REC_MISS; break; }
         g = shade<MODE == MODE_INST>(S, ray, h);
@@ -88,7 +95,27 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
         int mtype = fbits(S.materials[g.material].w);
         if (is_specular(mtype)) {
             v3 wi;
-            bool ok = material_specular(mtype, g, -ray.d, &wi);
+            bool ok;
+            float4 sa, sb;
+            bool pbrt = false;
+            if (SPEC) {
+                sa = S.mat_spec[2 * g.material]; sb = S.mat_spec[2 * g.material + 1];
+                pbrt = fbits(sb.w) != 0;
+            }
+            if (SPEC && pbrt) {
+                float u = 0.f;
+                if (mtype == PM_GLASS) {
+                    uint32_t o4[4];
+                    pmdm_philox4x32_10((uint32_t)((uint64_t)pixel & 0xffffffffu), (uint32_t)((uint64_t)pixel >> 32), 2u,
+                                       (uint32_t)(depth + 1), P.light_seed, 0u, o4);
+                    u = pmdm_u01(o4[0]);
+                }
+                v3 w; float eta2;
+                ok = material_specular_pbrt(mtype, sa, sb, g, -ray.d, u, &wi, &w, &eta2);
+                if (ok) T = (T * w) * eta2; /* radiance: a transmitted step scales by (ei / et)^2 */
+            } else {
+                ok = material_specular(mtype, g, -ray.d, &wi);
+            }
             depth++;
             if (depth > P.max_spec || !ok) { flags = PM_REC_EXCEPTION; break; }
             ray.o = point; ray.d = wi; ray.tmin = P.eps; ray.tmax = RT_DEFAULT_MAX;
@@ -157,9 +184,15 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) {
     P.R.nrm[r] = make_float4(ns.x, ns.y, ns.z, __int_as_float(g.material));
     P.R.state[r] = make_float4(0.f, 0.f, 0.f, P.r2init);
     P.R.n[r] = 0.f;
+    if (SPEC) { L = T * L; kdf = T * kdf; }
     P.R.dl[r] = make_float4(L.x, L.y, L.z, 0.f);
     if (TEX) P.kd[r] = make_float4(kdf.x, kdf.y, kdf.z, 0.f);
 }
+
+template <int MODE, bool CAM = false, bool TEX = false>
+__global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) { eye_body<MODE, CAM, TEX, false>(P); }
+template <int MODE, bool CAM>
+__global__ __launch_bounds__(EYE_BLOCK) void k_eye_spec(EyeParams P) { eye_body<MODE, CAM, true, true>(P); }
 
 template <bool CAM, bool TEX>
 static void launch_eye_mode(const EyeParams &p, unsigned grid, size_t lds, hipStream_t s) {
@@ -171,11 +204,25 @@ static void launch_eye_mode(const EyeParams &p, unsigned grid, size_t lds, hipSt
     }
 }
 
+template <bool CAM>
+static void launch_eye_spec(const EyeParams &p, unsigned grid, size_t lds, hipStream_t s) {
+    switch (scene_mode(p.S)) {
+    case MODE_BRUTE: pm_launch((k_eye_spec<MODE_BRUTE, CAM>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    case MODE_LDS: pm_launch((k_eye_spec<MODE_LDS, CAM>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    case MODE_INST: pm_launch((k_eye_spec<MODE_INST, CAM>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    default: pm_launch((k_eye_spec<MODE_GLOBAL, CAM>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    }
+}
+
 hipError_t launch_eye(const EyeParams &p, hipStream_t s) {
     if (p.R.count <= 0) return hipSuccess;
     unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
     const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
-    if (p.S.tex_recs) { /* a textured scene: the TEX instantiations, which write the records' albedo */
+    if (p.S.mat_spec) { /* a material of the physical specular model: the SPEC instantiations */
+        if (!p.kd || !p.S.mat_tex) return hipErrorInvalidValue;
+        if (p.camera) launch_eye_spec<true>(p, grid, lds, s);
+        else launch_eye_spec<false>(p, grid, lds, s);
+    } else if (p.S.tex_recs) { /* a textured scene: the TEX instantiations, which write the records' albedo */
         if (!p.kd) return hipErrorInvalidValue;
         if (p.camera) launch_eye_mode<true, true>(p, grid, lds, s);
         else launch_eye_mode<false, true>(p, grid, lds, s);
@@ -505,25 +552,29 @@ PMD bool emit_path(const TraceParams &P, const SceneDev &S, const uint32_t *perm
 
 /* one ray of a path: trace, then specular continuation or diffuse deposit +
  * Lambert bounce (photontracing.cu:119-183); false when the path ends */
-template <int HOLD, bool INST = false, bool TEX = false>
+template <int HOLD, bool INST = false, bool TEX = false, bool SPEC = false>
 PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, const Hit &h, TProf &prof, Held &held);
 
-template <int MODE, int HOLD, bool TEX, class C>
+template <int MODE, int HOLD, bool TEX, bool SPEC, class C>
 PMD bool path_step(const TraceParams &P, const SceneDev &S, int *stack, PathState &st, C &cen, TProf &prof,
                    Held &held) {
     Hit h;
     const bool hit = traverse<false, MODE>(S, st.ray, h, stack, TRACE_BLOCK, cen);
     prof.mark(1);
     if (!hit) return false;
-    return path_shade<HOLD, MODE == MODE_INST, TEX>(P, S, st, h, prof, held);
+    return path_shade<HOLD, MODE == MODE_INST, TEX, SPEC>(P, S, st, h, prof, held);
 }
 
 /* the hit of a path's ray: specular continuation, or diffuse deposit +
  * Lambert bounce (photontracing.cu:119-183); false when the path ends.
  * HOLD: the deposit goes to `held` (written at path end, held_write).
  * TEX (a scene with a textured material): the Lambert bounce takes Kd from
- * the texture at the hit, so a photon off a red texel carries red */
-template <int HOLD, bool INST, bool TEX>
+ * the texture at the hit, so a photon off a red texel carries red.
+ * SPEC (a scene with a material of the physical specular model, always with
+ * TEX): such a material's step picks its lobe with a Philox draw of the
+ * bounce stream's key at word 2 = the path's specular count (>= 1; the
+ * Lambert bounce has 0 there) and scales alpha by the lobe's weight */
+template <int HOLD, bool INST, bool TEX, bool SPEC>
 PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, const Hit &h, TProf &prof, Held &held) {
     const uint32_t mpc = (uint32_t)P.mpc;
     Geo g = shade<INST>(S, st.ray, h);
@@ -533,9 +584,32 @@ PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, cons
     prof.mark(3);
     if (is_specular(mtype)) {
         v3 wi;
-        if (!material_specular(mtype, g, -st.ray.d, &wi)) return false;
-        if ((int)++st.spec > P.max_spec) return false;
-        if (st.nI == 0) st.nI++;
+        float4 sa, sb;
+        bool pbrt = false;
+        if (SPEC) {
+            sa = S.mat_spec[2 * g.material]; sb = S.mat_spec[2 * g.material + 1];
+            pbrt = fbits(sb.w) != 0;
+        }
+        if (SPEC && pbrt) {
+            /* the counters first (the reference's model steps, then counts): the
+             * draw below is keyed by spec and nI after their increments; a path
+             * ends either way, so the order changes no outcome */
+            if ((int)++st.spec > P.max_spec) return false;
+            if (st.nI == 0) st.nI++;
+            float u = 0.f;
+            if (mtype == PM_GLASS) { /* nI >= 1 here, so path pid's counters never meet path pid + 1's */
+                uint32_t o4[4];
+                pmdm_philox4x32_10(st.pid * mpc + st.nI, (uint32_t)P.pass, st.spec, 0u, P.seed, 0u, o4);
+                u = pmdm_u01(o4[0]);
+            }
+            v3 w; float eta2;
+            if (!material_specular_pbrt(mtype, sa, sb, g, -st.ray.d, u, &wi, &w, &eta2)) return false;
+            st.alpha = st.alpha * w; /* flux: no (ei / et)^2 (pbrt-v3's correction of v2) */
+        } else {
+            if (!material_specular(mtype, g, -st.ray.d, &wi)) return false;
+            if ((int)++st.spec > P.max_spec) return false;
+            if (st.nI == 0) st.nI++;
+        }
         st.ray.o = hit_point; st.ray.d = wi; st.ray.tmin = P.eps; st.ray.tmax = RT_DEFAULT_MAX;
         return true;
     }
@@ -609,8 +683,8 @@ PMD void finish_path(const TraceParams &P, PathState &st, const Held *held = nul
  * §5) and removed. HOLD: deposits held in LDS and written per path.
  * COUNT: census [rays traced, BVH nodes entered, primitive tests, photons
  * deposited], one atomic per wave (counting launches only, never timed). */
-template <int COUNT, int MODE, int HOLD, int ALL = 0, bool TEX = false>
-__global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
+template <int COUNT, int MODE, int HOLD, int ALL, bool TEX, bool SPEC>
+PMD void trace_lane_body(const TraceParams &P) {
     extern __shared__ __attribute__((aligned(16))) int stk[];
     __shared__ uint32_t perm[28];
     const int tid = threadIdx.x;
@@ -634,7 +708,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
         prof.mark(0);
         while (alive) {
             ++rays;
-            alive = path_step<MODE, HOLD, TEX>(P, S, stack, st, cen, prof, held);
+            alive = path_step<MODE, HOLD, TEX, SPEC>(P, S, stack, st, cen, prof, held);
             prof.mark(2);
         }
         if (COUNT) deposits += st.stored;
@@ -647,6 +721,11 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
         count4(P.counters, rays, nodes, prims, deposits);
     }
 }
+
+template <int COUNT, int MODE, int HOLD, int ALL = 0, bool TEX = false>
+__global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) { trace_lane_body<COUNT, MODE, HOLD, ALL, TEX, false>(P); }
+template <int COUNT, int MODE, int HOLD, int ALL>
+__global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane_spec(TraceParams P) { trace_lane_body<COUNT, MODE, HOLD, ALL, true, true>(P); }
 
 /* Pooled photon tracer for scenes traversed from HBM with the 4-wide BVH
  * (C3). A ray's traversal lives across iterations of the wave's loop
@@ -667,8 +746,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) {
 constexpr int POOL_STEPS = PM_POOL_STEPS, POOL_SHADE_MIN = PM_POOL_SHADE_MIN;
 enum { PHASE_DEAD = 0, PHASE_TRAV = 1, PHASE_SHADE = 2 };
 
-/* W8: the 8-wide tree (S.wide == 3, TravState8); ALL: emit_path's; TEX: path_shade's */
-template <int COUNT, int HOLD, int W8, int ALL, bool TEX>
+/* W8: the 8-wide tree (S.wide == 3, TravState8); ALL: emit_path's; TEX, SPEC: path_shade's */
+template <int COUNT, int HOLD, int W8, int ALL, bool TEX, bool SPEC>
 /* 5 waves/SIMD: 96 VGPRs (102 unconstrained -> 4 waves), no scratch; with
  * the LDS stacks capped at 31 entries (PM_POOL_STACK, the rest spilled) five
  * 256-thread blocks fit a CU. C3 trace (same box): 4.59-4.61 ms at 4 waves,
@@ -719,7 +798,7 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
         if (travm == 0ull || waiting >= POOL_SHADE_MIN) {
             if (phase == PHASE_SHADE) {
                 ++rays;
-                const bool alive = tr.best.ref != 0xffffffffu && path_shade<HOLD, false, TEX>(P, S, st, tr.best, prof, held);
+                const bool alive = tr.best.ref != 0xffffffffu && path_shade<HOLD, false, TEX, SPEC>(P, S, st, tr.best, prof, held);
                 if (alive) {
                     trav_begin(st.ray, tr);
                     phase = PHASE_TRAV;
@@ -757,10 +836,15 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
 }
 
 template <int COUNT, int HOLD, int ALL = 0, bool TEX = false>
-__global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool(TraceParams P) { trace_pool_body<COUNT, HOLD, 0, ALL, TEX>(P); }
+__global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool(TraceParams P) { trace_pool_body<COUNT, HOLD, 0, ALL, TEX, false>(P); }
+template <int COUNT, int HOLD, int ALL>
+__global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool_spec(TraceParams P) { trace_pool_body<COUNT, HOLD, 0, ALL, true, true>(P); }
 template <int COUNT, int HOLD, int ALL = 0, bool TEX = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
-void k_trace_pool8(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, TEX>(P); }
+void k_trace_pool8(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, TEX, false>(P); }
+template <int COUNT, int HOLD, int ALL>
+__global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
+void k_trace_pool8_spec(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, true, true>(P); }
 
 /* resident waves of the pooled kernel per CU at this LDS size (0 if unknown) */
 int trace_pool_waves_per_cu(size_t lds, int hold, int w8) { /* lds: the stacks */
@@ -805,44 +889,62 @@ static bool trace_hold(const TraceParams &p) {
     return p.hold && p.mpc == HOLD_MPC && ((uintptr_t)p.slots & 15u) == 0u;
 }
 
-template <int HOLD, int ALL, bool TEX>
+/* MAT: which instantiations a scene runs: 0 = the plain ones, 1 = TEX (a
+ * textured material), 2 = SPEC (a material of the physical specular model) */
+template <int COUNT, int MODE, int HOLD, int ALL, int MAT>
+static auto lane_kernel() {
+    if constexpr (MAT == 2) return &k_trace_lane_spec<COUNT, MODE, HOLD, ALL>;
+    else return &k_trace_lane<COUNT, MODE, HOLD, ALL, MAT == 1>;
+}
+template <int COUNT, int HOLD, int W8, int ALL, int MAT>
+static auto pool_kernel() {
+    if constexpr (W8 != 0) {
+        if constexpr (MAT == 2) return &k_trace_pool8_spec<COUNT, HOLD, ALL>;
+        else return &k_trace_pool8<COUNT, HOLD, ALL, MAT == 1>;
+    } else {
+        if constexpr (MAT == 2) return &k_trace_pool_spec<COUNT, HOLD, ALL>;
+        else return &k_trace_pool<COUNT, HOLD, ALL, MAT == 1>;
+    }
+}
+
+template <int HOLD, int ALL, int MAT>
 static void launch_lane(const TraceParams &p, dim3 grid, size_t lds, int count, hipStream_t s) {
     switch (scene_mode(p.S)) {
     case MODE_BRUTE:
-        if (count) pm_launch((k_trace_lane<1, MODE_BRUTE, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_BRUTE, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((lane_kernel<1, MODE_BRUTE, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((lane_kernel<0, MODE_BRUTE, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     case MODE_LDS:
-        if (count) pm_launch((k_trace_lane<1, MODE_LDS, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_LDS, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((lane_kernel<1, MODE_LDS, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((lane_kernel<0, MODE_LDS, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     case MODE_INST: /* instances: the per-lane kernel (the pooled one walks only one level) */
-        if (count) pm_launch((k_trace_lane<1, MODE_INST, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_INST, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((lane_kernel<1, MODE_INST, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((lane_kernel<0, MODE_INST, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     default:
-        if (count) pm_launch((k_trace_lane<1, MODE_GLOBAL, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((k_trace_lane<0, MODE_GLOBAL, HOLD, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count) pm_launch((lane_kernel<1, MODE_GLOBAL, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else pm_launch((lane_kernel<0, MODE_GLOBAL, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
     }
 }
 
 /* the pooled kernels (4-wide: k_trace_pool; 8-wide: k_trace_pool8) */
-template <int ALL, bool TEX>
+template <int ALL, int MAT>
 static void launch_pool(const TraceParams &p, dim3 grid, size_t lds, size_t lds_h, bool hold, int count, hipStream_t s) {
     if (p.S.wide == 3) {
-        if (count && hold) pm_launch((k_trace_pool8<1, 1, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-        else if (count) pm_launch((k_trace_pool8<1, 0, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else if (hold) pm_launch((k_trace_pool8<0, 1, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-        else pm_launch((k_trace_pool8<0, 0, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
-    } else if (count && hold) pm_launch((k_trace_pool<1, 1, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-    else if (count) pm_launch((k_trace_pool<1, 0, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
-    else if (hold) pm_launch((k_trace_pool<0, 1, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-    else pm_launch((k_trace_pool<0, 0, ALL, TEX>), grid, dim3(TRACE_BLOCK), lds, s, p);
+        if (count && hold) pm_launch((pool_kernel<1, 1, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+        else if (count) pm_launch((pool_kernel<1, 0, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
+        else if (hold) pm_launch((pool_kernel<0, 1, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+        else pm_launch((pool_kernel<0, 0, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
+    } else if (count && hold) pm_launch((pool_kernel<1, 1, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+    else if (count) pm_launch((pool_kernel<1, 0, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
+    else if (hold) pm_launch((pool_kernel<0, 1, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds_h, s, p);
+    else pm_launch((pool_kernel<0, 0, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
 }
 
-template <bool TEX>
-static hipError_t launch_trace_tex(const TraceParams &p, int count, hipStream_t s) {
+template <int MAT>
+static hipError_t launch_trace_mat(const TraceParams &p, int count, hipStream_t s) {
     /* PM_ALL_LIGHTS: the ALL instantiations; a fixed light is an index into S.lights */
     const bool all = p.light_index == PM_ALL_LIGHTS;
     if (all ? !p.light_cdf : p.light_index < 0 || p.light_index >= p.S.n_lights) return hipErrorInvalidValue;
@@ -854,8 +956,8 @@ static hipError_t launch_trace_tex(const TraceParams &p, int count, hipStream_t 
         const unsigned grid = (unsigned)((waves + TRACE_BLOCK / 64 - 1) / (TRACE_BLOCK / 64));
         const bool hold = trace_hold(p);
         const size_t lds_h = lds + (hold ? (size_t)HOLD_WORDS * TRACE_BLOCK * 4 : 0);
-        if (all) launch_pool<1, TEX>(p, dim3(grid), lds, lds_h, hold, count, s);
-        else launch_pool<0, TEX>(p, dim3(grid), lds, lds_h, hold, count, s);
+        if (all) launch_pool<1, MAT>(p, dim3(grid), lds, lds_h, hold, count, s);
+        else launch_pool<0, MAT>(p, dim3(grid), lds, lds_h, hold, count, s);
         return hipGetLastError();
     }
     /* one path per lane */
@@ -863,18 +965,21 @@ static hipError_t launch_trace_tex(const TraceParams &p, int count, hipStream_t 
     const unsigned grid = (unsigned)((p.path_count + TRACE_BLOCK - 1) / TRACE_BLOCK);
     const size_t lds_h = lds + ((size_t)p.S.lds_bytes + 15u) / 16u * 16u - p.S.lds_bytes + (size_t)HOLD_WORDS * TRACE_BLOCK * 4;
     if (trace_hold(p)) {
-        if (all) launch_lane<1, 1, TEX>(p, dim3(grid), lds_h, count, s);
-        else launch_lane<1, 0, TEX>(p, dim3(grid), lds_h, count, s);
-    } else if (all) launch_lane<0, 1, TEX>(p, dim3(grid), lds, count, s);
-    else launch_lane<0, 0, TEX>(p, dim3(grid), lds, count, s);
+        if (all) launch_lane<1, 1, MAT>(p, dim3(grid), lds_h, count, s);
+        else launch_lane<1, 0, MAT>(p, dim3(grid), lds_h, count, s);
+    } else if (all) launch_lane<0, 1, MAT>(p, dim3(grid), lds, count, s);
+    else launch_lane<0, 0, MAT>(p, dim3(grid), lds, count, s);
     return hipGetLastError();
 }
 
-/* a scene with a textured material (SceneDev::tex_recs) runs the TEX
- * instantiations; every other scene the kernels it ran before textures existed */
+/* a scene with a material of the physical specular model (SceneDev::mat_spec)
+ * runs the SPEC instantiations, one with a textured material
+ * (SceneDev::tex_recs) the TEX ones; every other scene the kernels it ran
+ * before either existed */
 hipError_t launch_trace(const TraceParams &p, int count, hipStream_t s) {
     if (p.path_count <= 0) return hipSuccess;
-    return p.S.tex_recs ? launch_trace_tex<true>(p, count, s) : launch_trace_tex<false>(p, count, s);
+    if (p.S.mat_spec) return p.S.mat_tex ? launch_trace_mat<2>(p, count, s) : hipErrorInvalidValue;
+    return p.S.tex_recs ? launch_trace_mat<1>(p, count, s) : launch_trace_mat<0>(p, count, s);
 }
 
 } // namespace pm

@@ -16,6 +16,7 @@ PM_LIGHT_AREA_MESH = 4  # ours: an emitting triangle mesh (pm_add_light_mesh)
 PM_LIGHT_DISTANT = 6  # ours: pbrt-v2's distant light (pm_add_light_distant); 5 is kept for a spot light
 PM_SCENE_WORLD_SPHERE = 10  # pm_scene_section: centre xyz, radius of the last commit's world sphere
 PM_SCENE_TEXTURES, PM_SCENE_MAT_TEX = 11, 12  # pm_scene_section: the texture records, per material its Kd texture
+PM_SCENE_MAT_SPEC = 13  # pm_scene_section: per material (Kr, index) (Kt, flag) of pm_add_material_specular
 # wrap modes of an image texture (pm_add_texture_image)
 PM_TEX_WRAP_REPEAT, PM_TEX_WRAP_BLACK, PM_TEX_WRAP_CLAMP = 0, 1, 2
 TEX_WRAPS = {"repeat": PM_TEX_WRAP_REPEAT, "black": PM_TEX_WRAP_BLACK, "clamp": PM_TEX_WRAP_CLAMP}

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .abi import (LIGHT_TRI_DTYPE, PM_SCENE_MAT_TEX, PM_SCENE_TEXTURES, PM_SCENE_WORLD_SPHERE, TEX_REC_DTYPE, TEX_WRAPS, PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PM_FILM_TABLE, PM_FILTER_NONE, Camera,
+from .abi import (LIGHT_TRI_DTYPE, PM_SCENE_MAT_SPEC, PM_SCENE_MAT_TEX, PM_SCENE_TEXTURES, PM_SCENE_WORLD_SPHERE, TEX_REC_DTYPE, TEX_WRAPS, PHOTON_DTYPE, RECORD_DTYPE, PM_ERR_NO_PHOTONS, PM_FILM_TABLE, PM_FILTER_NONE, Camera,
                   Filter, PMConfig, RenderParams, Stats, f32, fptr, iptr, record_pixels)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,6 +50,7 @@ def load_library(path=None):
         "pm_add_texture_checker": (c_int, [vp, P_f, c_int, P_f, c_int, P_f, P_i]),
         "pm_add_texture_scale": (c_int, [vp, c_int, P_f, c_int, P_f, P_i]),
         "pm_add_material_textured": (c_int, [vp, c_int, c_int, P_i]),
+        "pm_add_material_specular": (c_int, [vp, c_int, P_f, P_f, c_float, P_i]),
         "pm_download_record_albedo": (c_int, [vp, P_f, i64]),
         "pm_upload_record_albedo": (c_int, [vp, P_f, i64]),
         "pm_add_trimesh": (c_int, [vp, P_f, c_int, P_i, c_int, P_f, P_f, c_int, c_int]),
@@ -252,9 +253,16 @@ class Context:
         self._chk(self.lib.pm_add_material_textured(self.h, int(mtype), int(kd_tex), ctypes.byref(out)))
         return out.value
 
+    def add_material_specular(self, mtype, kr, kt=(1.0, 1.0, 1.0), index=1.5):
+        """A PM_MIRROR or PM_GLASS of the physical model (pm_add_material_specular). Returns the material id."""
+        out = ctypes.c_int()
+        self._chk(self.lib.pm_add_material_specular(self.h, int(mtype), fptr(f32(kr, 3)), fptr(f32(kt, 3)), float(index),
+                                                    ctypes.byref(out)))
+        return out.value
+
     def record_albedo(self):
         """(n_records, 3): the factor pm_final applies to each record's indirect term
-        (pm_download_record_albedo; textured scenes only)."""
+        (pm_download_record_albedo; scenes with a textured or physically specular material only)."""
         out = np.zeros((self.num_records(), 3), np.float32)
         self._chk(self.lib.pm_download_record_albedo(self.h, fptr(out), len(out)))
         return out
@@ -551,7 +559,8 @@ class Context:
                       "light_tris": (8, LIGHT_TRI_DTYPE), "light_cdf": (9, np.float32)}
     # textured scenes (empty otherwise): the texture records and per material its Kd texture; buffers of
     # their own, kept apart from the sections every scene has
-    TEXTURE_SECTIONS = {"textures": (PM_SCENE_TEXTURES, TEX_REC_DTYPE), "mat_tex": (PM_SCENE_MAT_TEX, np.int32)}
+    TEXTURE_SECTIONS = {"textures": (PM_SCENE_TEXTURES, TEX_REC_DTYPE), "mat_tex": (PM_SCENE_MAT_TEX, np.int32),
+                        "mat_spec": (PM_SCENE_MAT_SPEC, np.float32)}  # 8 floats per material (pm_api.h)
 
     def scene_section(self, name):
         """One section of the committed scene blob as the kernels read it (pm_scene_section)."""

@@ -39,6 +39,14 @@ class Tex:
     index: int
 
 
+@dataclass(frozen=True)
+class Spec:
+    """Parameters of a specular material of the physical model (Scene.material_specular)."""
+    kr: np.ndarray
+    kt: np.ndarray
+    index: float
+
+
 @dataclass
 class Scene:
     materials: list = field(default_factory=list)   # (type, rgb)
@@ -58,6 +66,12 @@ class Scene:
     def material(self, mtype, rgb):
         """rgb: a colour, or a Tex handle for the Kd of a PM_MATTE (pm_add_material_textured)."""
         self.materials.append((mtype, rgb if isinstance(rgb, Tex) else np.asarray(rgb, np.float32)))
+        return len(self.materials) - 1
+
+    def material_specular(self, mtype, kr, kt=(1.0, 1.0, 1.0), index=1.5):
+        """A PM_MIRROR or PM_GLASS of the physical model (pm_add_material_specular): Fresnel glass with the
+        lobes kr, kt and its own index, or a mirror that reflects kr."""
+        self.materials.append((mtype, Spec(np.asarray(kr, np.float32), np.asarray(kt, np.float32), float(index))))
         return len(self.materials) - 1
 
     def texture_image(self, array, wrap="repeat", mapping=(1.0, 1.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0)):
@@ -160,10 +174,16 @@ class Scene:
         if self.textures and not hasattr(api, "add_texture_image"):
             raise NotImplementedError(f"{type(api).__name__} has no textures (pm_add_texture_*); every material "
                                       "is one constant colour there, as in the reference")
+        if any(isinstance(rgb, Spec) for _, rgb in self.materials) and not hasattr(api, "add_material_specular"):
+            raise NotImplementedError(f"{type(api).__name__} has no physical specular model "
+                                      "(pm_add_material_specular); a mirror reflects everything and glass "
+                                      "refracts with 1.5 there, as in the reference")
         tex_ids = self._load_textures(api) if self.textures else []
         for mtype, rgb in self.materials:
             if isinstance(rgb, Tex):
                 api.add_material_textured(mtype, tex_ids[rgb.index])
+            elif isinstance(rgb, Spec):
+                api.add_material_specular(mtype, rgb.kr, rgb.kt, rgb.index)
             else:
                 api.add_material(mtype, rgb)
         for m in self.meshes:
@@ -459,6 +479,19 @@ def caustic_scene(W=256, H=256, mirror=True):
         mir = s.material(PM_MIRROR, (0.9, 0.9, 0.9))
         o2w, w2o = translate(150.0, 90.0, 380.0)
         s.spheres.append((np.float32(90.0), o2w, w2o, mir, -1))
+    return s
+
+
+def caustic_fresnel(W=256, H=256):
+    """caustic_scene with the physical specular model (pm_add_material_specular): a Fresnel glass sphere
+    (Kr = Kt = 1, index 1.5) and a mirror sphere that reflects 90 %."""
+    s = cornell_box(W, H, blocks=False)
+    glass = s.material_specular(PM_GLASS, (1.0, 1.0, 1.0), (1.0, 1.0, 1.0), 1.5)
+    o2w, w2o = translate(370.0, 100.0, 250.0)
+    s.spheres.append((np.float32(100.0), o2w, w2o, glass, -1))
+    mir = s.material_specular(PM_MIRROR, (0.9, 0.9, 0.9))
+    o2w, w2o = translate(150.0, 90.0, 380.0)
+    s.spheres.append((np.float32(90.0), o2w, w2o, mir, -1))
     return s
 
 

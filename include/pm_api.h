@@ -218,6 +218,50 @@ int pm_add_texture_checker(void *ctx, const float mapping[4], int tex1, const fl
                            const float rgb2[3], int *out_tex);
 int pm_add_texture_scale(void *ctx, int tex1, const float rgb1[3], int tex2, const float rgb2[3], int *out_tex);
 int pm_add_material_textured(void *ctx, int type, int kd_tex, int *out_id);
+/* A specular material of the physical model (ours, opt-in: pm_add_material's
+ * PM_MIRROR and PM_GLASS keep the reference's, which reflects 100 % and
+ * refracts with a fixed 1.5, never reflecting, a path ending at total internal
+ * reflection). type is PM_MIRROR (kt and index are not looked at) or PM_GLASS.
+ * Everything is fp32 without contraction, in the order written, in the local
+ * shading frame (wo = the direction back along the ray, cos = wo.z):
+ *   mirror: wi = (-wo.x, -wo.y, wo.z), weight Kr, no random number.
+ *   glass (pbrt-v2's FresnelDielectric(1, index), a specular reflection lobe
+ *   Kr and a specular transmission lobe Kt):
+ *     entering = wo.z > 0; ei = entering ? 1 : index; et = entering ? index : 1;
+ *     eta = ei / et; sini2 = max(0, 1 - wo.z^2); sint2 = eta^2 sini2;
+ *     sint2 >= 1 (total internal reflection): F = 1; else
+ *       cost = sqrt(max(0, 1 - sint2)), ci = |wo.z|,
+ *       rpar = (et ci - ei cost) / (et ci + ei cost),
+ *       rper = (ei ci - et cost) / (ei ci + et cost), F = 0.5 (rpar^2 + rper^2);
+ *     wr = F Kr, wt = (1 - F) Kt; both black: the path or chain ends.
+ *     q = 1 if wt is black, 0 if wr is black, else F. One uniform u is always
+ *     drawn; the step reflects iff u < q. For 0 < q < 1 its weight is Kr
+ *     (reflected) or Kt (transmitted) exactly, the probability cancelling;
+ *     otherwise wr or wt. Reflected wi: the mirror's; transmitted wi:
+ *     (eta -wo.x, eta -wo.y, entering ? -cost : cost).
+ * A photon path carries flux: alpha *= weight, with no index scaling (pbrt-v2
+ * scales photons by (ei / et)^2 as well; pbrt-v3 corrected that, and we follow
+ * v3). An eye chain carries radiance: it follows one branch per eye sample
+ * (the camera's strata average the branches) and keeps an rgb throughput T,
+ * T *= weight, and for a transmitted step T *= eta^2. The record then holds
+ * dl = T L (emitted term included) and the albedo factor T x (the texel, or
+ * 1) (pm_download_record_albedo). A chain that runs past max_specular_depth
+ * or whose lobes are both black ends as PM_REC_EXCEPTION. pm_render_simple
+ * follows no chain.
+ * Random numbers, u = pmdm_u01(o[0]) of pmdm_philox4x32_10(counter; key):
+ *   photon: (pm_index + nI, pass, spec, 0; rng_seed, 0): pm_index = path id x
+ *     max_photon_count, nI the path's deposit counter at the hit (>= 1: a
+ *     path's first hit makes it 1 before the draw, so no two paths share a
+ *     counter), spec the path's specular count including this hit (>= 1; the
+ *     Lambert bounce draws with 0 there).
+ *   eye: (lo32(q), hi32(q), 2, depth; light_rng_seed, 0): q the sample or
+ *     record index that keys the light samples, depth the chain's depth
+ *     including this hit (the camera draws with word 2 = 1, the light samples
+ *     with word 2 = 0).
+ * Both models may share a scene. PM_ERR_INVALID: a null pointer, another
+ * type, a colour component that is negative or not finite, an index that is
+ * not finite or <= 0; checked before the context is. */
+int pm_add_material_specular(void *ctx, int type, const float kr[3], const float kt[3], float index, int *out_id);
 /* World-space mesh (pbrt TriangleMesh::p is already world space,
  * cudatrianglemesh.cpp:24-30). N and uv may be NULL. light_index = index of
  * the area light this shape emits for, -1 otherwise. */
@@ -491,10 +535,12 @@ int pm_download_slots(void *ctx, pm_photon *out, int64_t n);
 int pm_upload_slots(void *ctx, const pm_photon *in, int64_t n);
 int pm_download_records(void *ctx, pm_record *out, int64_t n);
 int pm_upload_records(void *ctx, const pm_record *in, int64_t n); /* leaves the albedo factors below as they are */
-/* Scenes with a textured material only (else PM_ERR_INVALID): per record the
- * rgb factor pm_final applies to the indirect term, written by pm_eye_pass:
- * the texel at a textured matte hit, (1, 1, 1) on any other surface (whose Kd
- * the gather already applied), 0 for an inactive record. Final radiance:
+/* Scenes with a textured material or one of pm_add_material_specular only
+ * (else PM_ERR_INVALID): per record the rgb factor pm_final applies to the
+ * indirect term, written by pm_eye_pass: the texel at a textured matte hit,
+ * (1, 1, 1) on any other surface (whose Kd the gather already applied), times
+ * the throughput T of the record's specular chain (pm_add_material_specular);
+ * 0 for an inactive record. Final radiance:
  * PPM dl + (factor flux) (1 / pi) / (radius2 emitted), kNN dl + flux / emitted
  * (Kd / pi factor). Upload takes n = pm_num_records values. */
 int pm_download_record_albedo(void *ctx, float *out_rgb, int64_t n);
@@ -548,6 +594,10 @@ int pm_scene_info(void *ctx, int64_t out[7]);
  * material the int index of its Kd texture (-1: none) */
 #define PM_SCENE_TEXTURES 11
 #define PM_SCENE_MAT_TEX 12
+/* scenes with a material of pm_add_material_specular (else empty): 32 B per
+ * material, (Kr rgb, index) (Kt rgb, 1 as int bits) for such a material (a
+ * mirror's Kt and index are stored as 0), all zero for any other */
+#define PM_SCENE_MAT_SPEC 13
 int pm_scene_section(void *ctx, int section, void *out, int64_t max_bytes, int64_t *bytes);
 /* the current photon map (pm_build_photon_map; the reference's
  * CreatePhotonMap, photonmappingrenderer.cpp:150-180): [0] structure
