@@ -144,10 +144,7 @@ struct SceneDev {
     uint32_t lds_bytes; /* = blob_bytes when the blob fits LDS_SCENE_MAX (LDS-resident mode), else 0 */
 };
 
-/* how the kernels see the scene (template argument of the traversal kernels) */
-enum SceneMode : int { MODE_GLOBAL = 0, MODE_LDS = 1, MODE_BRUTE = 2, MODE_INST = 3 };
-/* MODE_INST: a MODE_GLOBAL scene with object instances (two-level 4-wide trees) */
-constexpr bool mode_lds(int mode) { return mode == MODE_LDS || mode == MODE_BRUTE; }
+/* SceneMode, mode_lds: pm_scene_pod.h */
 
 struct Ray { v3 o, d; float tmin, tmax; };
 

@@ -1,6 +1,6 @@
 /*
  * pm_kernels.h — kernel parameter blocks and launcher declarations shared by
- * the host orchestration (pm_api.cpp) and the HIP kernels (pm_trace.hip, pm_bucket.hip, pm_gather.hip,
+ * the host orchestration (pm_api*.cpp around pm_ctx.h) and the HIP kernels (pm_trace.hip, pm_bucket.hip, pm_gather.hip,
  * pm_gather_knn.hip, pm_records.hip).
  */
 #pragma once
@@ -12,6 +12,9 @@
 #include "pm_plan_pod.h"
 
 namespace pm {
+
+enum TraceFamily : int; /* pm_plan.h (host only): the trace launch's plan */
+struct TracePlan;
 
 /* Stage timing without marker packets: the API (pm_api.cpp timer_begin /
  * timer_end) points g_stage at an event pair around one stage, and every
@@ -34,7 +37,7 @@ inline void pm_launch(F kernel, dim3 grid, dim3 block, uint32_t shmem, hipStream
 }
 
 constexpr int EYE_BLOCK = 128;     /* traversal kernels: LDS stack column per lane */
-constexpr int TRACE_BLOCK = 256;    /* k_trace: 4 waves compact paths together */
+/* TRACE_BLOCK: pm_plan_pod.h */
 constexpr int GATHER_BLOCK = 256;
 /* k_gather_tile: waves per block. Its waves never synchronise with each
  * other, and a block's LDS is held until its last wave ends, so with several
@@ -317,14 +320,14 @@ hipError_t launch_camera_rays(const EyeParams &p, int64_t first, int64_t count, 
 /* the film (pm_film.hip): fills hx / hy / row_w / band_rows of p itself */
 hipError_t launch_film(FilmParams p, hipStream_t s);
 /* writes every slot of its paths (deposits, then zeros); count: census */
-/* resident waves of k_trace_pool per CU with `lds` bytes of dynamic LDS per block */
-int trace_pool_waves_per_cu(size_t lds, int hold, int w8 = 0);
+/* pm_plan.h's WavesPerCu from the occupancy API: resident waves per CU of a trace kernel family */
+int trace_waves_per_cu(TraceFamily family, bool hold, size_t lds);
 size_t scan_scratch_words(int64_t n);
-int trace_lane_waves_per_cu(const SceneDev &S, size_t lds, int hold);
 /* adaptive-grid histogram: sum the R2_COPIES copies into host-mapped
  * out[R2_BINS] with plain stores (no copy engine) and zero the copies */
 hipError_t launch_r2hist_reduce(uint32_t *hist, uint32_t *out_mapped, hipStream_t s);
-hipError_t launch_trace(const TraceParams &p, int count, hipStream_t s);
+/* kernel, grid and LDS bytes from pl, the plan p was filled from */
+hipError_t launch_trace(const TraceParams &p, const TracePlan &pl, int count, hipStream_t s);
 /* photon-bucket build (pm_bucket.hip): count + rank, scan, fill.
  * count and cell_start have ncells + 1 entries; cell_start[ncells] = valid
  * photons; scratch holds bucket_scratch_words() uint32: key[n], rank[n], ...

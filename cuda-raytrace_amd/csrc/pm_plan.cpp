@@ -89,4 +89,69 @@ std::vector<std::vector<std::pair<int64_t, int64_t>>> device_bands(int64_t n, in
     return owned;
 }
 
+/* the dynamic LDS of a trace block, the one place its bytes are written
+ * down: a stack column per thread, then (per-lane kernels) the scene blob,
+ * then (HOLD) the held deposits' columns from the next 16-B boundary */
+static size_t stack_bytes(int entries) { return (size_t)entries * TRACE_BLOCK * 4; }
+static size_t hold_bytes() { return (size_t)HOLD_WORDS * TRACE_BLOCK * 4; }
+static size_t lane_lds(const TraceShape &sh, bool hold) {
+    const size_t lds = stack_bytes(sh.stack_depth) + sh.lds_bytes;
+    return hold ? lds + ((size_t)sh.lds_bytes + 15u) / 16u * 16u - sh.lds_bytes + hold_bytes() : lds;
+}
+static TraceFamily lane_family(int mode) {
+    return mode == MODE_BRUTE ? TRACE_LANE_BRUTE : mode == MODE_LDS ? TRACE_LANE_LDS : mode == MODE_INST ? TRACE_LANE_INST : TRACE_LANE_GLOBAL;
+}
+
+TracePlan plan_trace(const TraceShape &sh, const WavesPerCu &waves_per_cu) {
+    constexpr int64_t block_waves = TRACE_BLOCK / 64;
+    TracePlan pl;
+    pl.hold = sh.trace_hold ? 1 : 0;
+    if (pl.hold && !sh.wide) { /* per-lane kernel: only when the held deposits' LDS costs no resident waves */
+        const TraceFamily asked = sh.mode == MODE_INST ? TRACE_LANE_GLOBAL : lane_family(sh.mode);
+        if (waves_per_cu(asked, true, lane_lds(sh, true)) < waves_per_cu(asked, false, lane_lds(sh, false))) pl.hold = 0;
+    }
+    if (sh.wide) {
+        /* pooled kernel: one occupancy round (resident waves per CU: VGPRs
+         * and the LDS stacks), each wave with a contiguous pool of paths. C3
+         * sweep (1M paths, 256 CUs): 4096 waves 5.25 ms, 8192 (two rounds)
+         * 5.81, 5462 (1.33 rounds) 6.73, 2048 7.22 */
+        /* LDS stack entries per lane (pool_stack; 0 = the tree's exact
+         * bound): below the bound, deeper entries spill to global memory and
+         * the smaller LDS reservation admits more resident blocks */
+        pl.lstk = sh.pool_stack > 0 && sh.pool_stack < sh.stack_depth ? sh.pool_stack : sh.stack_depth;
+        const TraceFamily pool = sh.wide == 3 ? TRACE_POOL8 : TRACE_POOL;
+        const size_t asked = stack_bytes(pl.lstk) + sh.lds_bytes; /* with S.lds_bytes: see pm_plan.h */
+        int per_cu = waves_per_cu(pool, false, asked);
+        if (pl.hold) { /* the held deposits' LDS must not cost resident waves */
+            const int per_cu_h = waves_per_cu(pool, true, asked + hold_bytes());
+            if (per_cu_h < per_cu) pl.hold = 0;
+            else per_cu = per_cu_h;
+        }
+        const int64_t waves = (int64_t)(sh.cus > 0 ? sh.cus : 256) * (per_cu > 0 ? per_cu : 16);
+        /* any pool size works (the wave's cursor hands out paths to dead lanes) */
+        const int64_t per = std::max<int64_t>(1, (sh.path_count + waves - 1) / waves);
+        pl.pool_paths = sh.trace_pool || sh.wide == 3 ? per : 0;
+        pl.pooled = pl.pool_paths > 0 && sh.mode == MODE_GLOBAL;
+        const int64_t pool_blocks = ((sh.path_count + per - 1) / per + block_waves - 1) / block_waves;
+        if (pl.lstk < sh.stack_depth) {
+            pl.spill_entries = sh.stack_depth - pl.lstk;
+            pl.spill_stride = (uint32_t)(pool_blocks * TRACE_BLOCK);
+        }
+        if (pl.pooled) {
+            pl.family = pool;
+            pl.grid_blocks = pool_blocks;
+            pl.lds = stack_bytes(pl.lstk);
+            pl.lds_hold = pl.lds + hold_bytes();
+        }
+    }
+    if (!pl.pooled) {
+        pl.family = lane_family(sh.mode);
+        pl.grid_blocks = (sh.path_count + TRACE_BLOCK - 1) / TRACE_BLOCK;
+        pl.lds = lane_lds(sh, false);
+        pl.lds_hold = lane_lds(sh, true);
+    }
+    pl.hold_launch = pl.hold && sh.mpc == HOLD_MPC && sh.slots_aligned;
+    return pl;
+}
+
 } // namespace pm

@@ -1,18 +1,23 @@
 /*
  * pm_plan.h — pass planning: which photon grid a pass gets (the grid of a
- * radius, the adaptive radius and its state machine) and which record bands
- * a device of a group gathers. Host code only, no HIP: pm_api.cpp performs
- * the HIP call each answer asks for, and tests/native drives the same code
- * on a CPU (tests/test_pass_plan.py).
+ * radius, the adaptive radius and its state machine), which record bands
+ * a device of a group gathers, and the trace launch's geometry (TracePlan).
+ * Host code only, no HIP: pm_api_stage.cpp performs the HIP call each answer
+ * asks for, and tests/native drives the same code on a CPU
+ * (tests/test_pass_plan.py, tests/test_trace_plan.py).
  */
 #pragma once
 #include <stdint.h>
 
+#include <stddef.h>
+
+#include <functional>
 #include <utility>
 #include <vector>
 
 #include "../../include/pm_api.h"
 #include "pm_plan_pod.h"
+#include "pm_scene_pod.h"
 
 namespace pm {
 
@@ -85,5 +90,67 @@ struct R2Plan {
  * bands (`unit` records each) in runs dealt round-robin, about four runs per
  * device (pmrender/dist.py _bands; tests/test_pass_plan.py holds them equal) */
 std::vector<std::vector<std::pair<int64_t, int64_t>>> device_bands(int64_t n, int64_t unit, int world);
+
+/* ---- the trace launch ------------------------------------------------------
+ * One trace call's launch geometry, decided once: pm_trace_photons
+ * (pm_api_stage.cpp) fills TraceParams and sizes the spill buffer from it,
+ * launch_trace (pm_trace.hip) takes its kernel, grid and LDS bytes from it.
+ * The kernels index what it sizes: trace_lane_body / trace_pool_body
+ * (pm_trace.hip) derive the same lstk from TraceParams::pool_stack and
+ * S.stack_depth, lay the LDS out as [stacks][scene blob, per-lane LDS modes
+ * only][pad to 16 B][held deposits] and address the spill area by
+ * blockIdx.x * TRACE_BLOCK + threadIdx.x < spill_stride. */
+
+/* the kernel family whose resident waves are asked for / that launches */
+enum TraceFamily : int { TRACE_LANE_GLOBAL = 0, TRACE_LANE_LDS, TRACE_LANE_BRUTE, TRACE_LANE_INST, TRACE_POOL, TRACE_POOL8 };
+
+struct TraceShape {
+    int64_t path_count = 0;
+    int mpc = HOLD_MPC;        /* max_photon_count of the call */
+    bool slots_aligned = true; /* the slot buffer is 16-B aligned */
+    int mode = MODE_GLOBAL;    /* scene_mode(S) */
+    int wide = 0;              /* S.wide: 0 no wide tree, 1 / 2 a 4-wide one, 3 the 8-wide one */
+    int stack_depth = 2;       /* S.stack_depth: the traversal stack's bound */
+    uint32_t lds_bytes = 0;    /* S.lds_bytes */
+    int pool_stack = 31;       /* the context's settings (env PM_POOL_STACK, PM_TRACE_POOL, PM_TRACE_HOLD) */
+    bool trace_pool = true, trace_hold = true;
+    int cus = 0;               /* compute units of the device; <= 0: unknown, taken as 256 */
+};
+
+/* resident waves per CU of `family`'s HOLD (hold) or plain instantiation at
+ * `lds` bytes of dynamic LDS per block, all of it (the held deposits' share
+ * included); 0: unknown. The library asks the occupancy API
+ * (trace_waves_per_cu, pm_trace.hip), the CPU test a table. */
+using WavesPerCu = std::function<int(TraceFamily family, bool hold, size_t lds)>;
+
+struct TracePlan {
+    TraceFamily family = TRACE_LANE_GLOBAL; /* the kernel that launches */
+    bool pooled = false;      /* family is TRACE_POOL / TRACE_POOL8: pool_paths paths per wave; else one path per lane */
+    int lstk = 0;             /* TraceParams::pool_stack: LDS stack entries per lane of a scene with a wide tree
+                               * (pool_stack when set and below stack_depth, else stack_depth); 0 without one */
+    int64_t pool_paths = 0;   /* TraceParams::pool_paths */
+    int64_t grid_blocks = 0;  /* blocks of TRACE_BLOCK threads */
+    size_t lds = 0, lds_hold = 0; /* the launch's dynamic LDS bytes: per-deposit stores / held deposits */
+    int hold = 0;             /* TraceParams::hold: held deposits wanted and free of resident waves; the fused
+                               * counting's key layout and the lazy zero fill follow this one */
+    bool hold_launch = false; /* the HOLD instantiation launches (with lds_hold): hold, mpc == HOLD_MPC, aligned slots */
+    int spill_entries = 0;    /* stack entries per thread beyond lstk: TraceParams::spill holds spill_entries * spill_stride ints */
+    uint32_t spill_stride = 0; /* TraceParams::spill_stride (0 with no spill) */
+};
+
+/* Oddities of the launch as it was measured, kept:
+ *  - occupancy unknown (0) counts as 16 waves per CU, an unknown device as 256 CUs;
+ *  - the 8-wide tree always takes the pooled kernel (its deeper stacks need the spill), whatever trace_pool says;
+ *  - MODE_INST with a wide tree is planned like a pooled scene (lstk, pool_paths, hold, spill) but launches the
+ *    per-lane kernel (the pooled one walks one level), which reads none of the four;
+ * and where two sites disagreed, each keeps its value:
+ *  - the pooled occupancy is asked at stacks + S.lds_bytes, the pooled launch reserves the stacks alone (a pooled
+ *    launch has S.lds_bytes == 0: the two differ only where the per-lane kernel launches after all);
+ *  - `hold` stays set at another mpc or a misaligned slot buffer, where the launch stores per deposit
+ *    (hold_launch): the fused keys are then slot-major and not lazily zeroed, as for a held launch;
+ *  - a per-lane MODE_INST launch asks the occupancy of TRACE_LANE_GLOBAL;
+ *  - a wide scene launched per lane (MODE_INST, or trace_pool off) still gets the pooled geometry's spill_stride,
+ *    which is not its grid's thread count: the per-lane kernel has no spill. */
+TracePlan plan_trace(const TraceShape &sh, const WavesPerCu &waves_per_cu);
 
 } // namespace pm

@@ -1,6 +1,6 @@
 /*
  * pm_scene.h — the host scene and its assembly into the scene blob the
- * kernels read (SceneDev, pm_device.h). Host code only, no HIP: pm_api.cpp
+ * kernels read (SceneDev, pm_device.h). Host code only, no HIP: pm_api_scene.cpp
  * fills a HostScene through the pm_add_* calls; pm_commit makes the
  * primitive boxes, assembles the blob here (or lets the device build the
  * tree, with the same layout) and uploads it. tests/native checks the
@@ -175,7 +175,7 @@ int finish_lights(HostScene &hs, const float blo[3], const float bhi[3], float s
 
 /* --------------------------------------------------------------- textures */
 /* The pm_add_texture_* calls of pm_api.h. The check_* functions look at the
- * arguments alone (pm_api.cpp runs them before it touches the context); the
+ * arguments alone (pm_api_scene.cpp runs them before it touches the context); the
  * add_* ones repeat them, resolve operand ids against the scene and append
  * the record. An operand id names a TEX_SINGLE record (an image or a
  * constant); a checkerboard or a scale as an operand is refused. */

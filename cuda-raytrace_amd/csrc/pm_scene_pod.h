@@ -85,6 +85,11 @@ constexpr uint32_t LDS_SCENE_MAX = 16384;
  * tests every primitive (MODE_BRUTE) */
 constexpr int BRUTE_MAX_PRIMS = 64;
 
+/* how the kernels see the scene (template argument of the traversal kernels) */
+enum SceneMode : int { MODE_GLOBAL = 0, MODE_LDS = 1, MODE_BRUTE = 2, MODE_INST = 3 };
+/* MODE_INST: a MODE_GLOBAL scene with object instances (two-level 4-wide trees) */
+constexpr bool mode_lds(int mode) { return mode == MODE_LDS || mode == MODE_BRUTE; }
+
 constexpr int BVH_STACK_DEPTH = 48; /* LDS stack entries per lane (builder caps depth below it) */
 constexpr int BVH_STACK = BVH_STACK_DEPTH; /* >= max BVH depth (builder enforces it) */
 /* the 8-wide tree's exact stack bound (seven pushes per level) runs deeper:

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "pm_kernels.h"
+#include "pm_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -418,8 +419,7 @@ PMD void flush_rank(const TraceParams &P, PathState &st) {
  * C3). Registers were not an option: holding 36 words cost ~90 VGPRs in
  * the brute-force trace (4 -> 3 waves/SIMD). LDS: HOLD_WORDS x TRACE_BLOCK
  * words after the stacks and the scene blob, a column per thread. */
-constexpr int HOLD_MPC = 4;
-constexpr int HOLD_WORDS = 27; /* slots 0..2: p, alpha, wi */
+/* HOLD_MPC, HOLD_WORDS: pm_plan_pod.h */
 struct Held {
     uint32_t *col;    /* this thread's LDS column: word i at col[i * TRACE_BLOCK] */
     uint4 key, rank;  /* shift registers, .x the newest deposit's */
@@ -441,7 +441,7 @@ PMD void held_put(Held &h, const TraceParams &P, size_t slot, uint32_t k, v3 p, 
     h.rank = make_uint4(rank, h.rank.x, h.rank.y, h.rank.z);
 }
 /* the path's slot block (16-B aligned: 160 B per path from a 16-B aligned
- * buffer, launch_trace checks): slots 0..2 from LDS (zero past the n
+ * buffer, plan_trace's hold_launch): slots 0..2 from LDS (zero past the n
  * deposits), slot 3 zero unless its deposit was stored; with fused counting
  * the key and rank quads (key 0xffffffff past n) */
 PMD void held_write(const TraceParams &P, uint32_t pid, const Held &h, uint32_t n) {
@@ -699,7 +699,7 @@ PMD void trace_lane_body(const TraceParams &P) {
     const int64_t path = (int64_t)blockIdx.x * TRACE_BLOCK + tid;
     PathState st;
     Held held;
-    if (HOLD) /* after the stacks and the (16-B padded) scene blob */
+    if (HOLD) /* after the stacks and the (16-B padded) scene blob: the layout plan_trace (pm_plan.cpp lane_lds) sizes */
         held.col = reinterpret_cast<uint32_t *>(stk + P.S.stack_depth * TRACE_BLOCK + (mode_lds(MODE) ? (int)((P.S.lds_bytes + 15u) / 4u & ~3u) : 0)) + tid;
     prof.begin();
     if (path < P.path_count) {
@@ -773,7 +773,9 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
     const SceneDev &S = P.S;
     __syncthreads();
     int *stack = stk + tid;
-    /* LDS stack entries per lane (P.pool_stack, else the tree's bound); deeper ones spill to global memory */
+    /* LDS stack entries per lane (P.pool_stack, else the tree's bound); deeper ones spill to global memory.
+     * plan_trace (pm_plan.cpp) sizes the launch's LDS for this lstk (+ the held columns) and the spill
+     * area for grid x TRACE_BLOCK threads (P.spill_stride) */
     const int lstk = P.pool_stack > 0 && P.pool_stack < P.S.stack_depth ? P.pool_stack : P.S.stack_depth;
     const SpillStack sstk{stack, TRACE_BLOCK, lstk, P.spill, P.spill_stride, (uint32_t)(blockIdx.x * TRACE_BLOCK + tid)};
     typename std::conditional<COUNT != 0, Census, NoCensus>::type cen;
@@ -846,47 +848,29 @@ template <int COUNT, int HOLD, int ALL>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
 void k_trace_pool8_spec(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, true, true>(P); }
 
-/* resident waves of the pooled kernel per CU at this LDS size (0 if unknown) */
-int trace_pool_waves_per_cu(size_t lds, int hold, int w8) { /* lds: the stacks */
+/* resident waves per CU of a trace kernel family at `lds` bytes of dynamic
+ * LDS (0 if unknown): the occupancy plan_trace (pm_plan.h) asks for. The
+ * bytes are the plan's; this only picks the kernel */
+template <class K>
+static int kernel_waves_per_cu(K kernel, size_t lds) {
     int blocks = 0;
-    if (hold) lds += (size_t)HOLD_WORDS * TRACE_BLOCK * 4;
-    const hipError_t e =
-        w8 ? (hold ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_pool8<0, 1>, TRACE_BLOCK, lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_pool8<0, 0>, TRACE_BLOCK, lds))
-           : (hold ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_pool<0, 1>, TRACE_BLOCK, lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_pool<0, 0>, TRACE_BLOCK, lds));
-    if (e != hipSuccess) return 0;
-    return blocks * (TRACE_BLOCK / 64);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, TRACE_BLOCK, lds) == hipSuccess ? blocks * (TRACE_BLOCK / 64) : 0;
 }
-
-/* resident waves per CU of the per-lane kernel (scene mode of S) with or
- * without the held deposits' LDS: the host keeps HOLD only when it costs no
- * waves (C2: one occupancy round of 4,096 waves) */
-int trace_lane_waves_per_cu(const SceneDev &S, size_t lds, int hold) {
-    int blocks = 0;
-    hipError_t e;
+int trace_waves_per_cu(TraceFamily family, bool hold, size_t lds) {
+    if (family == TRACE_POOL8) return hold ? kernel_waves_per_cu(k_trace_pool8<0, 1>, lds) : kernel_waves_per_cu(k_trace_pool8<0, 0>, lds);
+    if (family == TRACE_POOL) return hold ? kernel_waves_per_cu(k_trace_pool<0, 1>, lds) : kernel_waves_per_cu(k_trace_pool<0, 0>, lds);
     if (hold) {
-        lds += ((size_t)S.lds_bytes + 15u) / 16u * 16u - S.lds_bytes + (size_t)HOLD_WORDS * TRACE_BLOCK * 4;
-        switch (scene_mode(S)) {
-        case MODE_BRUTE: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_lane<0, MODE_BRUTE, 1>, TRACE_BLOCK, lds); break;
-        case MODE_LDS: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_lane<0, MODE_LDS, 1>, TRACE_BLOCK, lds); break;
-        default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_lane<0, MODE_GLOBAL, 1>, TRACE_BLOCK, lds); break;
-        }
-    } else {
-        switch (scene_mode(S)) {
-        case MODE_BRUTE: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_lane<0, MODE_BRUTE, 0>, TRACE_BLOCK, lds); break;
-        case MODE_LDS: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_lane<0, MODE_LDS, 0>, TRACE_BLOCK, lds); break;
-        default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_lane<0, MODE_GLOBAL, 0>, TRACE_BLOCK, lds); break;
+        switch (family) {
+        case TRACE_LANE_BRUTE: return kernel_waves_per_cu(k_trace_lane<0, MODE_BRUTE, 1>, lds);
+        case TRACE_LANE_LDS: return kernel_waves_per_cu(k_trace_lane<0, MODE_LDS, 1>, lds);
+        default: return kernel_waves_per_cu(k_trace_lane<0, MODE_GLOBAL, 1>, lds);
         }
     }
-    return e == hipSuccess ? blocks * (TRACE_BLOCK / 64) : 0;
-}
-
-/* deposits held in registers and written per path (Held): the reference's
- * 4 photons per path, a 16-B aligned slot buffer; env PM_TRACE_HOLD=0 (read
- * by pm_api.cpp into TraceParams::hold) keeps the per-deposit stores */
-static bool trace_hold(const TraceParams &p) {
-    return p.hold && p.mpc == HOLD_MPC && ((uintptr_t)p.slots & 15u) == 0u;
+    switch (family) {
+    case TRACE_LANE_BRUTE: return kernel_waves_per_cu(k_trace_lane<0, MODE_BRUTE, 0>, lds);
+    case TRACE_LANE_LDS: return kernel_waves_per_cu(k_trace_lane<0, MODE_LDS, 0>, lds);
+    default: return kernel_waves_per_cu(k_trace_lane<0, MODE_GLOBAL, 0>, lds); /* the plan asks no other family */
+    }
 }
 
 /* MAT: which instantiations a scene runs: 0 = the plain ones, 1 = TEX (a
@@ -908,17 +892,17 @@ static auto pool_kernel() {
 }
 
 template <int HOLD, int ALL, int MAT>
-static void launch_lane(const TraceParams &p, dim3 grid, size_t lds, int count, hipStream_t s) {
-    switch (scene_mode(p.S)) {
-    case MODE_BRUTE:
+static void launch_lane(const TraceParams &p, TraceFamily family, dim3 grid, size_t lds, int count, hipStream_t s) {
+    switch (family) {
+    case TRACE_LANE_BRUTE:
         if (count) pm_launch((lane_kernel<1, MODE_BRUTE, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         else pm_launch((lane_kernel<0, MODE_BRUTE, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
-    case MODE_LDS:
+    case TRACE_LANE_LDS:
         if (count) pm_launch((lane_kernel<1, MODE_LDS, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         else pm_launch((lane_kernel<0, MODE_LDS, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
-    case MODE_INST: /* instances: the per-lane kernel (the pooled one walks only one level) */
+    case TRACE_LANE_INST: /* instances: the per-lane kernel (the pooled one walks only one level) */
         if (count) pm_launch((lane_kernel<1, MODE_INST, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         else pm_launch((lane_kernel<0, MODE_INST, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
         break;
@@ -931,44 +915,40 @@ static void launch_lane(const TraceParams &p, dim3 grid, size_t lds, int count, 
 
 /* the pooled kernels (4-wide: k_trace_pool; 8-wide: k_trace_pool8) */
 template <int ALL, int MAT>
-static void launch_pool(const TraceParams &p, dim3 grid, size_t lds, size_t lds_h, bool hold, int count, hipStream_t s) {
-    if (p.S.wide == 3) {
-        if (count && hold) pm_launch((pool_kernel<1, 1, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-        else if (count) pm_launch((pool_kernel<1, 0, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else if (hold) pm_launch((pool_kernel<0, 1, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-        else pm_launch((pool_kernel<0, 0, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-    } else if (count && hold) pm_launch((pool_kernel<1, 1, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-    else if (count) pm_launch((pool_kernel<1, 0, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-    else if (hold) pm_launch((pool_kernel<0, 1, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds_h, s, p);
-    else pm_launch((pool_kernel<0, 0, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
+static void launch_pool(const TraceParams &p, const TracePlan &pl, dim3 grid, int count, hipStream_t s) {
+    const bool hold = pl.hold_launch;
+    if (pl.family == TRACE_POOL8) {
+        if (count && hold) pm_launch((pool_kernel<1, 1, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds_hold, s, p);
+        else if (count) pm_launch((pool_kernel<1, 0, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds, s, p);
+        else if (hold) pm_launch((pool_kernel<0, 1, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds_hold, s, p);
+        else pm_launch((pool_kernel<0, 0, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds, s, p);
+    } else if (count && hold) pm_launch((pool_kernel<1, 1, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds_hold, s, p);
+    else if (count) pm_launch((pool_kernel<1, 0, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds, s, p);
+    else if (hold) pm_launch((pool_kernel<0, 1, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds_hold, s, p);
+    else pm_launch((pool_kernel<0, 0, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds, s, p);
 }
 
+/* kernel, grid and LDS bytes are the plan's (plan_trace, pm_plan.h: the one
+ * place they are computed); p carries the same plan's pool_stack, pool_paths,
+ * hold and spill_stride to the kernel */
 template <int MAT>
-static hipError_t launch_trace_mat(const TraceParams &p, int count, hipStream_t s) {
+static hipError_t launch_trace_mat(const TraceParams &p, const TracePlan &pl, int count, hipStream_t s) {
     /* PM_ALL_LIGHTS: the ALL instantiations; a fixed light is an index into S.lights */
     const bool all = p.light_index == PM_ALL_LIGHTS;
     if (all ? !p.light_cdf : p.light_index < 0 || p.light_index >= p.S.n_lights) return hipErrorInvalidValue;
-    if (p.pool_paths > 0 && scene_mode(p.S) == MODE_GLOBAL && p.S.wide) {
-        const int lstk = p.pool_stack > 0 && p.pool_stack < p.S.stack_depth ? p.pool_stack : p.S.stack_depth;
-        if (lstk < p.S.stack_depth && !p.spill) return hipErrorInvalidValue;
-        const size_t lds = (size_t)lstk * TRACE_BLOCK * 4;
-        const int64_t waves = (p.path_count + p.pool_paths - 1) / p.pool_paths;
-        const unsigned grid = (unsigned)((waves + TRACE_BLOCK / 64 - 1) / (TRACE_BLOCK / 64));
-        const bool hold = trace_hold(p);
-        const size_t lds_h = lds + (hold ? (size_t)HOLD_WORDS * TRACE_BLOCK * 4 : 0);
-        if (all) launch_pool<1, MAT>(p, dim3(grid), lds, lds_h, hold, count, s);
-        else launch_pool<0, MAT>(p, dim3(grid), lds, lds_h, hold, count, s);
+    const dim3 grid((unsigned)pl.grid_blocks);
+    if (pl.pooled) {
+        if (pl.spill_entries > 0 && !p.spill) return hipErrorInvalidValue;
+        if (all) launch_pool<1, MAT>(p, pl, grid, count, s);
+        else launch_pool<0, MAT>(p, pl, grid, count, s);
         return hipGetLastError();
     }
     /* one path per lane */
-    const size_t lds = (size_t)p.S.stack_depth * TRACE_BLOCK * 4 + p.S.lds_bytes;
-    const unsigned grid = (unsigned)((p.path_count + TRACE_BLOCK - 1) / TRACE_BLOCK);
-    const size_t lds_h = lds + ((size_t)p.S.lds_bytes + 15u) / 16u * 16u - p.S.lds_bytes + (size_t)HOLD_WORDS * TRACE_BLOCK * 4;
-    if (trace_hold(p)) {
-        if (all) launch_lane<1, 1, MAT>(p, dim3(grid), lds_h, count, s);
-        else launch_lane<1, 0, MAT>(p, dim3(grid), lds_h, count, s);
-    } else if (all) launch_lane<0, 1, MAT>(p, dim3(grid), lds, count, s);
-    else launch_lane<0, 0, MAT>(p, dim3(grid), lds, count, s);
+    if (pl.hold_launch) {
+        if (all) launch_lane<1, 1, MAT>(p, pl.family, grid, pl.lds_hold, count, s);
+        else launch_lane<1, 0, MAT>(p, pl.family, grid, pl.lds_hold, count, s);
+    } else if (all) launch_lane<0, 1, MAT>(p, pl.family, grid, pl.lds, count, s);
+    else launch_lane<0, 0, MAT>(p, pl.family, grid, pl.lds, count, s);
     return hipGetLastError();
 }
 
@@ -976,10 +956,10 @@ static hipError_t launch_trace_mat(const TraceParams &p, int count, hipStream_t 
  * runs the SPEC instantiations, one with a textured material
  * (SceneDev::tex_recs) the TEX ones; every other scene the kernels it ran
  * before either existed */
-hipError_t launch_trace(const TraceParams &p, int count, hipStream_t s) {
+hipError_t launch_trace(const TraceParams &p, const TracePlan &pl, int count, hipStream_t s) {
     if (p.path_count <= 0) return hipSuccess;
-    if (p.S.mat_spec) return p.S.mat_tex ? launch_trace_mat<2>(p, count, s) : hipErrorInvalidValue;
-    return p.S.tex_recs ? launch_trace_mat<1>(p, count, s) : launch_trace_mat<0>(p, count, s);
+    if (p.S.mat_spec) return p.S.mat_tex ? launch_trace_mat<2>(p, pl, count, s) : hipErrorInvalidValue;
+    return p.S.tex_recs ? launch_trace_mat<1>(p, pl, count, s) : launch_trace_mat<0>(p, pl, count, s);
 }
 
 } // namespace pm

@@ -1,5 +1,5 @@
 """The committed scene blob, byte for byte (pm_commit: csrc/pm_scene.cpp's
-host assembly and pm_api.cpp's device-build path): scene_info and a sha256 of
+host assembly and pm_api_scene.cpp's device-build path): scene_info and a sha256 of
 every section the binding exposes equal tests/golden/scene_sections.json,
 recorded before scene assembly moved out of pm_api.cpp. The scenes are the
 smallest that reach each assembly path (id order + triangle pairs, mesh

@@ -450,6 +450,29 @@ def test_every_traversal_mode_gives_the_same_records_albedo_and_slots(monkeypatc
             assert a.tobytes() == b.tobytes(), f"{mode} {env}: {what} differ from the brute-force scene's"
 
 
+@pytest.mark.parametrize("bvh8", ["0", "1"])
+def test_pool_stack_spill_leaves_the_slots_unchanged(monkeypatch, bvh8):
+    """The pooled trace keeps PM_POOL_STACK traversal-stack entries per lane in LDS and spills deeper ones to
+    global memory (pm_device.h SpillStack; sized by pm_plan.cpp plan_trace). PM_POOL_STACK=0 reserves the tree's
+    exact bound: no spill. PM_POOL_STACK=1 is the smallest cap SpillStack supports by its code (entry i < cap in
+    LDS, every other one in the spill area; a cap of 0 means `the exact bound` to plan_trace), and it is below
+    every tree's bound: fill_scene_dev sets S.stack_depth = max(2, the wide tree's stack bound + 1), and the
+    tree here is at least three levels deep (scene_info), so a ray that hits two children of a node on two
+    levels in a row holds a second entry. Same paths, same traversal order: the slots must not differ by a bit."""
+    for k in ("PM_BVH8", "PM_BVH_BUILD", "PM_TRACE_POOL", "PM_TRACE_HOLD", "PM_BVH_GPU_MIN", "PM_POOL_STACK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("PM_BVH8", bvh8)
+    sc = padded(300)
+    info = sc.load_into(hip.Context(0)).scene_info()
+    assert info["mode"] == "bvh-hbm" and info["bvh_depth"] >= 3, info
+    slots = {}
+    for cap in ("0", "1"):
+        monkeypatch.setenv("PM_POOL_STACK", cap)
+        slots[cap] = mode_result(sc, "bvh-hbm")[2]
+    assert (slots["0"]["bits"] & 1).sum() > PATHS
+    assert slots["1"].tobytes() == slots["0"].tobytes(), f"bvh8={bvh8}: the spilled stack changed the photon slots"
+
+
 # ---- sphere and disk ---------------------------------------------------------------------------
 SPH_C, SPH_R = (150.0, 90.0, 220.0), 80.0
 DISK_O, DISK_R = (400.0, 150.0, 500.0), 110.0  # upright, facing the camera
