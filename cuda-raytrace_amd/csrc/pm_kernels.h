@@ -1,7 +1,7 @@
 /*
  * pm_kernels.h — kernel parameter blocks and launcher declarations shared by
- * the host orchestration (pm_api*.cpp around pm_ctx.h) and the HIP kernels (pm_trace.hip, pm_bucket.hip, pm_gather.hip,
- * pm_gather_knn.hip, pm_records.hip).
+ * the host orchestration (pm_api*.cpp around pm_ctx.h) and the HIP kernels (pm_trace.hip, pm_eye.hip, pm_bucket.hip,
+ * pm_gather.hip, pm_gather_knn.hip, pm_records.hip, pm_bvh_gpu.hip, pm_film.hip).
  */
 #pragma once
 #include <hip/hip_ext.h>
@@ -113,30 +113,6 @@ PMD void camera_randoms(const CameraDev &C, int64_t q, float *ju, float *jv, flo
 PMD void camera_film_xy(const CameraDev &C, int ix, int iy, float ju, float jv, float *fx, float *fy) {
     *fx = ((float)ix + ju) / (float)C.xs;
     *fy = ((float)iy + jv) / (float)C.ys;
-}
-/* The camera ray of sample (ix, iy) of the WS x HS raster, in the order of
- * operations pm_api.h pins: shared by k_eye, k_simple and k_camera_rays. */
-PMD void camera_ray(const CameraDev &C, float4 eye4, float4 fwd4, float4 right4, float4 up4, int WS, int HS, int ix,
-                    int iy, v3 *o, v3 *d, float *fx, float *fy) {
-    float ju, jv, lu, lv;
-    camera_randoms(C, (int64_t)iy * WS + ix, &ju, &jv, &lu, &lv);
-    camera_film_xy(C, ix, iy, ju, jv, fx, fy);
-    const v3 eye = xyz(eye4), fwd = xyz(fwd4), right = xyz(right4), up = xyz(up4);
-    const float sx = (2.0f * ((float)ix + ju)) / (float)WS - 1.0f;
-    const float sy = 1.0f - (2.0f * ((float)iy + jv)) / (float)HS;
-    const v3 d0 = fwd + sx * right + sy * up;
-    if (C.lens_radius > 0.0f) {
-        float cx, cy;
-        concentric_sample_disk(lu, lv, &cx, &cy);
-        const v3 ol = eye + C.lens_radius * (cx * normalize(right) + cy * normalize(up));
-        const float ft = C.focal / sqrtf(dot(fwd, fwd));
-        const v3 pf = eye + d0 * ft;
-        *o = ol;
-        *d = normalize(pf - ol);
-    } else {
-        *o = eye;
-        *d = normalize(d0);
-    }
 }
 
 /* the film (pm_film.hip k_film): one workgroup per FILM_TILE x FILM_TILE

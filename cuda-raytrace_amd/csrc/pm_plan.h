@@ -109,7 +109,7 @@ struct TraceShape {
     int mpc = HOLD_MPC;        /* max_photon_count of the call */
     bool slots_aligned = true; /* the slot buffer is 16-B aligned */
     int mode = MODE_GLOBAL;    /* scene_mode(S) */
-    int wide = 0;              /* S.wide: 0 no wide tree, 1 / 2 a 4-wide one, 3 the 8-wide one */
+    int wide = 0;              /* S.wide: 0 no wide tree, 2 the 4-wide one, 3 the 8-wide one */
     int stack_depth = 2;       /* S.stack_depth: the traversal stack's bound */
     uint32_t lds_bytes = 0;    /* S.lds_bytes */
     int pool_stack = 31;       /* the context's settings (env PM_POOL_STACK, PM_TRACE_POOL, PM_TRACE_HOLD) */

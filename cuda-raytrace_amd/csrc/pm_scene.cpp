@@ -240,7 +240,7 @@ BuildOptions build_options_from_env() {
 
 bool gpu_bvh_wanted(const BuildOptions &opt, int64_t nprims) {
     const bool want = opt.build == "gpu" ? nprims >= 2 : (opt.build == "auto" && nprims >= opt.gpu_min);
-    if (!want || PM_BVH4_QUANT == 0) return false;
+    if (!want) return false;
     /* the breadth-first renumbering of the host tree is a host-path switch */
     return !opt.bfs_set;
 }
@@ -425,7 +425,7 @@ int assemble_scene(const HostScene &hs, std::vector<BuildPrim> &prims, const Bui
      * node fetches per ray; binary leaves of one primitive);
      * instanced scenes always (their objects' trees are 4-wide) */
     std::vector<uint32_t> qn; /* the wide tree's quantized nodes */
-    Bvh4Out w;                /* ... or its float nodes (PM_BVH4_QUANT=0 builds) */
+    Bvh4Out w;                /* the collapsed tree the quantizer reads */
     if (opt.bvh8 && ni == 0 && hbm) {
         collapse_bvh8(bvh, 1, w);
         if (quantize_bvh8(w.nodes, bvh.refs, qn) && w.max_stack <= BVH8_STACK) {
@@ -440,17 +440,15 @@ int assemble_scene(const HostScene &hs, std::vector<BuildPrim> &prims, const Bui
         w = Bvh4Out();
         collapse_bvh4(bvh, 1, w);
         if (ptimes) fprintf(stderr, "pm_commit: collapse %.1f ms\n", tms(t_c0, tnow()));
-        /* node format fixed at build time (pm_scene_pod.h PM_BVH4_QUANT) */
-        const bool quant = PM_BVH4_QUANT != 0;
         /* a leaf the quantized count cannot code (>= LEAF_TRIS primitives,
          * possible at build_bvh's depth limit) keeps the binary traversal,
          * like a tree whose stack bound exceeds BVH_STACK */
         if (opt.bfs) bvh4_bfs_order(w.nodes);
         const auto t_q0 = tnow();
         qn.clear();
-        const bool coded = !quant || quantize_bvh4(w.nodes, bvh.refs, qn);
+        const bool coded = quantize_bvh4(w.nodes, bvh.refs, qn);
         if (ptimes) fprintf(stderr, "pm_commit: quantize %.1f ms\n", tms(t_q0, tnow()));
-        if (ni > 0 && !(coded && quant && w.max_stack + IL.max_stack + 1 <= BVH_STACK))
+        if (ni > 0 && !(coded && w.max_stack + IL.max_stack + 1 <= BVH_STACK))
             return fail(err, "instanced scene: top-level tree not codable (stack %d + %d)", w.max_stack, IL.max_stack);
         if (coded && w.max_stack <= BVH_STACK) {
             if (ni > 0) { /* the objects' nodes follow the top-level tree's */
@@ -460,14 +458,13 @@ int assemble_scene(const HostScene &hs, std::vector<BuildPrim> &prims, const Bui
                 qn.insert(qn.end(), IL.qn.begin(), IL.qn.end());
                 L.size[SEC_INSTS] = vbytes(IL.insts);
             }
-            L.wide = quant ? 2 : 1;
+            L.wide = 2;
             L.wide_stack = w.max_stack + (ni > 0 ? IL.max_stack : 0);
-            out.bvh4_nodes = (int64_t)(quant ? qn.size() / 16 : w.nodes.size() / 32);
+            out.bvh4_nodes = (int64_t)(qn.size() / 16);
             out.bvh4_depth = w.depth;
         }
     }
-    const void *wsrc = L.wide == 1 ? (const void *)w.nodes.data() : (const void *)qn.data();
-    L.size[SEC_WNODES] = L.wide == 0 ? 0 : L.wide == 1 ? vbytes(w.nodes) : vbytes(qn);
+    L.size[SEC_WNODES] = L.wide == 0 ? 0 : vbytes(qn);
     /* instanced scenes never go LDS-resident (MODE_INST walks the 4-wide trees from HBM) */
     plan_layout(L, ni > 0);
 
@@ -483,7 +480,7 @@ int assemble_scene(const HostScene &hs, std::vector<BuildPrim> &prims, const Bui
     src[SEC_OBJV] = IL.objv.data(); src[SEC_OBJINFO] = IL.objinfo.data();
     src[SEC_OBJN] = IL.objn.data(); src[SEC_OBJUV] = IL.objuv.data();
     src[SEC_OBJMESH] = IL.objmesh.data(); src[SEC_INSTS] = IL.insts.data();
-    src[SEC_WNODES] = wsrc;
+    src[SEC_WNODES] = qn.data();
     for (int s = 0; s < SEC_COUNT; ++s)
         if (L.size[s]) std::memcpy(&out.bytes[L.off[s]], src[s], L.size[s]);
 

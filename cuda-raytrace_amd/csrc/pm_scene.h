@@ -103,9 +103,9 @@ enum SceneSection {
 /* bytes per element of a section */
 constexpr size_t NODE_BYTES = 64, REF_BYTES = 4, TRI_GEO_BYTES = 48, TRI_SHADE_BYTES = 32, TRI_ID_BYTES = 4,
                  TRI_INFO_BYTES = 16, NODE_PLACEHOLDER_BYTES = 16 /* a scene without a binary tree */, INST_BYTES = 128, OBJ_TRI_BYTES = 48, BVH4Q_NODE_BYTES = 64,
-                 BVH4F_NODE_BYTES = 128, BVH8Q_NODE_BYTES = 128;
+                 BVH8Q_NODE_BYTES = 128;
 constexpr size_t TRI_GEO_FLOATS = TRI_GEO_BYTES / 4, TRI_SHADE_FLOATS = TRI_SHADE_BYTES / 4, TRI_INFO_INTS = TRI_INFO_BYTES / 4;
-constexpr size_t wide_node_bytes(int wide) { return wide == 2 ? BVH4Q_NODE_BYTES : wide == 3 ? BVH8Q_NODE_BYTES : BVH4F_NODE_BYTES; }
+constexpr size_t wide_node_bytes(int wide) { return wide == 3 ? BVH8Q_NODE_BYTES : BVH4Q_NODE_BYTES; }
 
 /* where each section of the scene blob lies. One blob of 16-B aligned
  * sections: the same offsets address it in HBM and, for scenes that fit

@@ -1,7 +1,7 @@
 /*
  * pm_scene_pod.h — the plain structs and constants of the committed scene
- * that both the kernels (pm_device.h, pm_kernels.h) and the host-only scene
- * assembly (pm_scene.h) read. A HIP translation unit includes it after
+ * that both the kernels (pm_device.h, pm_shade.h, pm_kernels.h) and the
+ * host-only scene assembly (pm_scene.h) read. A HIP translation unit includes it after
  * hip_runtime.h and gets HIP's float4 / int4; a plain C++ unit gets the two
  * stand-ins below, laid out the same (four 32-bit lanes x y z w, 16-B
  * aligned), so the structs have one layout on both sides. The two kinds of
@@ -17,10 +17,6 @@ struct alignas(16) int4 { int x, y, z, w; };
 #endif
 static_assert(sizeof(float4) == 16 && alignof(float4) == 16 && sizeof(int4) == 16 && alignof(int4) == 16,
               "float4 / int4: four lanes, 16-B aligned");
-
-#ifndef PM_BVH4_QUANT
-#define PM_BVH4_QUANT 1 /* build-time node format: 1 = quantized 64-B nodes, 0 = 128-B float nodes */
-#endif
 
 namespace pm {
 

@@ -1,6 +1,6 @@
 /*
- * pm_texture.h — device-side texture lookup (included by pm_device.h after
- * SceneDev): the (u, v) of a triangle hit and tex_eval, which maps a texture
+ * pm_texture.h — device-side texture lookup (included at the end of
+ * pm_shade.h): the (u, v) of a triangle hit and tex_eval, which maps a texture
  * record (pm_scene_pod.h TexRec) and (u, v) to the rgb of a matte Kd. The
  * photon bounce, the eye pass and the simple renderer all call it.
  *

@@ -43,7 +43,7 @@ RECORD_DTYPE = np.dtype([
     ("flux", "<f4", 3), ("radius2", "<f4"), ("dl", "<f4", 3), ("photon_count", "<f4"),
 ])
 assert RECORD_DTYPE.itemsize == 64
-# one emitting triangle of a mesh light (PM_SCENE_LIGHT_TRIS; pm_device.h LightTri), 64 B
+# one emitting triangle of a mesh light (PM_SCENE_LIGHT_TRIS; pm_scene_pod.h LightTri), 64 B
 LIGHT_TRI_DTYPE = np.dtype([("p0", "<f4", 3), ("cdf", "<f4"), ("e1", "<f4", 4), ("e2", "<f4", 4), ("n", "<f4", 4)])
 assert LIGHT_TRI_DTYPE.itemsize == 64
 # one texture record (PM_SCENE_TEXTURES; pm_scene_pod.h TexRec), 128 B: an operand is a constant rgb

@@ -567,7 +567,7 @@ int pm_trace_counters(void *ctx, int64_t out[4]);
 int pm_scene_info(void *ctx, int64_t out[7]);
 /* diagnostics: one section of the committed scene as the kernels read it
  * (refs; per storage slot the triangle records geo 48 B, shade 32 B, id,
- * info 16 B; the 4-wide nodes, 64 B quantized or 128 B float). *bytes = its
+ * info 16 B; the quantized wide nodes, 64 B 4-wide or 128 B 8-wide). *bytes = its
  * size; out may be null to query it, else max_bytes must hold it. Lets a
  * test compare the device-built tree with its host restatement. */
 #define PM_SCENE_REFS 0

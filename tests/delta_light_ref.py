@@ -1,5 +1,5 @@
 """float64 numpy restatement of the distant light (include/pm_api.h
-pm_add_light_distant; pm_device.h sample_le, sample_l_shading; pm_scene.cpp
+pm_add_light_distant; pm_shade.h sample_le, sample_l_shading; pm_scene.cpp
 world_sphere, finish_lights), driven by the random numbers the GPU uses
 (mesh_light_ref.emission_samples). The oracle has no such light: this file
 is the yardstick of tests/test_delta_lights*.py.

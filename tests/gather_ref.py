@@ -24,7 +24,7 @@ from pmrender.abi import (PHOTON_DTYPE, PM_ESTIMATOR_KNN, PM_GATHER_GRID, PM_MAT
                           PM_REC_EXCEPTION, PM_REC_INACTIVE, PM_REC_INVALID, PM_REC_MISS, RECORD_DTYPE, RenderParams)
 
 f32 = np.float32
-INV_PI = f32(0.31830988618379067154)  # pm_device.h INV_PI
+INV_PI = f32(0.31830988618379067154)  # pm_math.h INV_PI
 
 # pm_gather.hip, by macro
 TILE_CAP = 128          # PM_TILE_CAP: photons per LDS window

@@ -1,5 +1,5 @@
 """float64 numpy restatement of the triangle-mesh area light (pm_add_light_mesh,
-pm_device.h sample_light_mesh / sample_le / sample_l_shading), and of the disk
+pm_shade.h sample_light_mesh / sample_le / sample_l_shading), and of the disk
 light's same formulas, driven by the random numbers the GPU uses: the permuted
 Halton emission samples (index pid * max_photon_count) and the Philox light
 samples of the pinhole eye pass (pixel, slot, light_rng_seed). The oracle has

@@ -77,7 +77,7 @@ def light_sets():
 
 # ------------------------------------------------------------------ Halton
 def radical_inverse_f32(n, base, table):
-    """permuted_radical_inverse (photontracing.cu:19-31; pm_device.h) over an
+    """permuted_radical_inverse (photontracing.cu:19-31; pm_sample.h) over an
     array of indices, every operation in float32 as the device performs it:
     val += p[n % base] * invBi; n = (uint)((float)n * invBase); invBi *= invBase."""
     n = np.asarray(n, np.uint32).copy()

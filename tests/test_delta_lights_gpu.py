@@ -1,4 +1,4 @@
-"""The distant light on the device (pm_add_light_distant; pm_device.h sample_le,
+"""The distant light on the device (pm_add_light_distant; pm_shade.h sample_le,
 sample_l_shading) against the float64 restatement in delta_light_ref.py, at
 the same Halton samples.
 

@@ -1,5 +1,5 @@
 """Exhaustive CPU checks behind the device's Halton fast paths
-(cuda-raytrace_amd/csrc/pm_device.h permuted_halton4), which must equal the
+(cuda-raytrace_amd/csrc/pm_sample.h permuted_halton4), which must equal the
 reference's loop (photontracing.cu:19-31: digit p[n % base], then the quirk
 `n *= invBase` on a uint — a float multiply truncated) bit for bit:
 

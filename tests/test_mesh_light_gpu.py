@@ -1,4 +1,4 @@
-"""Triangle-mesh area lights on the device (pm_add_light_mesh; pm_device.h
+"""Triangle-mesh area lights on the device (pm_add_light_mesh; pm_shade.h
 sample_light_mesh, sample_le, sample_l_shading, light_le) against the float64
 numpy restatement in mesh_light_ref.py, on four light meshes: (a) one
 triangle, (b) a quad of two equal triangles, (c) a 7-triangle fan with areas

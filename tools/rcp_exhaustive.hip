@@ -1,7 +1,7 @@
 // Exhaustive check (every finite normal float with 2^-125 <= |x| < 2^125) that
 // one FMA Newton step on the hardware reciprocal gives the IEEE correctly
 // rounded 1/x bit for bit:  r = rcp(x); e = fma(-x, r, 1); r' = fma(e, r, r).
-// Used to justify pm_device.h rcp_exact(). Prints mismatch count.
+// Used to justify pm_math.h rcp_exact(). Prints mismatch count.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
