@@ -566,16 +566,6 @@ static int knn_ss_debug_dump(Ctx *c, const GatherParams &G, hipStream_t s) {
     HIPCHK(c, hipMemcpyAsync(&nb, G.knn_ovf_n, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     fprintf(stderr, "pm knn_ss: %u of %lld tiles handed back\n", nb, (long long)(G.tiles ? G.n_tiles : (G.rec_end - G.rec_begin + 63) / 64));
-    std::vector<uint32_t> hdr(KNN_OVF_HDR);
-    HIPCHK(c, hipMemcpy(hdr.data(), G.knn_ovf_n, KNN_OVF_HDR * 4, hipMemcpyDeviceToHost));
-    if (hdr[1] || hdr[2]) { /* PM_KNN_SS_DBG builds */
-        fprintf(stderr, "pm knn_ss dbg: %u bad collects, %u NaN radii\n", hdr[1], hdr[2]);
-        for (uint32_t i = 0; i < std::min<uint32_t>(hdr[1], 60); ++i) {
-            fprintf(stderr, "  ");
-            for (int w = 0; w < 16; ++w) fprintf(stderr, " %u", hdr[64 + 16 * i + w]);
-            fprintf(stderr, "\n");
-        }
-    }
     return PM_OK;
 }
 

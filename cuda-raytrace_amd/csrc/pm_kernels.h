@@ -260,9 +260,9 @@ struct GatherParams {
     int knn_pack; /* 1: (re)write the pairs (the map changed since the last pack); else only clear the counters */
     uint32_t *knn_ovf, *knn_ovf_n;
 };
-/* knn_ovf_n[0] = handed-back tiles; [1..63] and the 16-word records at
- * [64, 1024 + 64) are PM_KNN_SS_DBG diagnostics; the list follows */
-constexpr int KNN_OVF_HDR = 64 + 1024;
+/* knn_ovf_n[0] = handed-back tiles, in a header of 64 counters that
+ * k_knn_pack / launch_knn_ss's memset clear; the list follows */
+constexpr int KNN_OVF_HDR = 64;
 
 struct FinalParams {
     RecordsDev R;
@@ -317,6 +317,12 @@ hipError_t launch_bucket_build(const pm_photon *slots, int64_t n, GridDesc g, ui
 hipError_t launch_gather(const GatherParams &p, int structure, int partial, int count, hipStream_t s);
 /* kNN estimator (pbrt LPhoton) over the photon buckets, fused record update */
 hipError_t launch_gather_knn(const GatherParams &p, int count, hipStream_t s);
+/* its scalar-stream step (pm_gather_knn_ss.hip): the photon pairs when
+ * p.knn_pack (else only the handed-back counters cleared), then
+ * k_gather_knn_ss over grid tiles; the tiles it does not handle are left in
+ * p.knn_ovf[0 .. *p.knn_ovf_n) for k_gather_knn_tile. Returns the memset's
+ * error; a launch error stays for the hipGetLastError after the tile launch */
+hipError_t launch_knn_ss(const GatherParams &p, unsigned grid, hipStream_t s);
 hipError_t launch_ppm_update(const GatherParams &p, const long long *partial, int64_t rec_begin, int64_t rec_count,
                              hipStream_t s);
 hipError_t launch_ppm_update_split(const GatherParams &p, const int *count, const long long *flux, int64_t n_view,

@@ -909,8 +909,45 @@ def knn_ragged():
     return sc, p, recs, _with_invalid(_slots(np.concatenate(pts), rng), rng)
 
 
+SHELL_D2 = (64.0, 64.6)  # knn_shell's dense shell: inside one 1/16-octave bin of d2, [64, 68)
+
+
+def _shell_offsets(lo2, hi2):
+    """offsets on the 1/32 lattice (non-negative octant) with pairwise distinct d2 in [lo2, hi2]; every d2
+    is a multiple of 2^-10 below 2^7, exact in float32 in any summation order"""
+    m = int(np.sqrt(hi2) * 32) + 1
+    a, b = np.meshgrid(np.arange(m + 1), np.arange(m + 1), indexing="ij")
+    c0 = np.ceil(np.sqrt(np.maximum(lo2 * 1024.0 - a * a - b * b, 0.0))).astype(np.int64)
+    o = np.concatenate([np.stack([a, b, c0 + s], -1).reshape(-1, 3) for s in (0, 1, 2)])
+    n = (o * o).sum(axis=1)
+    o, n = o[(n >= lo2 * 1024) & (n <= hi2 * 1024)], n[(n >= lo2 * 1024) & (n <= hi2 * 1024)]
+    _, first = np.unique(n, return_index=True)
+    return o[first] / 32.0
+
+
+def knn_shell():
+    """K = 50, one tile of 64 live records at one point: 30 photons at distinct d2 < 40, then 240 at
+    distinct d2 inside SHELL_D2, so the 50th nearest is the 20th of a shell that fills one bin of either
+    kernel's first histogram and, 32 x finer, still puts more photons into a bin than a COLLECT keeps:
+    the scalar stream refines twice, the tile kernel re-bins [min, max] of the shell"""
+    rng = np.random.RandomState(213)
+    sc, p = _scene(), _knn_params(50)
+    recs = _blank(sc, p)
+    c = np.asarray([110.0, 110.0, 110.0])
+    _set_live(recs, np.arange(64), np.tile(c, (64, 1)), KNN_R2, rng)
+    recs["flags"][[3, 17, 40]] = PM_REC_BACKFACE
+    near, shell = _distinct_offsets(40.0), _shell_offsets(*SHELL_D2)
+    assert len(near) >= 30 and len(shell) >= 240
+    o = np.concatenate([near[rng.choice(len(near), size=30, replace=False)],
+                        shell[rng.choice(len(shell), size=240, replace=False)]])
+    o = (o * rng.choice([-1.0, 1.0], size=o.shape))[rng.permutation(len(o))]
+    slots = _slots(c[None, :] + o, rng, wi=_knn_facing(rng, len(o), recs["ns"][0]))
+    return sc, p, recs, _with_invalid(slots, rng)
+
+
 KNN_CASES = {"knn_counts[K=1]": knn_counts(1), "knn_counts[K=2]": knn_counts(2), "knn_counts[K=50]": knn_counts(50),
-             "knn_counts[K=64]": knn_counts(64), "knn_ties": knn_ties, "knn_zero": knn_zero, "knn_ragged": knn_ragged}
+             "knn_counts[K=64]": knn_counts(64), "knn_ties": knn_ties, "knn_zero": knn_zero, "knn_ragged": knn_ragged,
+             "knn_shell": knn_shell}
 
 _built = {}
 

@@ -323,3 +323,24 @@ def test_precondition_knn_ties_and_zero():
     sc, p, recs, slots = G.case("knn_ragged")
     found, r2, Sum, live = G.knn_ref(sc, recs, slots, 5, p.initial_radius2)
     assert len(recs) == 256 and (~live).sum() == 5 and (found[live] == 5).sum() > 100 and (found[live] < 5).sum() > 20
+
+
+def test_precondition_knn_shell():
+    sc, p, recs, slots = G.case("knn_shell")
+    found, r2, Sum, live = G.knn_ref(sc, recs, slots, 50, p.initial_radius2)
+    lo, hi = np.float32(G.SHELL_D2[0]), np.float32(G.SHELL_D2[1])
+    assert live.sum() == 64 and (found[live] == 50).all() and (found[~live] == 0).all()
+    assert ((r2[live] > lo) & (r2[live] < hi)).all()
+    assert (recs["flags"][live] != 0).sum() == 3 and np.isfinite(Sum).all() and (np.abs(Sum[live]).sum(axis=1) > 0).all()
+    ph = slots[(slots["bits"] & 1) != 0]
+    d2 = G.d2_f32(recs["pos"][0], ph["p"])
+    assert len(np.unique(d2)) == len(d2) == 270 and (d2 < 40.0).sum() == 30 and ((d2 >= lo) & (d2 <= hi)).sum() == 240
+    # the scalar stream's bins are runs of d2 bit patterns: 2^19 wide at level 0 (maxD^2 = 100 and 64 lie
+    # a whole number of them apart), 2^14 after one refinement, 2^9 after two. The shell lies in one
+    # level-0 bin, and the bin of the 50th after one refinement holds more than the 12 values a COLLECT keeps
+    bits, top, kth = u32(d2).astype(np.int64), int(u32(np.float32([G.KNN_R2]))[0]), int(u32(r2[:1])[0])
+    base = int(u32(np.float32([lo]))[0])
+    assert (top - base) % (1 << 19) == 0 and (bits[d2 >= lo] - base < (1 << 19)).all()
+    assert ((bits - base) >> 14 == (kth - base) >> 14).sum() > 12
+    # the tile kernel's first histogram: 32 equal bins of [0, maxD^2), the shell in one of them
+    assert len(np.unique((d2[d2 >= lo] * np.float32(32.0 / G.KNN_R2)).astype(np.int64))) == 1

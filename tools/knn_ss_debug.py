@@ -1,8 +1,7 @@
 """Debug aid for k_gather_knn_ss: C2 kNN (1080p Cornell, 262,144 paths,
 K = 50, r^2 = 100) gathered by the scalar-stream kernel and by the per-lane
 heap kernel on the same photon map; prints the records that differ and the
-kernel's PM_KNN_SS_DEBUG report (run with PMHIP_LIB=<variant built with
--DPM_KNN_SS_DBG> for the per-lane diagnostics)."""
+kernel's PM_KNN_SS_DEBUG report."""
 import os
 import sys
 
