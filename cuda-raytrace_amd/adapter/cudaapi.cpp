@@ -245,6 +245,23 @@ void CudaRender::createSubRenderer(Sampler *sampler, Camera *camera, const Param
         f.ywidth = params.FindOneFloat("ywidth", f.ywidth);
         devcam_.filter = f;
     }
+    /* "bool resample" ["true"]: a fresh jitter and lens sample per pixel every
+     * photon pass (pm_render_resampled). The camera goes to the device with
+     * one stratum, no film and jitter on, whatever "devicecamera" and its keys
+     * say (a filter or strata there warn); "float lensradius" /
+     * "focaldistance" and "integer sampleseed" are read as above. */
+    if (params.FindOneBool("resample", false)) {
+        if (!devcam_.device_camera) {
+            devcam_.sample_seed = (uint32_t)params.FindOneInt("sampleseed", 0);
+            devcam_.lens_radius = params.FindOneFloat("lensradius", 0.f);
+            devcam_.focal_distance = params.FindOneFloat("focaldistance", 0.f);
+        }
+        const bool strata = devcam_.device_camera && devcam_.xsamples * devcam_.ysamples > 1;
+        const bool filtered = devcam_.device_camera && params.FindOneString("pixelfilter", "") != "";
+        pmcuda::resampleCamera(devcam_);
+        if (strata) Warning("Renderer \"cuda\": xsamples / ysamples ignored under \"resample\" (the passes are the samples)");
+        if (filtered) Warning("Renderer \"cuda\": pixelfilter ignored under \"resample\"");
+    }
     impl_.createSubRenderer(s, rendername);
 }
 

@@ -397,7 +397,9 @@ public:
     void AddInt(const string &name, const int *data, int nItems) { if (nItems > 0) ints.push_back(std::make_pair(name, data[0])); }
     void AddFloat(const string &name, const float *data, int nItems) { if (nItems > 0) floats.push_back(std::make_pair(name, data[0])); }
     void AddString(const string &name, const string *data, int nItems) { if (nItems > 0) strings.push_back(std::make_pair(name, data[0])); }
+    void AddBool(const string &name, const bool *data, int nItems) { if (nItems > 0) bools.push_back(std::make_pair(name, data[0])); }
     int FindOneInt(const string &name, int d) const { return find(ints, name, d); }
+    bool FindOneBool(const string &name, bool d) const { return find(bools, name, d); }
     float FindOneFloat(const string &name, float d) const { return find(floats, name, d); }
     string FindOneString(const string &name, const string &d) const { return find(strings, name, d); }
 private:
@@ -406,6 +408,7 @@ private:
         return d;
     }
     vector<std::pair<string, int> > ints;
+    vector<std::pair<string, bool> > bools;
     vector<std::pair<string, float> > floats;
     vector<std::pair<string, string> > strings;
 };

@@ -319,6 +319,18 @@ void CudaRender::Render(const std::vector<Light> &lights, Camera &camera) {
 }
 
 /* ------------------------------------------------------------ renderer */
+int resampleCamera(Camera &c) {
+    const int over = (c.device_camera && c.xsamples * c.ysamples > 1 ? 1 : 0) |
+                     (c.device_camera && c.filter.type != PM_FILTER_NONE ? 2 : 0);
+    c.pinhole = true;
+    c.device_camera = true;
+    c.resample = true;
+    c.xsamples = c.ysamples = 1;
+    c.jitter = true;
+    c.filter = pm_filter{PM_FILTER_NONE, 0.f, 0.f, 0.f, 0.f};
+    return over;
+}
+
 static int64_t set_camera(void *ctx, const Camera &camera) {
     if (camera.pinhole && camera.device_camera) {
         pm_camera c{};
@@ -379,7 +391,10 @@ void PhotonMappingRenderer::render(CudaRender *r, const std::vector<Light> &, Ca
     /* eye pass -> (photon pass -> photon map -> gather) x passes -> final
      * (photonmappingrenderer.cpp:31-45), NaN / negative / inf -> black */
     rgb.assign((size_t)(3 * n), 0.f);
-    check(ctx, pm_render(ctx, &settings.params, rgb.data(), &stats), "pm_render");
+    if (camera.resample) /* a fresh eye sample in front of every photon pass; refused scenes fail with the library's message */
+        check(ctx, pm_render_resampled(ctx, &settings.params, rgb.data(), &stats), "pm_render_resampled");
+    else
+        check(ctx, pm_render(ctx, &settings.params, rgb.data(), &stats), "pm_render");
     splat(camera, rgb, n);
 }
 

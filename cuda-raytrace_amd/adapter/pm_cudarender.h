@@ -160,11 +160,20 @@ struct Camera {
     float lens_radius = 0.f, focal_distance = 0.f;
     uint32_t sample_seed = 0;
     pm_filter filter = {PM_FILTER_NONE, 0.f, 0.f, 0.f, 0.f};
+    /* resample (set by resampleCamera): the photon-mapping renderer draws a
+     * fresh jitter and lens sample per pixel every pass (pm_render_resampled) */
+    bool resample = false;
     std::vector<float> rays, rand2d;
     int n2d = 0;
     std::vector<CameraSample> samples;
     Film *film = nullptr;
 };
+
+/* The camera of a resampled render (Renderer "cuda" "bool resample", pm_render_cli
+ * --resample): the device camera with one stratum, no film and jitter on; the
+ * lens stays. Returns what it overrode: bit 0 a sampler with more than one
+ * sample per pixel, bit 1 a pixel filter (the callers warn). */
+int resampleCamera(Camera &camera);
 
 class CudaRender;
 

@@ -561,6 +561,14 @@ struct PbrtParser::Impl {
     bool jitter = true, have_filter = false;
     pm_filter filter = {PM_FILTER_NONE, 0.f, 0.f, 0.f, 0.f};
     float lens_radius = 0.f, focal_distance = 0.f;
+    std::string sampler_at, filter_at; /* "file:line" of the Sampler / PixelFilter directive */
+
+    void warn_at(const std::string &where, const char *fmt, const std::string &a) {
+        std::fprintf(stderr, "Warning: %s: ", where.c_str());
+        std::fprintf(stderr, fmt, a.c_str());
+        std::fprintf(stderr, "\n");
+        opts->warnings++;
+    }
 
     void camera_done() {
         /* the device camera + film only where the scene asks for more than
@@ -574,6 +582,14 @@ struct PbrtParser::Impl {
             cam.focal_distance = lens_radius > 0.f ? focal_distance : 0.f;
             cam.filter = filter;
             if (cam.device_camera && !have_filter) cam.filter = pm_filter{PM_FILTER_BOX, 0.5f, 0.5f, 0.f, 0.f};
+            /* Renderer "bool resample": the passes are the samples, a record is a pixel */
+            if (opts->resample) {
+                cam.filter = filter; /* only a PixelFilter of the file counts as overridden */
+                const int over = resampleCamera(cam);
+                if (over & 1) warn_at(sampler_at, "Sampler: %s samples per pixel ignored under Renderer \"resample\" (the passes are the samples)",
+                                      std::to_string(xsamples * ysamples));
+                if (over & 2) warn_at(filter_at, "PixelFilter ignored under Renderer \"resample\"%s", "");
+            }
         }
         /* pinhole through the pixel centres: d = fwd + sx*right + sy*up,
          * sx, sy in [-1, 1] (pm_set_pinhole); the screen window folds into
@@ -680,6 +696,7 @@ struct PbrtParser::Impl {
                 pm_render_params &p = opts->settings.params;
                 p.paths_per_pass = ps.oneInt("paths", (int)p.paths_per_pass);
                 p.passes = ps.oneInt("passes", p.passes);
+                opts->resample = ps.oneBool("resample", false);
                 opts->specular = ps.oneString("specular", "reference");
                 if (opts->specular != "pbrt" && opts->specular != "reference")
                     lx.fail(line, "Renderer \"specular\": \"%s\" is not \"pbrt\" or \"reference\"", opts->specular.c_str());
@@ -723,6 +740,7 @@ struct PbrtParser::Impl {
                 }
                 if (xsamples < 1 || xsamples > 8 || ysamples < 1 || ysamples > 8)
                     lx.fail(line, "Sampler: %d x %d samples per pixel (1..8 each)", xsamples, ysamples);
+                sampler_at = lx.file() + ":" + std::to_string(line);
             } else if (d == "PixelFilter") {
                 std::string n = str(lx);
                 const ParamSet ps = params(lx);
@@ -740,6 +758,7 @@ struct PbrtParser::Impl {
                     lx.fail(line, "PixelFilter widths (%g, %g) outside (0, 4]", f.xwidth, f.ywidth);
                 filter = f;
                 have_filter = true;
+                filter_at = lx.file() + ":" + std::to_string(line);
             } else if (d == "SurfaceIntegrator" || d == "VolumeIntegrator" ||
                        d == "Accelerator" || d == "Volume") {
                 str(lx);

@@ -37,7 +37,8 @@
  *                "reference" | "pbrt": with "pbrt" Material "mirror" takes Kr
  *                (0.9) and "glass" Kr, Kt, index (1, 1, 1.5) into the
  *                physical model of pm_add_material_specular; a non-constant
- *                texture on one of them warns and leaves the default)
+ *                texture on one of them warns and leaves the default;
+ *                "bool resample": PbrtOptions::resample)
  *                Camera "float lensradius" / "float focaldistance" (thin lens),
  *                Sampler "stratified" (xsamples, ysamples, jitter) or
  *                "lowdiscrepancy" | "bestcandidate" | "random" (pixelsamples N,
@@ -97,6 +98,11 @@ struct PbrtOptions {
      * index). specular_override, when the caller sets it before parsing to
      * either word, wins over the file (pm_render_cli --specular) */
     std::string specular = "reference", specular_override;
+    /* Renderer "bool resample" ["true"]: a fresh eye sample per pixel every pass
+     * (pm_render_resampled). The camera is then forced (resampleCamera): one
+     * stratum, no film, jitter on, the Camera's lens kept; a Sampler with more
+     * than one sample or a PixelFilter warns that it is ignored */
+    bool resample = false;
     int warnings = 0;
 };
 

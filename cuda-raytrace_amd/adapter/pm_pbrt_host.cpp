@@ -21,6 +21,7 @@
  *        [--lightsource K]  (Renderer "cuda" "integer lightsource" [K]; -1: photons from every light)
  *        [--caustic]     (scenes/caustic-fresnel.pbrt: a GlassMaterial sphere and a MirrorMaterial sphere instead of the blocks)
  *        [--specular pbrt|reference]  (Renderer "cuda" "string specular": pbrt = the Fresnel model with the materials' Kr, Kt, index)
+ *        [--resample]    (Renderer "cuda" "bool resample" ["true"]: a fresh eye sample per pass; --lensradius R --focaldistance F --passes P)
  * The header's third word is the number of light 2D samples per ray
  * (nsamples per area light).
  */
@@ -56,6 +57,8 @@ struct Opts {
     int devicecamera = 0, xsamples = 1, ysamples = 1, jitter = 1;
     float lensradius = 0.f, focaldistance = 0.f, xwidth = 0.f;
     std::string pixelfilter;
+    bool resample = false; /* --resample: the ParamSet's "bool resample" (with --lensradius / --focaldistance / --passes) */
+    int passes = 1;
 };
 
 /* pixel centres in raster order, one sample per pixel; light 2D randoms:
@@ -270,6 +273,11 @@ int run(const Opts &o) {
         if (!o.pixelfilter.empty()) params.AddString("pixelfilter", &o.pixelfilter, 1);
         if (o.xwidth > 0.f) { params.AddFloat("xwidth", &o.xwidth, 1); params.AddFloat("ywidth", &o.xwidth, 1); }
     }
+    if (o.resample) {
+        params.AddBool("resample", &o.resample, 1);
+        if (!o.devicecamera) { params.AddFloat("lensradius", &o.lensradius, 1); params.AddFloat("focaldistance", &o.focaldistance, 1); }
+    }
+    if (o.passes != 1) params.AddInt("passes", &o.passes, 1);
     CentreSampler *sampler = new CentreSampler(o.W, o.H);
     Renderer *renderer = CreateCudaRenderer(sampler, camera, params, o.renderer == "simple" ? "simple" : "photonmap");
     /* pbrtWorldEnd */
@@ -320,6 +328,8 @@ int main(int argc, char **argv) {
         else if (a == "--focaldistance") o.focaldistance = std::stof(val());
         else if (a == "--pixelfilter") o.pixelfilter = val();
         else if (a == "--filterwidth") o.xwidth = std::stof(val());
+        else if (a == "--resample") o.resample = true;
+        else if (a == "--passes") o.passes = std::stoi(val());
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (o.out.empty()) { std::fprintf(stderr, "usage: %s --out f.bin [options]\n", argv[0]); return 2; }

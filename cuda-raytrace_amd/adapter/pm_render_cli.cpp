@@ -13,6 +13,8 @@
  *                 [--light N|all]
  *                 (a pbrt-v2 scene file through pm_pbrt.h; command-line options override the file)
  *                 [--spp XxY] [--filter name[:xw[:yw[:a[:b]]]]] [--lens R:F] [--no-jitter]   (the device camera + film)
+ *                 [--resample]   (a fresh jitter and lens sample per pixel every pass, pm_render_resampled: one
+ *                 stratum, no film, jitter on; as Renderer "cuda" "bool resample" ["true"] in the scene file)
  *   pm_render_cli --pbrt scene.pbrt --dump   (parse only, no device: the plugin calls as JSON, with the
  *                 renderer's light_source_index and the scene's light selection table)
  * --light: the light the photon paths start on; "all" (or -1) starts them on
@@ -255,7 +257,10 @@ float lightArea(const Light &L) {
 struct CameraFlags {
     std::string spp, filter, lens;
     bool no_jitter = false;
-    bool any() const { return !spp.empty() || !filter.empty() || !lens.empty() || no_jitter; }
+    /* --resample: Renderer "bool resample" from the command line; --spp, --filter
+     * and --no-jitter are then ignored with a warning, --lens still sets the lens */
+    bool resample = false;
+    bool any() const { return !spp.empty() || !filter.empty() || !lens.empty() || no_jitter || resample; }
 };
 float flag_float(const std::string &flag, const std::string &v) {
     char *end = nullptr;
@@ -313,6 +318,25 @@ void apply_camera_flags(const CameraFlags &f, Camera &c) {
     if (c.device_camera && !filter_given) c.filter = pm_filter{PM_FILTER_BOX, 0.5f, 0.5f, 0.f, 0.f};
     if (!c.device_camera) c.filter = pm_filter{PM_FILTER_NONE, 0.f, 0.f, 0.f, 0.f};
 }
+/* the same, then the resampled render's camera over it (--resample, or the scene file's Renderer "bool resample") */
+void apply_camera_flags(const CameraFlags &f, PbrtOptions &o) {
+    const bool from_file = o.resample;
+    if (f.resample) o.resample = true;
+    if (!o.resample) { apply_camera_flags(f, o.camera); return; }
+    if (!from_file) { /* the file's own Sampler / PixelFilter: the parser has warned where the file asked */
+        const int over = resampleCamera(o.camera);
+        if (over & 1) { std::fprintf(stderr, "Warning: --resample: the scene's Sampler is ignored (the passes are the samples)\n"); o.warnings++; }
+        if (over & 2) { std::fprintf(stderr, "Warning: --resample: the scene's PixelFilter is ignored\n"); o.warnings++; }
+    }
+    if (!f.spp.empty() || !f.filter.empty() || f.no_jitter) {
+        std::fprintf(stderr, "Warning: --spp, --filter and --no-jitter are ignored under resampling\n");
+        o.warnings++;
+    }
+    CameraFlags lens;
+    lens.lens = f.lens;
+    apply_camera_flags(lens, o.camera);
+    resampleCamera(o.camera);
+}
 
 /* --specular pbrt|reference: overrides the file's Renderer "string specular" */
 std::string g_specular;
@@ -323,7 +347,7 @@ int dump(const std::string &path, const CameraFlags &cflags) {
     o.specular_override = g_specular;
     PbrtParser parser;
     parser.parseFile(path, sink, o);
-    apply_camera_flags(cflags, o.camera);
+    apply_camera_flags(cflags, o);
     std::string lights;
     for (const Light &L : o.lights) {
         if (!lights.empty()) lights += ",\n";
@@ -407,9 +431,9 @@ int dump(const std::string &path, const CameraFlags &cflags) {
         }
     }
     std::printf("%s},\n\"renderer\": \"%s\", \"paths\": %lld, \"passes\": %d, \"gather\": %d, \"film\": \"%s\", "
-                "\"light_source_index\": %d, \"light_cdf\": %s], \"warnings\": %d}\n",
+                "\"light_source_index\": %d, \"light_cdf\": %s], \"resample\": %d, \"warnings\": %d}\n",
                 cam.c_str(), o.renderer.c_str(), (long long)p.paths_per_pass, p.passes, p.gather_structure,
-                o.film_filename.c_str(), p.light_source_index, cdf.c_str(), o.warnings);
+                o.film_filename.c_str(), p.light_source_index, cdf.c_str(), o.resample ? 1 : 0, o.warnings);
     return 0;
 }
 
@@ -442,7 +466,7 @@ int render_pbrt(const std::string &path, std::string out, const std::string &ren
     if (!structure.empty()) p.gather_structure = structure == "kd" ? PM_GATHER_KDTREE : PM_GATHER_GRID;
     if (!light.empty()) { p.light_source_index = parse_light(light); check_light(p.light_source_index, o.lights.size()); }
     if (out.empty()) out = o.film_filename;
-    apply_camera_flags(cflags, o.camera);
+    apply_camera_flags(cflags, o);
     CudaRender *render = CreateCudaRenderer(o.settings, o.renderer);
     PixelFilm film(o.camera.width, o.camera.height, out); /* the device film writes one value per pixel */
     o.camera.film = &film;
@@ -500,6 +524,7 @@ int main(int argc, char **argv) {
         else if (a == "--filter") cflags.filter = next();
         else if (a == "--lens") cflags.lens = next();
         else if (a == "--no-jitter") cflags.no_jitter = true;
+        else if (a == "--resample") cflags.resample = true;
         else if (a == "--camera") {
             for (float &c : cam) c = std::strtof(next(), nullptr);
             have_cam = true;
@@ -515,7 +540,7 @@ int main(int argc, char **argv) {
         }
     }
     if (cflags.any()) {
-        std::fprintf(stderr, "--spp, --filter, --lens and --no-jitter need --pbrt scene.pbrt\n");
+        std::fprintf(stderr, "--spp, --filter, --lens, --no-jitter and --resample need --pbrt scene.pbrt\n");
         return 2;
     }
     if (out.empty()) out = "out.pfm";

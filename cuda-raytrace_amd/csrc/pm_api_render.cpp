@@ -265,6 +265,56 @@ int pm_render(void *ptr, const pm_render_params *p, float *out_rgb, pm_stats *st
     return PM_OK;
 }
 
+/* pm_render's loop with a fresh eye sample per pass in front of the trace
+ * (stochastic progressive photon mapping: one record per pixel, moved under
+ * its statistics); the final divides the summed direct light by the passes */
+int pm_render_resampled(void *ptr, const pm_render_params *p, float *out_rgb, pm_stats *st) {
+    GETCTX(ptr);
+    int rc;
+    if ((rc = check_params(c, p))) return rc;
+    if (!out_rgb) FAIL(c, PM_ERR_INVALID, "null output");
+    if (p->passes < 1 || p->paths_per_pass < 1) FAIL(c, PM_ERR_INVALID, "passes and paths_per_pass must be >= 1");
+    hipStream_t s = c->stream;
+    double t_eye = 0, t_trace = 0, t_build = 0, t_gather = 0, t_final = 0;
+    int64_t nvalid = 0;
+    int64_t counters[2] = {0, 0};
+    for (int pass = 0; pass < p->passes; ++pass) {
+        if ((rc = pm_eye_resample(c, p, pass, s))) return rc;
+        t_eye += timer_ms(c, "eye");
+        if ((rc = pm_trace_photons(c, p, pass, 0, p->paths_per_pass, 0, s))) return rc;
+        t_trace += timer_ms(c, "trace");
+        if ((rc = pm_build_photon_map(c, p, p->paths_per_pass * p->max_photon_count, s))) return rc;
+        t_build += timer_ms(c, "build");
+        if ((rc = valid_photons(c, c, p, nvalid))) return rc;
+        if ((rc = pm_gather(c, p, s))) return rc;
+        t_gather += timer_ms(c, "gather");
+        if (c->counting) {
+            unsigned long long hc[2];
+            HIPCHK(c, hipMemcpy(hc, c->d_counters.p, 16, hipMemcpyDeviceToHost));
+            counters[0] = (int64_t)hc[0]; counters[1] = (int64_t)hc[1];
+        }
+    }
+    const double emitted = (double)p->paths_per_pass * p->passes;
+    const int64_t nout = (int64_t)c->W * c->H; /* one stratum, no film: the sample raster is the image */
+    HIPCHK(c, c->d_out.ensure(nout * 3 * sizeof(float)));
+    FinalParams F = final_params(c, emitted, 0, c->nrec, c->d_out.as<float>());
+    F.raster = 1;
+    F.n_eye = p->passes; F.resampled = 1; /* also for a single pass, where it is pm_render's final */
+    timer_begin(c, "final", s);
+    HIPCHK(c, launch_final(F, s));
+    timer_end(c, "final", s);
+    if ((rc = deliver_image(c, nout, out_rgb))) return rc;
+    t_final = timer_ms(c, "final");
+    if (st) {
+        if ((rc = render_stats(c, c, emitted, nvalid, st))) return rc; /* gather_points: the last pass's */
+        st->nodes_visited = counters[0];
+        st->photons_in_radius = counters[1];
+        st->ms_eye = t_eye; st->ms_trace = t_trace; st->ms_build = t_build; st->ms_gather = t_gather;
+        st->ms_final = t_final;
+    }
+    return PM_OK;
+}
+
 /* ------------------------------------------------------- simple renderer */
 int pm_simple_pass(void *ptr, const pm_render_params *p, void *d_out, void *stream) {
     GETCTX(ptr);

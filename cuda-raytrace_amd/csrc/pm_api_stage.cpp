@@ -57,6 +57,19 @@ RecordsDev recs(Ctx *c) {
     return R;
 }
 
+/* the parameter block of an eye pass over the context's records (pass 0) */
+EyeParams eye_params(Ctx *c, const pm_render_params *p) {
+    EyeParams E{};
+    E.S = c->S;
+    E.R = recs(c);
+    eye_camera(c, E);
+    E.rays = c->d_rays.as<float>(); E.rand2d = c->d_rand2d.as<float>();
+    E.eps = p->scene_epsilon; E.r2init = p->initial_radius2; E.max_spec = p->max_specular_depth;
+    E.light_seed = p->light_rng_seed;
+    E.kd = c->albedo() ? c->d_rkd.as<float4>() : nullptr;
+    return E;
+}
+
 /* cells per axis of a box of width 2 r' (r' of radius2) on grid g: the tile
  * kernel's run count (GatherParams::span), clamped to its instances 2..5
  * (larger boxes scan per lane) */
@@ -143,6 +156,8 @@ FinalParams final_params(Ctx *c, double emitted, int64_t begin, int64_t count, f
     F.emitted = (float)emitted; /* gContext["emittingPhotons"]->setFloat((float)totalPhotons) */
     F.rec_begin = begin; F.rec_count = count; F.out = out; F.raster = 0; F.W = c->W;
     F.kd = c->albedo() ? c->d_rkd.as<float4>() : nullptr;
+    /* records of a resampled render (pm_eye_resample: PPM, no albedo): dl sums eye_samples samples */
+    if (c->eye_samples > 1) { F.n_eye = c->eye_samples; F.resampled = 1; }
     return F;
 }
 
@@ -190,19 +205,48 @@ int pm_eye_pass(void *ptr, const pm_render_params *p, void *stream) {
     if (!c->pinhole && c->rand2d_total > c->n2d)
         FAIL(c, PM_ERR_INVALID, "eye rays carry %d 2D samples, lights need %d", c->n2d, c->rand2d_total);
     hipStream_t s = pick(c, stream);
-    EyeParams E{};
-    E.S = c->S;
-    E.R = recs(c);
-    eye_camera(c, E);
-    E.rays = c->d_rays.as<float>(); E.rand2d = c->d_rand2d.as<float>();
-    E.eps = p->scene_epsilon; E.r2init = p->initial_radius2; E.max_spec = p->max_specular_depth;
-    E.light_seed = p->light_rng_seed;
-    E.kd = c->albedo() ? c->d_rkd.as<float4>() : nullptr;
+    const EyeParams E = eye_params(c, p);
     timer_begin(c, "eye", s);
     HIPCHK(c, launch_eye(E, s));
     timer_end(c, "eye", s);
     c->rec_fresh = false; /* the eye pass writes every record */
+    c->eye_samples = 1;
     c->tiles.invalidate();
+    c->grid_plan.invalidate();
+    if (c->view_active && (rc = build_view(c, s))) return rc;
+    return PM_OK;
+}
+
+int pm_eye_resample(void *ptr, const pm_render_params *p, int pass, void *stream) {
+    /* what needs no context is checked before the context is */
+    if (!p) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_eye_resample: null params");
+    if (pass < 0) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_eye_resample: pass %d is negative", pass);
+    GETCTX(ptr);
+    int rc;
+    if ((rc = check_params(c, p))) return rc;
+    if (!c->camera) FAIL(c, PM_ERR_INVALID, "pm_eye_resample: needs the device camera (pm_set_camera)");
+    if (c->cam.xsamples != 1 || c->cam.ysamples != 1)
+        FAIL(c, PM_ERR_INVALID, "pm_eye_resample: the camera has %d x %d samples per pixel; the passes are the samples (1 x 1)",
+             c->cam.xsamples, c->cam.ysamples);
+    if (real_filter(c->cam.filter))
+        FAIL(c, PM_ERR_INVALID, "pm_eye_resample: the camera has a pixel filter; a record is one pixel (PM_FILTER_NONE)");
+    if (p->estimator != PM_ESTIMATOR_PPM)
+        FAIL(c, PM_ERR_INVALID, "pm_eye_resample: PM_ESTIMATOR_PPM only (the kNN final applies the Kd of the record's current material)");
+    if (c->albedo())
+        FAIL(c, PM_ERR_INVALID, "pm_eye_resample: the scene has a textured or physically specular material, whose factor "
+                                "pm_final applies once per record: wrong when the hit moves");
+    if (pass == 0) return pm_eye_pass(ptr, p, stream);
+    if (c->eye_samples < 1 || c->nrec <= 0 || c->nrec != num_records(c))
+        FAIL(c, PM_ERR_INVALID, "pm_eye_resample: pass %d before any eye pass wrote this camera's records (pass 0 or pm_eye_pass first)", pass);
+    hipStream_t s = pick(c, stream);
+    if ((rc = materialize_reset(c, s))) return rc;
+    EyeParams E = eye_params(c, p);
+    E.pass = (uint32_t)pass;
+    timer_begin(c, "eye", s);
+    HIPCHK(c, launch_eye_resample(E, s));
+    timer_end(c, "eye", s);
+    ++c->eye_samples;
+    c->tiles.invalidate(); /* the flags moved with the hits */
     c->grid_plan.invalidate();
     if (c->view_active && (rc = build_view(c, s))) return rc;
     return PM_OK;

@@ -167,6 +167,11 @@ struct Ctx {
     /* records */
     DevBuf d_pos, d_nrm, d_state, d_n, d_dl;
     int64_t nrec = 0;
+    /* eye samples summed in the records' dl: 0 none yet (pm_set_camera,
+     * pm_set_pinhole, pm_set_eye_rays), 1 after pm_eye_pass, +1 per
+     * pm_eye_resample(pass > 0); above 1 pm_final / pm_final_view divide dl by
+     * it and keep MISS / EXCEPTION records (FinalParams::n_eye, resampled) */
+    int eye_samples = 0;
     /* slots */
     DevBuf d_slots;
     int64_t slots_used = 0;
@@ -315,8 +320,7 @@ void halton_perm(uint32_t seed, uint32_t out[28]);
 /* pm_api_scene.cpp */
 void eye_camera(const Ctx *c, EyeParams &E);
 /* pm_api_stage.cpp */
-FinalParams final_params(Ctx *c, double emitted, int64_t begin, int64_t count, float *out);
-int materialize_reset(Ctx *c, hipStream_t s);
+FinalParams final_params(Ctx *c, double emitted, int64_t begin, int64_t count, float *out);int materialize_reset(Ctx *c, hipStream_t s);
 int check_params(Ctx *c, const pm_render_params *p);
 
 #pragma GCC visibility pop

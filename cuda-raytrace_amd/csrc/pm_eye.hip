@@ -3,6 +3,8 @@
  *
  *   k_eye          eye pass: camera ray -> specular chain -> gather record +
  *                  direct light with shadow rays   (raytracing.cu:19-147)
+ *   k_eye_resample eye pass k > 0 of a resampled render (pm_eye_resample): the
+ *                  records move under their statistics, dl accumulates
  *   k_simple       the simple renderer: direct light per eye sample
  *                  (simple_render/simplerender.cu)
  *   k_camera_rays  pm_camera_rays: the rays of pm_set_camera's samples
@@ -22,11 +24,12 @@ namespace pm {
 /* The camera ray of sample (ix, iy) of the WS x HS raster, in the order of
  * operations pm_api.h pins (its jitter and film position, camera_randoms and
  * camera_film_xy of pm_kernels.h, are the film kernel's too): shared by k_eye,
- * k_simple and k_camera_rays. */
+ * k_simple and k_camera_rays. pass: the eye pass of a resampled render
+ * (pm_eye_resample), the constant 0 anywhere else. */
 PMD void camera_ray(const CameraDev &C, float4 eye4, float4 fwd4, float4 right4, float4 up4, int WS, int HS, int ix,
-                    int iy, v3 *o, v3 *d, float *fx, float *fy) {
+                    int iy, uint32_t pass, v3 *o, v3 *d, float *fx, float *fy) {
     float ju, jv, lu, lv;
-    camera_randoms(C, (int64_t)iy * WS + ix, &ju, &jv, &lu, &lv);
+    camera_randoms(C, (int64_t)iy * WS + ix, pass, &ju, &jv, &lu, &lv);
     camera_film_xy(C, ix, iy, ju, jv, fx, fy);
     const v3 eye = xyz(eye4), fwd = xyz(fwd4), right = xyz(right4), up = xyz(up4);
     const float sx = (2.0f * ((float)ix + ju)) / (float)WS - 1.0f;
@@ -62,7 +65,13 @@ PMD void camera_ray(const CameraDev &C, float4 eye4, float4 fwd4, float4 right4,
  * word 3 = the depth), and carries an rgb throughput T that multiplies what
  * the record contributes: dl = T L, P.kd = T x (the texel, or 1). A material
  * of the reference's model in such a scene steps as it always did. */
-template <int MODE, bool CAM, bool TEX, bool SPEC>
+/* RESAMPLE (with CAM, without TEX and SPEC): eye pass P.pass > 0 of
+ * pm_eye_resample. The record keeps its statistics (state, n) and moves under
+ * them: the camera randoms and the light samples take P.pass as counter word
+ * 3, pos / nrm are this sample's, and dl += this sample's direct light (0 for
+ * a miss or an exception). Padding records are left as pass 0 wrote them. The
+ * other instantiations hold none of it: their pass is the constant 0. */
+template <int MODE, bool CAM, bool TEX, bool SPEC, bool RESAMPLE = false>
 PMD void eye_body(const EyeParams &P) {
     extern __shared__ __attribute__((aligned(16))) int stk[]; /* [stack_depth x EYE_BLOCK][scene blob (LDS)] */
     int *stack = stk + threadIdx.x;
@@ -75,10 +84,12 @@ PMD void eye_body(const EyeParams &P) {
     Ray ray;
     int64_t pixel;
     float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint32_t pass = RESAMPLE ? P.pass : 0u;
     if (CAM) {
         int px, py;
         rec_to_pixel(r, P.W, &px, &py);
         if (px >= P.W || py >= P.H) {
+            if (RESAMPLE) return;
             P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float(PM_REC_INVALID));
             P.R.nrm[r] = zero4; P.R.state[r] = zero4; P.R.n[r] = 0.f; P.R.dl[r] = zero4;
             if (TEX) P.kd[r] = zero4;
@@ -86,7 +97,7 @@ PMD void eye_body(const EyeParams &P) {
         }
         pixel = (int64_t)py * P.W + px; /* the sample index q: keys the light samples below */
         float fx, fy;
-        camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, px, py, &ray.o, &ray.d, &fx, &fy);
+        camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, px, py, pass, &ray.o, &ray.d, &fx, &fy);
     } else if (P.pinhole) {
         int px, py;
         rec_to_pixel(r, P.W, &px, &py);
@@ -154,6 +165,10 @@ PMD void eye_body(const EyeParams &P) {
     }
     if (flags) {
         P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float((int)flags));
+        if (RESAMPLE) { /* this sample adds no light (dl + 0 is dl: a sum from +0 is never -0); the statistics stay */
+            P.R.nrm[r] = zero4;
+            return;
+        }
         P.R.nrm[r] = zero4; P.R.state[r] = zero4; P.R.n[r] = 0.f; P.R.dl[r] = zero4;
         if (TEX) P.kd[r] = zero4;
         return;
@@ -187,7 +202,7 @@ PMD void eye_body(const EyeParams &P) {
                     int slot = fbits(Lt.p2_r2d.w) + s;
                     if (P.pinhole) {
                         uint32_t o4[4];
-                        pmdm_philox4x32_10((uint32_t)pixel, (uint32_t)slot, 0u, 0u, P.light_seed, 0u, o4);
+                        pmdm_philox4x32_10((uint32_t)pixel, (uint32_t)slot, 0u, pass, P.light_seed, 0u, o4);
                         u1 = pmdm_u01(o4[0]); u2 = pmdm_u01(o4[1]);
                     } else {
                         const float *q = P.rand2d + ((size_t)pixel * P.n2d + slot) * 2;
@@ -210,6 +225,11 @@ PMD void eye_body(const EyeParams &P) {
     const uint32_t side = dot(ns, -dir) < 0.f ? PM_REC_BACKFACE : 0u;
     P.R.pos[r] = make_float4(point.x, point.y, point.z, __uint_as_float(side));
     P.R.nrm[r] = make_float4(ns.x, ns.y, ns.z, __int_as_float(g.material));
+    if (RESAMPLE) { /* one fp32 add per channel onto the earlier samples' sum */
+        const float4 a = P.R.dl[r];
+        P.R.dl[r] = make_float4(a.x + L.x, a.y + L.y, a.z + L.z, 0.f);
+        return;
+    }
     P.R.state[r] = make_float4(0.f, 0.f, 0.f, P.r2init);
     P.R.n[r] = 0.f;
     if (SPEC) { L = T * L; kdf = T * kdf; }
@@ -221,6 +241,8 @@ template <int MODE, bool CAM = false, bool TEX = false>
 __global__ __launch_bounds__(EYE_BLOCK) void k_eye(EyeParams P) { eye_body<MODE, CAM, TEX, false>(P); }
 template <int MODE, bool CAM>
 __global__ __launch_bounds__(EYE_BLOCK) void k_eye_spec(EyeParams P) { eye_body<MODE, CAM, true, true>(P); }
+template <int MODE>
+__global__ __launch_bounds__(EYE_BLOCK) void k_eye_resample(EyeParams P) { eye_body<MODE, true, false, false, true>(P); }
 
 template <bool CAM, bool TEX>
 static void launch_eye_mode(const EyeParams &p, unsigned grid, size_t lds, hipStream_t s) {
@@ -259,6 +281,20 @@ hipError_t launch_eye(const EyeParams &p, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_eye_resample(const EyeParams &p, hipStream_t s) {
+    if (p.R.count <= 0) return hipSuccess;
+    if (!p.camera || p.pass == 0u || p.S.mat_spec || p.S.tex_recs) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
+    const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
+    switch (scene_mode(p.S)) {
+    case MODE_BRUTE: pm_launch((k_eye_resample<MODE_BRUTE>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    case MODE_LDS: pm_launch((k_eye_resample<MODE_LDS>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    case MODE_INST: pm_launch((k_eye_resample<MODE_INST>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    default: pm_launch((k_eye_resample<MODE_GLOBAL>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
+    }
+    return hipGetLastError();
+}
+
 /* ====================================================================== */
 /* simple renderer (direct light only, simple_render/simplerender.cu)     */
 /* ====================================================================== */
@@ -286,7 +322,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
         if (px >= P.W || py >= P.H) return;
         pixel = (int64_t)py * P.W + px;
         float fx, fy;
-        camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, px, py, &ray.o, &ray.d, &fx, &fy);
+        camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, px, py, 0u, &ray.o, &ray.d, &fx, &fy);
     } else if (P.pinhole) {
         int px, py;
         rec_to_pixel(r, P.W, &px, &py);
@@ -368,8 +404,9 @@ hipError_t launch_simple(const EyeParams &p, float *out, hipStream_t s) {
     return hipGetLastError();
 }
 
-/* pm_camera_rays: the rays and film positions of samples [first, first +
- * count) in raster order, through camera_ray as the eye pass calls it */
+/* pm_camera_rays_pass: the rays and film positions of samples [first, first +
+ * count) in raster order for eye pass P.pass, through camera_ray as the eye
+ * pass calls it */
 __global__ __launch_bounds__(256) void k_camera_rays(EyeParams P, int64_t first, int64_t count, float *rays6,
                                                      float *film_xy) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -378,7 +415,7 @@ __global__ __launch_bounds__(256) void k_camera_rays(EyeParams P, int64_t first,
     const int ix = (int)(q % P.W), iy = (int)(q / P.W);
     v3 o, d;
     float fx, fy;
-    camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, ix, iy, &o, &d, &fx, &fy);
+    camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, ix, iy, P.pass, &o, &d, &fx, &fy);
     if (rays6) {
         float *r = rays6 + 6 * i;
         r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;

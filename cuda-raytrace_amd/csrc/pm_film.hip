@@ -67,7 +67,7 @@ __global__ __launch_bounds__(FILM_BLOCK) void k_film(FilmParams P) {
             }
             for (int j = t; j < ncol; j += FILM_BLOCK) {
                 float ju, jv, lu, lv, fx, fy;
-                if (P.cam.jitter) camera_randoms(P.cam, q0 + j, &ju, &jv, &lu, &lv);
+                if (P.cam.jitter) camera_randoms(P.cam, q0 + j, 0u, &ju, &jv, &lu, &lv);
                 else ju = jv = 0.5f; /* the lens randoms are the eye pass's alone */
                 camera_film_xy(P.cam, sc0 + j, iy, ju, jv, &fx, &fy);
                 s_fx[lb + j] = fx; s_fy[lb + j] = fy;

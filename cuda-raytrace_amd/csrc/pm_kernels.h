@@ -89,6 +89,11 @@ struct EyeParams {
      * itself is the pinhole's */
     int camera;
     CameraDev cam;
+    /* the resampled eye pass (pm_eye_resample, k_eye_resample) and
+     * pm_camera_rays_pass: the pass number, Philox counter word 3 of the camera
+     * randoms and of the light samples. 0 on every other path, whose kernels do
+     * not read it (it fills what was padding in front of kd) */
+    uint32_t pass;
     /* scenes with a textured material (S.tex_recs != null) or one of the
      * physical specular model (S.mat_spec != null) only: per record the
      * factor pm_final applies to its indirect term (float4, SoA like R's
@@ -98,12 +103,14 @@ struct EyeParams {
     float4 *kd;
 };
 
-/* the jitter and lens randoms of sample q (pm_api.h pm_set_camera) */
-PMD void camera_randoms(const CameraDev &C, int64_t q, float *ju, float *jv, float *lu, float *lv) {
+/* the jitter and lens randoms of sample q in eye pass `pass` (pm_api.h
+ * pm_set_camera, pm_eye_resample); every caller but the resampled eye pass
+ * and pm_camera_rays_pass passes the constant 0 */
+PMD void camera_randoms(const CameraDev &C, int64_t q, uint32_t pass, float *ju, float *jv, float *lu, float *lv) {
     /* uniform per launch: stratum centres through a pinhole use none of the four */
     if (!C.jitter && !(C.lens_radius > 0.0f)) { *ju = *jv = 0.5f; *lu = *lv = 0.0f; return; }
     uint32_t o4[4];
-    pmdm_philox4x32_10((uint32_t)((uint64_t)q & 0xffffffffu), (uint32_t)((uint64_t)q >> 32), 1u, 0u, C.seed, 0u, o4);
+    pmdm_philox4x32_10((uint32_t)((uint64_t)q & 0xffffffffu), (uint32_t)((uint64_t)q >> 32), 1u, pass, C.seed, 0u, o4);
     *ju = C.jitter ? pmdm_u01(o4[0]) : 0.5f;
     *jv = C.jitter ? pmdm_u01(o4[1]) : 0.5f;
     *lu = pmdm_u01(o4[2]);
@@ -278,6 +285,12 @@ struct FinalParams {
      * A textured matte's Kd is 1 in the materials table, so every gather sums
      * with f = 1 / pi, and the texel multiplies the indirect term here */
     const float4 *kd;
+    /* resampled != 0 (pm_eye_resample's records, k_final_resampled; never with
+     * knn or kd): dl is the sum of n_eye eye samples' direct light and is
+     * divided by (float)n_eye, and a record whose last sample is MISS or
+     * EXCEPTION still shows what its earlier samples gathered. Both 0 on every
+     * other path, whose kernel (k_final) reads neither */
+    int n_eye, resampled;
 };
 
 /* traversal mode of a scene: LDS-resident blob (brute force when tiny) or HBM */
@@ -286,11 +299,15 @@ inline int scene_mode(const SceneDev &S) {
 }
 
 hipError_t launch_eye(const EyeParams &p, hipStream_t s);
+/* eye pass p.pass > 0 of pm_eye_resample over the records of an earlier eye
+ * pass: pm_set_camera's rays, no textured or physically specular material */
+hipError_t launch_eye_resample(const EyeParams &p, hipStream_t s);
 /* simple renderer (simplerender.cu): direct light per eye sample into out
  * (float3, raster / sample order); only p.R.count of the records is read */
 hipError_t launch_simple(const EyeParams &p, float *out, hipStream_t s);
-/* pm_camera_rays: rays6 (o.xyz, d.xyz) and film_xy (fx, fy) of samples
- * [first, first + count) of p's camera (device buffers; either may be null) */
+/* pm_camera_rays_pass: rays6 (o.xyz, d.xyz) and film_xy (fx, fy) of samples
+ * [first, first + count) of p's camera in eye pass p.pass (device buffers;
+ * either may be null) */
 hipError_t launch_camera_rays(const EyeParams &p, int64_t first, int64_t count, float *rays6, float *film_xy,
                               hipStream_t s);
 /* the film (pm_film.hip): fills hx / hy / row_w / band_rows of p itself */

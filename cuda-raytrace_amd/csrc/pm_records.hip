@@ -225,6 +225,39 @@ __global__ __launch_bounds__(256) void k_final(FinalParams P) {
     P.out[3 * o + 2] = out.z;
 }
 
+/* k_final over the records of a resampled render (FinalParams::resampled,
+ * pm_eye_resample: PPM, no albedo factors): dl holds the sum of n_eye samples,
+ * and the current flags are only the last sample's, so a MISS or EXCEPTION
+ * record is written like any other: dl / n_eye + flux (1 / pi) / (radius2
+ * emitted), the indirect term 0 while the record has gathered nothing */
+__global__ __launch_bounds__(256) void k_final_resampled(FinalParams P) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= P.rec_count) return;
+    const int64_t r = P.view ? (int64_t)P.view[P.rec_begin + i] : P.rec_begin + i;
+    const uint32_t flags = (uint32_t)__float_as_int(P.R.pos[r].w);
+    int64_t o = i;
+    if (P.raster) {
+        int px, py;
+        rec_to_pixel(r, P.W, &px, &py);
+        if (flags & PM_REC_INVALID) return;
+        o = (int64_t)py * P.W + px;
+    }
+    v3 out = mk(0.f, 0.f, 0.f);
+    if (!(flags & PM_REC_INVALID)) {
+        const float4 dl = P.R.dl[r], st = P.R.state[r];
+        const float N = P.R.n[r];
+        v3 IDL = mk(0.f, 0.f, 0.f);
+        if (N != 0) IDL = xyz(st) * INV_PI / (st.w * P.emitted);
+        const float ne = (float)P.n_eye; /* one IEEE division per channel (v3 / float would multiply by 1 / ne) */
+        out = mk(dl.x / ne, dl.y / ne, dl.z / ne) + IDL;
+        float y = 0.212671f * out.x + 0.715160f * out.y + 0.072169f * out.z;
+        if (isnan(out.x) || isnan(out.y) || isnan(out.z) || y < -1e-5f || isinf(y)) out = mk(0.f, 0.f, 0.f);
+    }
+    P.out[3 * o + 0] = out.x;
+    P.out[3 * o + 1] = out.y;
+    P.out[3 * o + 2] = out.z;
+}
+
 __global__ __launch_bounds__(256) void k_tile_flags(RecordsDev R, uint8_t *flags) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     bool act = false;
@@ -312,7 +345,11 @@ hipError_t launch_tile_list(const RecordsDev &R, uint8_t *flags, uint32_t *list,
 
 hipError_t launch_final(const FinalParams &p, hipStream_t s) {
     if (p.rec_count <= 0) return hipSuccess;
-    pm_launch(k_final, dim3((unsigned)((p.rec_count + 255) / 256)), dim3(256), 0, s, p);
+    if (p.resampled) {
+        if (p.n_eye < 1 || p.knn || p.kd) return hipErrorInvalidValue;
+        pm_launch(k_final_resampled, dim3((unsigned)((p.rec_count + 255) / 256)), dim3(256), 0, s, p);
+    } else
+        pm_launch(k_final, dim3((unsigned)((p.rec_count + 255) / 256)), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

@@ -67,6 +67,9 @@ def load_library(path=None):
         "pm_set_camera": (c_int, [vp, ctypes.POINTER(Camera)]),
         "pm_film": (c_int, [vp, vp, vp, vp]),
         "pm_camera_rays": (c_int, [vp, i64, i64, P_f, P_f]),
+        "pm_camera_rays_pass": (c_int, [vp, c_int, i64, i64, P_f, P_f]),
+        "pm_eye_resample": (c_int, [vp, ctypes.POINTER(RenderParams), c_int, vp]),
+        "pm_render_resampled": (c_int, [vp, ctypes.POINTER(RenderParams), P_f, ctypes.POINTER(Stats)]),
         "pm_film_filter_table": (c_int, [ctypes.POINTER(Filter), P_f]),
         "pm_commit": (c_int, [vp]),
         "pm_render": (c_int, [vp, ctypes.POINTER(RenderParams), P_f, ctypes.POINTER(Stats)]),
@@ -354,13 +357,14 @@ class Context:
         """pm_film: device float3 sample raster (width x height) -> device float3 image."""
         self._chk(self.lib.pm_film(self.h, ctypes.c_void_p(d_samples), ctypes.c_void_p(d_image), stream))
 
-    def camera_rays(self, first=0, count=None):
+    def camera_rays(self, first=0, count=None, pass_=0):
         """(rays (count, 6), film_xy (count, 2)) of samples [first, first + count) of the sample
-        raster, computed by the device function the eye pass calls (pm_camera_rays)."""
+        raster in eye pass pass_ (0: the eye pass; k: eye_resample(k)), computed by the device
+        function the eye pass calls (pm_camera_rays_pass)."""
         if count is None:
             count = self.width * self.height - first
         rays, xy = np.zeros((count, 6), np.float32), np.zeros((count, 2), np.float32)
-        self._chk(self.lib.pm_camera_rays(self.h, int(first), int(count), fptr(rays), fptr(xy)))
+        self._chk(self.lib.pm_camera_rays_pass(self.h, int(pass_), int(first), int(count), fptr(rays), fptr(xy)))
         return rays, xy
 
     def _out_shape(self):
@@ -384,6 +388,15 @@ class Context:
             out = out.reshape(oh, ow, 3)
         return out, st.as_dict()
 
+    def render_resampled(self, params=None):
+        """pm_render_resampled: a fresh eye sample of set_camera's jitter and lens every pass, one
+        record per pixel (stochastic progressive photon mapping). Returns ((H, W, 3), stats)."""
+        params = params or RenderParams.defaults()
+        out = np.zeros((self.height * self.width, 3), np.float32)
+        st = Stats()
+        self._chk(self.lib.pm_render_resampled(self.h, ctypes.byref(params), fptr(out), ctypes.byref(st)))
+        return out.reshape(self.height, self.width, 3), st.as_dict()
+
     def render_simple(self, params=None):
         """SimpleRenderer (simplerender.cpp:18-103): direct light only."""
         params = params or RenderParams.simple_defaults()
@@ -402,6 +415,11 @@ class Context:
     # ---- stages ---------------------------------------------------------------
     def eye_pass(self, params, stream=None):
         self._chk(self.lib.pm_eye_pass(self.h, ctypes.byref(params), stream))
+
+    def eye_resample(self, params, pass_, stream=None):
+        """pm_eye_resample: eye pass pass_ of a resampled render (0: eye_pass; k > 0: the records
+        move to a fresh camera sample under their statistics, dl accumulates)."""
+        self._chk(self.lib.pm_eye_resample(self.h, ctypes.byref(params), int(pass_), stream))
 
     def trace_photons(self, params, pass_index=0, path_begin=0, path_count=None, slot_path_base=0, stream=None):
         if path_count is None:

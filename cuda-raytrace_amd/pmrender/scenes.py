@@ -62,6 +62,8 @@ class Scene:
     # ("image", (h, w, 3) array, wrap, mapping, scale) | ("checker", op1, op2, mapping) | ("scale", op1, op2);
     # an operand is a Tex (an image) or an rgb
     textures: list = field(default_factory=list)
+    # render with a fresh eye sample every pass (Context.render_resampled; Renderer "bool resample" in a scene file)
+    resample: bool = False
 
     def material(self, mtype, rgb):
         """rgb: a colour, or a Tex handle for the Kd of a PM_MATTE (pm_add_material_textured)."""
@@ -309,6 +311,16 @@ def cornell_box(W=256, H=256, blocks=True, nsamples=1):
         ], white)
     _ceiling_light(s, nsamples=nsamples)
     s.camera = pinhole(W, H)
+    return s
+
+
+def cornell_dof(W=256, H=256, lens_radius=20.0, focal_distance=970.0):
+    """The Cornell box through a thin lens focused on the short block (970 from the eye along the
+    view axis), rendered with a fresh jitter and lens sample per pixel every pass
+    (scenes/cornell-dof.pbrt): one stratum, no film, Scene.resample set."""
+    s = cornell_box(W, H)
+    s.camera = device_camera(W, H, lens_radius=lens_radius, focal_distance=focal_distance)
+    s.resample = True
     return s
 
 

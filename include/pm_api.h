@@ -419,6 +419,10 @@ int pm_film(void *ctx, const void *d_samples, void *d_image, void *stream);
  * count), computed on the device by the function the eye pass calls, into
  * host arrays; either may be null. A test hook like pm_scene_section. */
 int pm_camera_rays(void *ctx, int64_t first, int64_t count, float *rays6, float *film_xy);
+/* The same for eye pass `pass` of a resampled render (pm_eye_resample), by the
+ * same device function: pm_camera_rays is pass = 0. PM_ERR_INVALID also for
+ * pass < 0 (checked before the context is). */
+int pm_camera_rays_pass(void *ctx, int pass, int64_t first, int64_t count, float *rays6, float *film_xy);
 /* Host only: table[j * 16 + i] = (float)F((i + 0.5) / 16 * xwidth, (j + 0.5) /
  * 16 * ywidth), F in double from the float parameters: box 1; triangle
  * max(0, xw - |x|) max(0, yw - |y|); gaussian g(x, xw) g(y, yw) with g(t, w) =
@@ -435,6 +439,51 @@ int pm_commit(void *ctx);
  * raster order), NaN/negative/inf sanitized to black like
  * photonmappingrenderer.cpp:251-268. stats may be NULL. */
 int pm_render(void *ctx, const pm_render_params *params, float *out_rgb, pm_stats *stats);
+
+/* ---- resampled render: a fresh eye sample every pass ----------------------
+ * Stochastic progressive photon mapping (Hachisuka and Jensen 2009): one
+ * record per pixel keeps its statistics (flux, radius2, photon_count) while
+ * its hit point moves under them, every pass, to a fresh sample of
+ * pm_set_camera's jitter and lens. The lens and the pixel area are integrated
+ * over the photon passes; memory and gather cost stay at one record per pixel.
+ *
+ * pm_eye_resample(pass) is eye pass `pass` of such a render:
+ *   pass == 0: pm_eye_pass, bit for bit; the context's eye-sample count is 1.
+ *   pass  > 0: a pending pm_reset_records is applied first. Sample q of pass k
+ *     draws its camera randoms from pmdm_philox4x32_10(lo32(q), hi32(q), 1, k;
+ *     sample_seed, 0) (pm_set_camera's ray with counter word 3 = k) and its
+ *     light samples from (q, slot, 0, k; light_rng_seed, 0). Record r gets
+ *     pos (the hit and this sample's flags: MISS, EXCEPTION, BACKFACE as in
+ *     pm_eye_pass) and ns / material; dl += L, one fp32 add per channel, L
+ *     this sample's direct light with the emitted term, (0, 0, 0) for a miss
+ *     or an exception. flux, radius2 and photon_count are not written, padding
+ *     records (PM_REC_INVALID) not touched. The count goes up by one.
+ *   Both then drop the tile list and the grid plan and rebuild an active
+ *   record view, as pm_eye_pass does. pm_eye_pass sets the count back to 1;
+ *   pm_set_camera, pm_set_pinhole and pm_set_eye_rays to 0; pm_upload_records
+ *   leaves it.
+ * While the count is above 1, pm_final and pm_final_view write, for every
+ * record that is not padding, whatever its last sample's flags,
+ *   dl / (float)count + (flux (1 / pi)) (1 / (radius2 emitted))
+ * per channel in that order (one IEEE division of dl; the second term 0 while
+ * photon_count is 0), sanitised as always: a pixel whose last sample missed
+ * keeps what its earlier samples gathered. A pixel whose pass-0 sample
+ * missed keeps radius2 = 0 and shows direct light only.
+ * PM_ERR_INVALID, with the reason in the message: null params or pass < 0
+ * (checked before the context is); a multi-device context; no pm_set_camera,
+ * or one with xsamples or ysamples != 1 or a filter other than PM_FILTER_NONE
+ * (a record is a pixel; the passes are the samples); an estimator other than
+ * PM_ESTIMATOR_PPM (the kNN final applies the Kd of the record's current
+ * material); a scene with a textured material or one of
+ * pm_add_material_specular (their factor is applied in pm_final, once per
+ * record, which is wrong when the hit moves); pass > 0 before an eye pass or
+ * resample wrote this camera's records. */
+int pm_eye_resample(void *ctx, const pm_render_params *params, int pass, void *stream);
+/* pm_render with pm_eye_resample(pass) in front of each pass's trace and the
+ * final above with count = passes (for passes == 1 the image of pm_render).
+ * out_rgb: float[3 * width * height], raster order. ms_eye is summed over the
+ * passes, gather_points counts the last pass's active records. */
+int pm_render_resampled(void *ctx, const pm_render_params *params, float *out_rgb, pm_stats *stats);
 
 /* ---- simple renderer (SimpleRenderer::render, simple_render/simplerender.cpp:18-103)
  * Direct light only: closest hit of each eye sample, one shadow-tested sample
