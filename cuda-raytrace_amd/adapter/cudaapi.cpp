@@ -210,6 +210,13 @@ void CudaRender::createSubRenderer(Sampler *sampler, Camera *camera, const Param
     pmcuda::RenderSettings s;
     s.params.paths_per_pass = params.FindOneInt("photonpaths", (int)s.params.paths_per_pass);
     s.params.passes = params.FindOneInt("passes", s.params.passes);
+    /* "integer finalgathersamples" [N], N in 1..256: the photon-mapping renderer shoots N gather rays from
+     * every eye hit and takes the kNN estimate at their hits (pm_render_final_gather); 0 (the default): pm_render */
+    s.final_gather = params.FindOneInt("finalgathersamples", 0);
+    if (s.final_gather < 0 || s.final_gather > PM_FG_MAX) {
+        Warning("Renderer \"finalgathersamples\" %d outside 0..%d: final gathering is off", s.final_gather, PM_FG_MAX);
+        s.final_gather = 0;
+    }
     if (params.FindOneString("photonmap", "grid") == "kdtree") s.params.gather_structure = PM_GATHER_KDTREE;
     /* the light the photon paths start on; -1 (PM_ALL_LIGHTS): every light, picked per path by power */
     s.params.light_source_index = params.FindOneInt("lightsource", s.params.light_source_index);

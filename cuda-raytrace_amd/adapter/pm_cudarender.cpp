@@ -391,7 +391,10 @@ void PhotonMappingRenderer::render(CudaRender *r, const std::vector<Light> &, Ca
     /* eye pass -> (photon pass -> photon map -> gather) x passes -> final
      * (photonmappingrenderer.cpp:31-45), NaN / negative / inf -> black */
     rgb.assign((size_t)(3 * n), 0.f);
-    if (camera.resample) /* a fresh eye sample in front of every photon pass; refused scenes fail with the library's message */
+    if (settings.final_gather > 0) /* gather rays from every eye hit; what the library refuses (a resampled camera's
+                                    * records are not: the render runs its own single eye pass) fails with its message */
+        check(ctx, pm_render_final_gather(ctx, &settings.params, settings.final_gather, rgb.data(), &stats), "pm_render_final_gather");
+    else if (camera.resample) /* a fresh eye sample in front of every photon pass; refused scenes fail with the library's message */
         check(ctx, pm_render_resampled(ctx, &settings.params, rgb.data(), &stats), "pm_render_resampled");
     else
         check(ctx, pm_render(ctx, &settings.params, rgb.data(), &stats), "pm_render");

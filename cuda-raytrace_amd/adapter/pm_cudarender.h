@@ -129,6 +129,9 @@ struct Light {
  * pm_render_params for where each comes from) */
 struct RenderSettings {
     pm_render_params params;
+    /* > 0 (1..PM_FG_MAX): the photon-mapping renderer final-gathers with this many rays per eye hit
+     * (pm_render_final_gather; Renderer "cuda" "integer finalgathersamples", --final-gather); 0: pm_render */
+    int final_gather = 0;
     RenderSettings() { pm_default_params(&params); }
 };
 

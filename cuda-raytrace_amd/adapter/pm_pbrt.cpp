@@ -697,6 +697,9 @@ struct PbrtParser::Impl {
                 p.paths_per_pass = ps.oneInt("paths", (int)p.paths_per_pass);
                 p.passes = ps.oneInt("passes", p.passes);
                 opts->resample = ps.oneBool("resample", false);
+                opts->settings.final_gather = ps.oneInt("finalgathersamples", 0);
+                if (opts->settings.final_gather < 0 || opts->settings.final_gather > PM_FG_MAX)
+                    lx.fail(line, "Renderer \"finalgathersamples\": %d is outside 0..%d", opts->settings.final_gather, PM_FG_MAX);
                 opts->specular = ps.oneString("specular", "reference");
                 if (opts->specular != "pbrt" && opts->specular != "reference")
                     lx.fail(line, "Renderer \"specular\": \"%s\" is not \"pbrt\" or \"reference\"", opts->specular.c_str());

@@ -38,7 +38,9 @@
  *                (0.9) and "glass" Kr, Kt, index (1, 1, 1.5) into the
  *                physical model of pm_add_material_specular; a non-constant
  *                texture on one of them warns and leaves the default;
- *                "bool resample": PbrtOptions::resample)
+ *                "bool resample": PbrtOptions::resample;
+ *                "integer finalgathersamples" [N], 0..256: RenderSettings::final_gather,
+ *                N gather rays per eye hit through pm_render_final_gather)
  *                Camera "float lensradius" / "float focaldistance" (thin lens),
  *                Sampler "stratified" (xsamples, ysamples, jitter) or
  *                "lowdiscrepancy" | "bestcandidate" | "random" (pixelsamples N,

@@ -13,6 +13,8 @@
  *                 [--light N|all]
  *                 (a pbrt-v2 scene file through pm_pbrt.h; command-line options override the file)
  *                 [--spp XxY] [--filter name[:xw[:yw[:a[:b]]]]] [--lens R:F] [--no-jitter]   (the device camera + film)
+ *                 [--final-gather N]   (N in 1..256 gather rays per eye hit with a kNN estimate at their hits,
+ *                 pm_render_final_gather; as Renderer "cuda" "integer finalgathersamples" [N] in the scene file; 0: off)
  *                 [--resample]   (a fresh jitter and lens sample per pixel every pass, pm_render_resampled: one
  *                 stratum, no film, jitter on; as Renderer "cuda" "bool resample" ["true"] in the scene file)
  *   pm_render_cli --pbrt scene.pbrt --dump   (parse only, no device: the plugin calls as JSON, with the
@@ -340,6 +342,8 @@ void apply_camera_flags(const CameraFlags &f, PbrtOptions &o) {
 
 /* --specular pbrt|reference: overrides the file's Renderer "string specular" */
 std::string g_specular;
+/* --final-gather N: overrides the file's Renderer "integer finalgathersamples" (-1: not given) */
+int g_final_gather = -1;
 
 int dump(const std::string &path, const CameraFlags &cflags) {
     DumpSink sink;
@@ -348,6 +352,7 @@ int dump(const std::string &path, const CameraFlags &cflags) {
     PbrtParser parser;
     parser.parseFile(path, sink, o);
     apply_camera_flags(cflags, o);
+    if (g_final_gather >= 0) o.settings.final_gather = g_final_gather;
     std::string lights;
     for (const Light &L : o.lights) {
         if (!lights.empty()) lights += ",\n";
@@ -431,9 +436,10 @@ int dump(const std::string &path, const CameraFlags &cflags) {
         }
     }
     std::printf("%s},\n\"renderer\": \"%s\", \"paths\": %lld, \"passes\": %d, \"gather\": %d, \"film\": \"%s\", "
-                "\"light_source_index\": %d, \"light_cdf\": %s], \"resample\": %d, \"warnings\": %d}\n",
+                "\"light_source_index\": %d, \"light_cdf\": %s], \"resample\": %d, \"final_gather\": %d, \"warnings\": %d}\n",
                 cam.c_str(), o.renderer.c_str(), (long long)p.paths_per_pass, p.passes, p.gather_structure,
-                o.film_filename.c_str(), p.light_source_index, cdf.c_str(), o.resample ? 1 : 0, o.warnings);
+                o.film_filename.c_str(), p.light_source_index, cdf.c_str(), o.resample ? 1 : 0, o.settings.final_gather,
+                o.warnings);
     return 0;
 }
 
@@ -467,6 +473,7 @@ int render_pbrt(const std::string &path, std::string out, const std::string &ren
     if (!light.empty()) { p.light_source_index = parse_light(light); check_light(p.light_source_index, o.lights.size()); }
     if (out.empty()) out = o.film_filename;
     apply_camera_flags(cflags, o);
+    if (g_final_gather >= 0) o.settings.final_gather = g_final_gather;
     CudaRender *render = CreateCudaRenderer(o.settings, o.renderer);
     PixelFilm film(o.camera.width, o.camera.height, out); /* the device film writes one value per pixel */
     o.camera.film = &film;
@@ -525,6 +532,13 @@ int main(int argc, char **argv) {
         else if (a == "--lens") cflags.lens = next();
         else if (a == "--no-jitter") cflags.no_jitter = true;
         else if (a == "--resample") cflags.resample = true;
+        else if (a == "--final-gather") {
+            g_final_gather = std::atoi(next());
+            if (g_final_gather < 0 || g_final_gather > PM_FG_MAX) {
+                std::fprintf(stderr, "--final-gather %d: expected 0..%d\n", g_final_gather, PM_FG_MAX);
+                return 2;
+            }
+        }
         else if (a == "--camera") {
             for (float &c : cam) c = std::strtof(next(), nullptr);
             have_cam = true;
@@ -539,8 +553,8 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
-    if (cflags.any()) {
-        std::fprintf(stderr, "--spp, --filter, --lens, --no-jitter and --resample need --pbrt scene.pbrt\n");
+    if (cflags.any() || g_final_gather >= 0) {
+        std::fprintf(stderr, "--spp, --filter, --lens, --no-jitter, --resample and --final-gather need --pbrt scene.pbrt\n");
         return 2;
     }
     if (out.empty()) out = "out.pfm";

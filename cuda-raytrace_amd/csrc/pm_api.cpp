@@ -186,6 +186,7 @@ int pm_create(void **out, const pm_config *cfg) {
     if (const char *e = getenv("PM_TRACE_POOL")) c->trace_pool = atoi(e) != 0;
     if (const char *e = getenv("PM_POOL_STACK")) c->pool_stack = std::max(0, atoi(e));
     if (const char *e = getenv("PM_KD_STACK")) c->kd_stack = std::max(1, std::min(KD_STACK, atoi(e)));
+    if (const char *e = getenv("PM_FG_CHUNK")) c->fg_chunk = std::max<long long>(1, atoll(e));
     if (const char *e = getenv("PM_STAGE_TIMERS")) if (atoi(e) == 0) c->timed_stages.clear();
     (void)hipSetDevice(dev);
     e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -224,7 +225,8 @@ void pm_destroy(void *ptr) {
                       &c->d_dl, &c->d_slots, &c->d_count, &c->d_scratch, &c->d_vflags, &c->d_vrank, &c->d_vlist, &c->d_vsums,
                       &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times,
                       &c->d_kd, &c->d_out, &c->d_counters, &c->d_hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf, &c->d_film_table, &c->d_img,
-                      &c->d_tex_recs, &c->d_texels, &c->d_mat_tex, &c->d_tri_uv, &c->d_rkd, &c->d_mat_spec};
+                      &c->d_tex_recs, &c->d_texels, &c->d_mat_tex, &c->d_tri_uv, &c->d_rkd, &c->d_mat_spec,
+                      &c->d_fg_pos, &c->d_fg_nrm, &c->d_fg_state, &c->d_fg_n, &c->d_fg_dl, &c->d_fg_li, &c->d_fg_sum};
     for (DevBuf *b : bufs) b->release();
     c->tiles.release();
     if (c->hist_event) (void)hipEventDestroy(c->hist_event);

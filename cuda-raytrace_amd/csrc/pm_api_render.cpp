@@ -315,6 +315,53 @@ int pm_render_resampled(void *ptr, const pm_render_params *p, float *out_rgb, pm
     return PM_OK;
 }
 
+/* pm_render's loop with pm_final_gather_pass in the place of the primary
+ * records' gather, and the resolve in the place of the final. The buckets are
+ * built for the kNN estimator, whatever params->estimator says. */
+int pm_render_final_gather(void *ptr, const pm_render_params *p, int n_gather, float *out_rgb, pm_stats *st) {
+    if (!p) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_render_final_gather: null params");
+    if (n_gather < 1 || n_gather > PM_FG_MAX)
+        FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_render_final_gather: n_gather %d outside 1..%d", n_gather, PM_FG_MAX);
+    GETCTX(ptr);
+    int rc;
+    pm_render_params q = *p;
+    q.estimator = PM_ESTIMATOR_KNN;
+    if ((rc = check_params(c, &q))) return rc;
+    if (!out_rgb) FAIL(c, PM_ERR_INVALID, "null output");
+    if (q.passes < 1 || q.paths_per_pass < 1) FAIL(c, PM_ERR_INVALID, "passes and paths_per_pass must be >= 1");
+    if (c->albedo())
+        FAIL(c, PM_ERR_INVALID, "pm_render_final_gather: the scene has a textured or physically specular material; a "
+                                "secondary hit would need its texel or throughput");
+    hipStream_t s = c->stream;
+    double t_eye = 0, t_trace = 0, t_build = 0, t_gather = 0, t_final = 0;
+    if ((rc = pm_eye_pass(c, &q, s))) return rc;
+    t_eye = timer_ms(c, "eye");
+    int64_t nvalid = 0;
+    for (int pass = 0; pass < q.passes; ++pass) {
+        if ((rc = pm_trace_photons(c, &q, pass, 0, q.paths_per_pass, 0, s))) return rc;
+        t_trace += timer_ms(c, "trace");
+        if ((rc = pm_build_photon_map(c, &q, q.paths_per_pass * q.max_photon_count, s))) return rc;
+        t_build += timer_ms(c, "build");
+        if ((rc = valid_photons(c, c, &q, nvalid))) return rc;
+        if ((rc = pm_final_gather_pass(c, &q, n_gather, pass, s))) return rc;
+        /* every chunk of the pass; a stage that is not timed (pm_set_stage_timing) adds nothing */
+        t_gather += std::max(0.0, timer_ms(c, "fgrays", (size_t)c->fg_chunks)) +
+                    std::max(0.0, timer_ms(c, "fgather", (size_t)c->fg_chunks));
+    }
+    const double emitted = (double)q.paths_per_pass * q.passes;
+    const int64_t nout = c->pinhole ? (int64_t)c->W * c->H : c->nrec;
+    HIPCHK(c, c->d_out.ensure(nout * 3 * sizeof(float)));
+    if ((rc = pm_final_gather_resolve(c, 0, c->nrec, c->d_out.p, s))) return rc;
+    if ((rc = deliver_image(c, nout, out_rgb))) return rc;
+    t_final = timer_ms(c, "final");
+    if (st) {
+        if ((rc = render_stats(c, c, emitted, nvalid, st))) return rc;
+        st->ms_eye = t_eye; st->ms_trace = t_trace; st->ms_build = t_build; st->ms_gather = t_gather;
+        st->ms_final = t_final;
+    }
+    return PM_OK;
+}
+
 /* ------------------------------------------------------- simple renderer */
 int pm_simple_pass(void *ptr, const pm_render_params *p, void *d_out, void *stream) {
     GETCTX(ptr);

@@ -425,7 +425,7 @@ int pm_set_pinhole(void *ptr, const float eye[3], const float fwd[3], const floa
     for (int a = 0; a < 3; ++a)
         if (!(fabsf(eye[a]) <= PM_MAX_RAY_ORIGIN) || !std::isfinite(fwd[a]) || !std::isfinite(right[a]) || !std::isfinite(up[a]))
             FAIL(c, PM_ERR_INVALID, "pinhole camera: eye beyond 2^20 or a non-finite vector");
-    c->pinhole = 1; c->W = W; c->H = H; c->camera = 0; c->eye_samples = 0;
+    c->pinhole = 1; c->W = W; c->H = H; c->camera = 0; c->eye_samples = 0; c->fg_passes = 0;
     std::memcpy(c->eye, eye, 12); std::memcpy(c->fwd, fwd, 12);
     std::memcpy(c->right, right, 12); std::memcpy(c->up, up, 12);
     return PM_OK;
@@ -440,7 +440,7 @@ int pm_set_eye_rays(void *ptr, const float *rays, int64_t nrays, const float *ra
         for (int a = 0; a < 3; ++a)
             if (!(fabsf(rays[6 * i + a]) <= PM_MAX_RAY_ORIGIN) || !std::isfinite(rays[6 * i + 3 + a]))
                 FAIL(c, PM_ERR_INVALID, "ray %lld: origin beyond 2^20 or a non-finite component", (long long)i);
-    c->pinhole = 0; c->camera = 0; c->eye_samples = 0;
+    c->pinhole = 0; c->camera = 0; c->eye_samples = 0; c->fg_passes = 0;
     c->nrays = nrays;
     c->rays.assign(rays, rays + 6 * nrays);
     c->n2d = (rand2d && n2d > 0) ? n2d : 0;
@@ -523,7 +523,7 @@ int pm_set_camera(void *ptr, const pm_camera *cam) {
         HIPCHK(c, hipMemcpy(c->d_film_table.p, table, sizeof(table), hipMemcpyHostToDevice));
     }
     c->cam = *cam;
-    c->camera = 1; c->pinhole = 1; c->W = (int)WS; c->H = (int)HS; c->eye_samples = 0;
+    c->camera = 1; c->pinhole = 1; c->W = (int)WS; c->H = (int)HS; c->eye_samples = 0; c->fg_passes = 0;
     std::memcpy(c->eye, cam->eye, 12); std::memcpy(c->fwd, cam->fwd, 12);
     std::memcpy(c->right, cam->right, 12); std::memcpy(c->up, cam->up, 12);
     return PM_OK;

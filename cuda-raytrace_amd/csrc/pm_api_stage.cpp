@@ -45,6 +45,7 @@ int ensure_records(Ctx *c) {
         HIPCHK(c, hipMemcpy(c->d_rkd.p, ones.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
     }
     c->nrec = n;
+    c->fg_passes = 0; /* new primary records: the final-gather sums are another record set's */
     c->tiles.invalidate();
     c->grid_plan.invalidate();
     return PM_OK;
@@ -246,6 +247,7 @@ int pm_eye_resample(void *ptr, const pm_render_params *p, int pass, void *stream
     HIPCHK(c, launch_eye_resample(E, s));
     timer_end(c, "eye", s);
     ++c->eye_samples;
+    c->fg_passes = 0;
     c->tiles.invalidate(); /* the flags moved with the hits */
     c->grid_plan.invalidate();
     if (c->view_active && (rc = build_view(c, s))) return rc;
@@ -962,6 +964,148 @@ int pm_reset_records(void *ptr, const pm_render_params *p, void *stream) {
     c->rec_fresh = true;
     c->rec_fresh_r2 = p->initial_radius2;
     c->grid_plan.invalidate();
+    return PM_OK;
+}
+
+/* ------------------------------------------------------- final gathering */
+/* what pm_final_gather_pass and pm_final_gather_rays refuse alike */
+static int fg_validate(Ctx *c, const pm_render_params *p, const char *fn) {
+    int rc;
+    if ((rc = check_params(c, p))) return rc;
+    if (p->gather_structure != PM_GATHER_GRID)
+        FAIL(c, PM_ERR_INVALID, "%s: the gather rays' kNN estimate runs on the photon buckets (PM_GATHER_GRID)", fn);
+    if (p->knn_lookup < 1 || p->knn_lookup > PM_KNN_MAX)
+        FAIL(c, PM_ERR_INVALID, "%s: knn_lookup must be in [1, %d]", fn, PM_KNN_MAX);
+    if (c->eye_samples < 1 || c->nrec <= 0) FAIL(c, PM_ERR_INVALID, "%s: no records (run pm_eye_pass first)", fn);
+    if (c->eye_samples > 1)
+        FAIL(c, PM_ERR_INVALID, "%s: the records are pm_eye_resample's (%d eye samples); final gathering starts from one "
+                                "eye pass", fn, c->eye_samples);
+    if (c->albedo())
+        FAIL(c, PM_ERR_INVALID, "%s: the scene has a textured or physically specular material; a secondary hit would "
+                                "need its texel or throughput", fn);
+    return PM_OK;
+}
+
+static FgParams fg_params(Ctx *c, const pm_render_params *p, int n_gather, int pass) {
+    FgParams F{};
+    F.S = c->S;
+    F.P = recs(c);
+    F.n_gather = n_gather;
+    F.pass = (uint32_t)pass; F.light_seed = p->light_rng_seed;
+    F.eps = p->scene_epsilon; F.r2init = p->initial_radius2; F.max_spec = p->max_specular_depth;
+    return F;
+}
+
+#define FG_ARGS(fn)                                                                                              \
+    if (!p) FAIL((Ctx *)ptr, PM_ERR_INVALID, fn ": null params");                                                \
+    if (n_gather < 1 || n_gather > PM_FG_MAX)                                                                    \
+        FAIL((Ctx *)ptr, PM_ERR_INVALID, fn ": n_gather %d outside 1..%d", n_gather, PM_FG_MAX);                 \
+    if (pass < 0) FAIL((Ctx *)ptr, PM_ERR_INVALID, fn ": pass %d is negative", pass)
+
+int pm_final_gather_pass(void *ptr, const pm_render_params *p, int n_gather, int pass, void *stream) {
+    FG_ARGS("pm_final_gather_pass"); /* what needs no context is checked before the context is */
+    GETCTX(ptr);
+    int rc;
+    if ((rc = fg_validate(c, p, __func__))) return rc;
+    if (c->map_kind != PM_GATHER_GRID) FAIL(c, PM_ERR_INVALID, "pm_final_gather_pass: no photon map built on the buckets (pm_build_photon_map)");
+    if (!same_grid(c->grid, pm::make_grid(c->bbox_lo, c->bbox_hi, PM_ESTIMATOR_KNN, c->cell_span, p->initial_radius2)))
+        FAIL(c, PM_ERR_INVALID, "pm_final_gather_pass: the photon buckets were not built for PM_ESTIMATOR_KNN with this initial_radius2");
+    if (pass > 0 && (c->fg_passes < 1 || c->fg_n != n_gather || c->fg_nrec != c->nrec))
+        FAIL(c, PM_ERR_INVALID, "pm_final_gather_pass: pass %d continues no pass 0 of %d rays over these records", pass, n_gather);
+    hipStream_t s = pick(c, stream);
+    const int64_t N = n_gather, nrec = c->nrec;
+    /* whole primary tiles per chunk, at least one */
+    const int64_t chunk_recs = std::max<int64_t>(1, c->fg_chunk / (64 * N)) * 64;
+    const int64_t cap = std::min(chunk_recs, (nrec + 63) / 64 * 64) * N;
+    HIPCHK(c, c->d_fg_pos.ensure(cap * sizeof(float4)));
+    HIPCHK(c, c->d_fg_nrm.ensure(cap * sizeof(float4)));
+    HIPCHK(c, c->d_fg_state.ensure(cap * sizeof(float4)));
+    HIPCHK(c, c->d_fg_n.ensure(cap * sizeof(float)));
+    HIPCHK(c, c->d_fg_dl.ensure(cap * sizeof(float4)));
+    HIPCHK(c, c->d_fg_li.ensure(cap * 3 * sizeof(float)));
+    HIPCHK(c, c->d_fg_sum.ensure(nrec * sizeof(float4)));
+    if (pass == 0) { c->fg_passes = 0; c->fg_n = n_gather; c->fg_nrec = nrec; }
+    FgParams F = fg_params(c, p, n_gather, pass);
+    F.R.pos = c->d_fg_pos.as<float4>(); F.R.nrm = c->d_fg_nrm.as<float4>(); F.R.state = c->d_fg_state.as<float4>();
+    F.R.n = c->d_fg_n.as<float>(); F.R.dl = c->d_fg_dl.as<float4>();
+    /* the kNN gather and the final over the chunk's records: the context's
+     * own records, tile list, view and estimator are not part of either */
+    GatherParams G = gather_params(c, p);
+    G.view_rank = nullptr; G.view_list = nullptr;
+    FinalParams L{};
+    L.knn = 1; L.materials = c->S.materials; L.emitted = (float)p->paths_per_pass;
+    L.out = c->d_fg_li.as<float>(); L.W = c->W;
+    FgSumParams A{};
+    A.P = F.P; A.li = L.out; A.sum = c->d_fg_sum.as<float4>(); A.n_gather = n_gather; A.zero = pass == 0;
+    for (int64_t r0 = 0; r0 < nrec; r0 += chunk_recs) {
+        const int64_t nr = std::min(chunk_recs, nrec - r0);
+        F.sec_begin = r0 * N;
+        F.R.count = nr * N;
+        timer_begin(c, "fgrays", s);
+        HIPCHK(c, launch_fg_rays(F, s));
+        timer_end(c, "fgrays", s);
+        G.R = F.R; G.rec_begin = 0; G.rec_end = F.R.count;
+        timer_begin(c, "fgather", s);
+        if ((rc = gather_knn_setup(c, p, G))) return rc;
+        HIPCHK(c, launch_gather_knn(G, 0, s));
+        L.R = F.R; L.rec_begin = 0; L.rec_count = F.R.count;
+        HIPCHK(c, launch_final(L, s));
+        A.rec_begin = r0; A.rec_count = nr;
+        HIPCHK(c, launch_fg_accumulate(A, s));
+        timer_end(c, "fgather", s);
+    }
+    c->fg_chunks = (nrec + chunk_recs - 1) / chunk_recs;
+    ++c->fg_passes;
+    return PM_OK;
+}
+
+int pm_final_gather_resolve(void *ptr, int64_t rec_begin, int64_t rec_count, void *d_out, void *stream) {
+    GETCTX(ptr);
+    if (c->fg_passes < 1 || c->fg_nrec != c->nrec || c->nrec <= 0)
+        FAIL(c, PM_ERR_INVALID, "pm_final_gather_resolve: no final-gather pass over these records (pm_final_gather_pass)");
+    if (!d_out || rec_begin < 0 || rec_count < 0 || rec_begin + rec_count > c->nrec)
+        FAIL(c, PM_ERR_INVALID, "pm_final_gather_resolve: bad record range");
+    hipStream_t s = pick(c, stream);
+    FgResolveParams R{};
+    R.P = recs(c); R.sum = c->d_fg_sum.as<float4>(); R.materials = c->S.materials;
+    R.denom = (float)((int64_t)c->fg_n * c->fg_passes);
+    R.rec_begin = rec_begin; R.rec_count = rec_count; R.out = (float *)d_out; R.raster = c->pinhole; R.W = c->W;
+    timer_begin(c, "final", s);
+    HIPCHK(c, launch_fg_resolve(R, s));
+    timer_end(c, "final", s);
+    return PM_OK;
+}
+
+int pm_final_gather_rays(void *ptr, const pm_render_params *p, int n_gather, int pass, int64_t first, int64_t count,
+                         float *rays6) {
+    FG_ARGS("pm_final_gather_rays");
+    GETCTX(ptr);
+    int rc;
+    if ((rc = fg_validate(c, p, __func__))) return rc;
+    if (!rays6 || first < 0 || count < 0 || first + count > c->nrec * (int64_t)n_gather)
+        FAIL(c, PM_ERR_INVALID, "pm_final_gather_rays: bad ray range");
+    if (count == 0) return PM_OK;
+    DevBuf d;
+    HIPCHK(c, d.ensure((size_t)count * 6 * sizeof(float)));
+    const FgParams F = fg_params(c, p, n_gather, pass);
+    hipError_t e = launch_fg_ray_dump(F, first, count, d.as<float>(), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rays6, d.p, (size_t)count * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    d.release();
+    HIPCHK(c, e);
+    return PM_OK;
+}
+
+int pm_download_gather_sum(void *ptr, float *out_rgb, int64_t n) {
+    GETCTX(ptr);
+    if (!out_rgb) FAIL(c, PM_ERR_INVALID, "pm_download_gather_sum: null pointer");
+    if (c->fg_passes < 1 || n < 0 || n > c->fg_nrec || !c->d_fg_sum.p)
+        FAIL(c, PM_ERR_INVALID, "pm_download_gather_sum: %lld sums asked, %lld held (pm_final_gather_pass)", (long long)n,
+             (long long)(c->fg_passes < 1 ? 0 : c->fg_nrec));
+    HIPCHK(c, hipDeviceSynchronize());
+    std::vector<float4> a((size_t)n);
+    HIPCHK(c, hipMemcpy(a.data(), c->d_fg_sum.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) { out_rgb[3 * i] = a[i].x; out_rgb[3 * i + 1] = a[i].y; out_rgb[3 * i + 2] = a[i].z; }
     return PM_OK;
 }
 

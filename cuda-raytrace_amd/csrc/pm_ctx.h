@@ -217,7 +217,16 @@ struct Ctx {
     /* estimator of the last gather: what the records' flux / radius2 /
      * photon_count mean for the final pass (PPM state or kNN sums) */
     int rec_estimator = PM_ESTIMATOR_PPM;
-    int kd_stack = KD_STACK;        /* kd gather stack entries (env PM_KD_STACK, tests only) */
+    /* final gathering (pm_final_gather_pass): the secondary records of one
+     * chunk and k_final's radiances over them, the sums A (a float4 per
+     * primary record, valid for fg_nrec records of fg_n rays over fg_passes
+     * passes; any new primary records drop them) and the chunk cap in
+     * secondary records (env PM_FG_CHUNK, tests only) */
+    DevBuf d_fg_pos, d_fg_nrm, d_fg_state, d_fg_n, d_fg_dl, d_fg_li, d_fg_sum;
+    int64_t fg_nrec = 0, fg_chunk = (int64_t)1 << 22;
+    int fg_n = 0, fg_passes = 0;
+    int64_t fg_chunks = 0; /* chunks (launches per stage timer) of the last pass */
+    int kd_stack = KD_STACK;       /* kd gather stack entries (env PM_KD_STACK, tests only) */
     bool trace_pool = true;         /* 4-wide scenes: the pooled trace kernel (env PM_TRACE_POOL=0: one path per lane) */
     bool trace_hold = true;         /* deposits written once per path where it costs no waves (env PM_TRACE_HOLD=0: per deposit) */
     int pool_stack = 31;            /* pooled kernel: LDS stack entries per lane (env PM_POOL_STACK; 0 = the exact bound): 31 lets five blocks share a CU's LDS */

@@ -1,7 +1,7 @@
 /*
  * pm_kernels.h — kernel parameter blocks and launcher declarations shared by
  * the host orchestration (pm_api*.cpp around pm_ctx.h) and the HIP kernels (pm_trace.hip, pm_eye.hip, pm_bucket.hip,
- * pm_gather.hip, pm_gather_knn.hip, pm_records.hip, pm_bvh_gpu.hip, pm_film.hip).
+ * pm_gather.hip, pm_gather_knn.hip, pm_records.hip, pm_bvh_gpu.hip, pm_film.hip, pm_fgather.hip).
  */
 #pragma once
 #include <hip/hip_ext.h>
@@ -293,6 +293,38 @@ struct FinalParams {
     int n_eye, resampled;
 };
 
+/* final gathering (pm_fgather.hip; pm_api.h pm_final_gather_pass states the
+ * operation). Secondary record s = r * n_gather + j is gather ray j of primary
+ * record r; a launch covers the secondary records [sec_begin, sec_begin +
+ * R.count) of whole primary tiles, stored at R[s - sec_begin]. */
+struct FgParams {
+    SceneDev S;
+    RecordsDev P;  /* the primary records (pm_eye_pass); read only */
+    RecordsDev R;  /* the chunk's secondary records; R.count of them */
+    int64_t sec_begin;
+    int n_gather;
+    uint32_t pass, light_seed;
+    float eps, r2init;
+    int max_spec;
+};
+struct FgSumParams {
+    RecordsDev P;
+    const float *li;   /* k_final's output over the chunk's secondary records, float3 in record order */
+    float4 *sum;       /* A, one float4 per primary record */
+    int64_t rec_begin, rec_count; /* the chunk's primary records */
+    int n_gather;
+    int zero;          /* pass 0: A starts from 0 */
+};
+struct FgResolveParams {
+    RecordsDev P;
+    const float4 *sum;
+    const float4 *materials;
+    float denom;       /* (float)(n_gather * passes) */
+    int64_t rec_begin, rec_count;
+    float *out;        /* float3 */
+    int raster, W;     /* as FinalParams */
+};
+
 /* traversal mode of a scene: LDS-resident blob (brute force when tiny) or HBM */
 inline int scene_mode(const SceneDev &S) {
     return S.n_inst > 0 ? MODE_INST : S.lds_bytes ? (S.brute ? MODE_BRUTE : MODE_LDS) : MODE_GLOBAL;
@@ -349,6 +381,14 @@ hipError_t launch_ppm_update_radius(const GatherParams &p, const int *count, flo
 hipError_t launch_ppm_update_flux(const GatherParams &p, const float *ratio, const long long *flux, int64_t v_begin,
                                   int64_t v_count, hipStream_t s);
 hipError_t launch_final(const FinalParams &p, hipStream_t s);
+/* final gathering (pm_fgather.hip): the chunk's gather rays traced and shaded
+ * into its secondary records; rays6 non-null: only the rays (o.xyz, d.xyz;
+ * d = 0 for a ray that is not traced) of secondary records [first, first +
+ * count), nothing traced (p.R unused) */
+hipError_t launch_fg_rays(const FgParams &p, hipStream_t s);
+hipError_t launch_fg_ray_dump(const FgParams &p, int64_t first, int64_t count, float *rays6, hipStream_t s);
+hipError_t launch_fg_accumulate(const FgSumParams &p, hipStream_t s);
+hipError_t launch_fg_resolve(const FgResolveParams &p, hipStream_t s);
 /* list[0 .. *count) = the tiles (records [64 t, 64 t + 64)) holding an
  * active record, ascending, built on the device (flags: one byte per tile) */
 /* the slots of [0, n) whose fused-count key is invalid (0xffffffff) set to

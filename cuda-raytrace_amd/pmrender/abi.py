@@ -26,6 +26,7 @@ PM_REC_INACTIVE = PM_REC_EXCEPTION | PM_REC_MISS | PM_REC_INVALID
 PM_GATHER_GRID, PM_GATHER_KDTREE = 0, 1
 PM_ESTIMATOR_PPM, PM_ESTIMATOR_KNN = 0, 1
 PM_KNN_MAX = 64
+PM_FG_MAX = 256  # largest n_gather of pm_final_gather_pass
 PM_ALL_LIGHTS = -1  # light_source_index: photon paths start on every light, picked by power
 PM_PHOTON_MAX_RIGHT_CHILD = (1 << 29) - 1
 # pm_filter::type; PM_FILM_TABLE: the film's weight table is 16 x 16 (pbrt ImageFilm)

@@ -70,6 +70,11 @@ def load_library(path=None):
         "pm_camera_rays_pass": (c_int, [vp, c_int, i64, i64, P_f, P_f]),
         "pm_eye_resample": (c_int, [vp, ctypes.POINTER(RenderParams), c_int, vp]),
         "pm_render_resampled": (c_int, [vp, ctypes.POINTER(RenderParams), P_f, ctypes.POINTER(Stats)]),
+        "pm_final_gather_pass": (c_int, [vp, ctypes.POINTER(RenderParams), c_int, c_int, vp]),
+        "pm_final_gather_resolve": (c_int, [vp, i64, i64, vp, vp]),
+        "pm_render_final_gather": (c_int, [vp, ctypes.POINTER(RenderParams), c_int, P_f, ctypes.POINTER(Stats)]),
+        "pm_final_gather_rays": (c_int, [vp, ctypes.POINTER(RenderParams), c_int, c_int, i64, i64, P_f]),
+        "pm_download_gather_sum": (c_int, [vp, P_f, i64]),
         "pm_film_filter_table": (c_int, [ctypes.POINTER(Filter), P_f]),
         "pm_commit": (c_int, [vp]),
         "pm_render": (c_int, [vp, ctypes.POINTER(RenderParams), P_f, ctypes.POINTER(Stats)]),
@@ -397,6 +402,19 @@ class Context:
         self._chk(self.lib.pm_render_resampled(self.h, ctypes.byref(params), fptr(out), ctypes.byref(st)))
         return out.reshape(self.height, self.width, 3), st.as_dict()
 
+    def render_final_gather(self, params=None, n_gather=32):
+        """pm_render_final_gather: the indirect light of every eye hit from n_gather cosine-sampled
+        gather rays with a kNN estimate at their hits, not from the photon map at the hit itself."""
+        params = params or RenderParams.defaults()
+        oh, ow = self._out_shape()
+        n = oh * ow if self.pinhole else self.num_records()
+        out = np.zeros((n, 3), np.float32)
+        st = Stats()
+        self._chk(self.lib.pm_render_final_gather(self.h, ctypes.byref(params), int(n_gather), fptr(out), ctypes.byref(st)))
+        if self.pinhole:
+            out = out.reshape(oh, ow, 3)
+        return out, st.as_dict()
+
     def render_simple(self, params=None):
         """SimpleRenderer (simplerender.cpp:18-103): direct light only."""
         params = params or RenderParams.simple_defaults()
@@ -469,6 +487,44 @@ class Context:
     def final(self, emitted, rec_begin, rec_count, d_out, stream=None):
         self._chk(self.lib.pm_final(self.h, float(emitted), int(rec_begin), int(rec_count), ctypes.c_void_p(d_out),
                                     stream))
+
+    def final_gather_pass(self, params, n_gather, pass_=0, stream=None):
+        """pm_final_gather_pass: n_gather gather rays per active record against the built photon
+        buckets, their radiances added to the records' sums (pass_ 0 starts the sums)."""
+        self._chk(self.lib.pm_final_gather_pass(self.h, ctypes.byref(params), int(n_gather), int(pass_), stream))
+
+    def final_gather_resolve(self, rec_begin=0, rec_count=None):
+        """pm_final_gather_resolve of records [rec_begin, rec_begin + rec_count) into a zeroed torch
+        device buffer, returned on the host: the (H, W, 3) raster for pinhole and camera contexts
+        (the call writes in raster order), else (rec_count, 3) in record order."""
+        import torch
+        n = self.num_records()
+        if rec_count is None:
+            rec_count = n - rec_begin
+        rows = self.height * self.width if self.pinhole else rec_count
+        d = torch.zeros((rows, 3), dtype=torch.float32, device=f"cuda:{self.device}")
+        torch.cuda.synchronize()
+        self._chk(self.lib.pm_final_gather_resolve(self.h, int(rec_begin), int(rec_count), ctypes.c_void_p(d.data_ptr()), None))
+        self.synchronize()
+        out = d.cpu().numpy()
+        return out.reshape(self.height, self.width, 3) if self.pinhole else out
+
+    def final_gather_rays(self, params, n_gather, pass_=0, first=0, count=None):
+        """(count, 6) rays (o, d) of secondary records [first, first + count), by the device function
+        final_gather_pass calls; all zero for a ray that is not traced (pm_final_gather_rays)."""
+        if count is None:
+            count = self.num_records() * int(n_gather) - first
+        rays = np.zeros((count, 6), np.float32)
+        self._chk(self.lib.pm_final_gather_rays(self.h, ctypes.byref(params), int(n_gather), int(pass_), int(first),
+                                                int(count), fptr(rays)))
+        return rays
+
+    def gather_sum(self, n=None):
+        """The final-gather sums A of the first n primary records, (n, 3) (pm_download_gather_sum)."""
+        n = self.num_records() if n is None else int(n)
+        out = np.zeros((n, 3), np.float32)
+        self._chk(self.lib.pm_download_gather_sum(self.h, fptr(out), n))
+        return out
 
     def final_image(self, emitted):
         """pm_final over all records into a torch device buffer, returned on the

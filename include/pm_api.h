@@ -485,6 +485,81 @@ int pm_eye_resample(void *ctx, const pm_render_params *params, int pass, void *s
  * passes, gather_points counts the last pass's active records. */
 int pm_render_resampled(void *ctx, const pm_render_params *params, float *out_rgb, pm_stats *stats);
 
+/* ---- final gathering: cosine-sampled gather rays, a kNN estimate at their hits
+ * pbrt-v2's photon integrator does not show the photon map directly: at each
+ * eye hit it shoots gather rays over the hemisphere and takes the density
+ * estimate at their hits. The trace deposits a path's first diffuse hit only
+ * behind a specular bounce, so the map holds indirect and caustic light; the
+ * direct light at every hit comes from the eye pass's shading.
+ *
+ * Primary records are pm_eye_pass's; N = n_gather in 1..256. Secondary record
+ * s = r N + j is gather ray j of primary record r. A record is active when it
+ * has none of MISS, EXCEPTION, INVALID. All of it fp32 without contraction, in
+ * the order written:
+ *   rotation  o = pmdm_philox4x32_10(lo32(r), hi32(r), 3, pass; light_rng_seed, 0),
+ *             ru = pmdm_u01(o[0]), rv = pmdm_u01(o[1])
+ *   sample    a = ((float)j + 0.5f) / (float)N + ru, u1 = a - floorf(a);
+ *             b = (float)bitreverse32(j) * 2^-32 + rv, u2 = b - floorf(b);
+ *             both held to at most 1 - 2^-24 (a rotated Hammersley set)
+ *   direction (dx, dy) = the concentric disk map of (u1, u2) (the disk light's);
+ *             z = sqrtf(fmaxf(0, 1 - dx dx - dy dy)); n = the record's ns,
+ *             negated under PM_REC_BACKFACE; (v1, v2) = pbrt's
+ *             CoordinateSystem(n): |n.x| > |n.y| ? il = 1 / sqrtf(n.x n.x + n.z n.z),
+ *             v1 = (-n.z il, 0, n.x il) : il = 1 / sqrtf(n.y n.y + n.z n.z),
+ *             v1 = (0, n.z il, -n.y il); v2 = cross(n, v1);
+ *             v = (dx v1 + dy v2) + z n, d = v * (1 / sqrtf(v.v)), the dot
+ *             product summed x, y, z. A ray with z == 0 is not traced.
+ *   ray       origin the record's pos, tmin = scene_epsilon, no far limit
+ *   hit       found and shaded as pm_eye_pass does for a host-supplied ray
+ *             (the traversal of the scene's mode, the reference model's mirror
+ *             and glass chain up to max_specular_depth, the same flags, ns and
+ *             material), with two differences: the 2-D sample of light slot t
+ *             is (pmdm_u01(o[0]), pmdm_u01(o[1])) of pmdm_philox4x32_10(lo32(s),
+ *             hi32(s), 0, pass; light_rng_seed, t), and the emitted term of a
+ *             hit on a light is left out (the primary record's dl holds it).
+ *             The secondary record starts with flux 0, photon_count 0, radius2
+ *             = initial_radius2. A ray that is not traced, or of an inactive
+ *             primary record, gives a MISS record.
+ *   radiance  the kNN gather of PM_ESTIMATOR_KNN (knn_lookup, initial_radius2)
+ *             over the secondary records against the built photon buckets,
+ *             then pm_final's kNN form with emitted = paths_per_pass: Li_j,
+ *             sanitised, 0 for an inactive record
+ *   sum       A_r += Li_j per channel in ascending j. pass == 0 starts A from
+ *             0 and the pass count P from 0; every call adds 1 to P.
+ * pm_final_gather_resolve writes out_r = dl_r + Kd_r x (A_r / (float)(N P)),
+ * one IEEE division per channel, Kd_r the materials table's for the record's
+ * material (0 unless PM_MATTE), sanitised as pm_final does; an inactive record
+ * gets what pm_final writes for it; raster order for pinhole and camera
+ * contexts, else record order, [rec_begin, rec_begin + rec_count) as pm_final.
+ * Secondary records are made and used in chunks of whole 64-record primary
+ * tiles, at most 2^22 of them at a time (env PM_FG_CHUNK, for tests); the
+ * result does not depend on the chunk. The primary records, the tile list,
+ * the record view and the estimator the records are read under stay as they
+ * were.
+ * PM_ERR_INVALID, with the reason in the message: null params, n_gather
+ * outside 1..256, pass < 0 (these before the context is checked); a
+ * multi-device context; gather_structure != PM_GATHER_GRID; no eye pass yet;
+ * no built bucket map; records of pm_eye_resample; a scene with a textured
+ * material or one of pm_add_material_specular (a secondary hit would need its
+ * texel or throughput); pass > 0 with another n_gather or other records than
+ * pass 0's; a resolve before any pass. */
+#define PM_FG_MAX 256
+int pm_final_gather_pass(void *ctx, const pm_render_params *params, int n_gather, int pass, void *stream);
+int pm_final_gather_resolve(void *ctx, int64_t rec_begin, int64_t rec_count, void *d_out, void *stream);
+/* One eye pass; per pass trace, bucket build, pm_final_gather_pass(pass);
+ * resolve; the film as pm_render applies it. The primary records' own gather
+ * is not run. ms_gather carries the final-gather time (stages "fgrays": the
+ * rays, "fgather": the kNN gather, final and sum over them), ms_final the
+ * resolve. */
+int pm_render_final_gather(void *ctx, const pm_render_params *params, int n_gather, float *out_rgb, pm_stats *stats);
+/* Test hooks like pm_camera_rays: the rays (o.xyz, d.xyz) of secondary records
+ * [first, first + count) by the device function pm_final_gather_pass calls,
+ * with a zero direction for a ray that is not traced (all six zero for the
+ * rays of an inactive record); and A (rgb) of the first n primary records. */
+int pm_final_gather_rays(void *ctx, const pm_render_params *params, int n_gather, int pass, int64_t first,
+                         int64_t count, float *rays6);
+int pm_download_gather_sum(void *ctx, float *out_rgb, int64_t n);
+
 /* ---- simple renderer (SimpleRenderer::render, simple_render/simplerender.cpp:18-103)
  * Direct light only: closest hit of each eye sample, one shadow-tested sample
  * per light (sample index 0, no pdf division, no emitted term,
@@ -666,7 +741,7 @@ int pm_set_counting(void *ctx, int enabled);
 int pm_synchronize(void *ctx);
 /* Stage timings measured with HIP events recorded on the stream the kernels
  * run on. Stage names: "eye", "trace", "build", "gather", "update", "final",
- * "reset". last = most recent launch; total = sum over launches since
+ * "reset", "film", "simple", "fgrays", "fgather". last = most recent launch; total = sum over launches since
  * pm_timing_reset (synchronizes on the last event only when read). */
 int pm_last_kernel_ms(void *ctx, const char *name, double *ms);
 /* Which stages record events: "all" (default), "" / NULL (none) or a comma
