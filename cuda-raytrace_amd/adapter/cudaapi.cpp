@@ -217,6 +217,12 @@ void CudaRender::createSubRenderer(Sampler *sampler, Camera *camera, const Param
         Warning("Renderer \"finalgathersamples\" %d outside 0..%d: final gathering is off", s.final_gather, PM_FG_MAX);
         s.final_gather = 0;
     }
+    /* "bool causticmap" ["true"]: the caustic map looked up at the eye hits (pm_set_caustic_map), with final gathering only */
+    s.caustic_map = params.FindOneBool("causticmap", false);
+    if (s.caustic_map && s.final_gather == 0) {
+        Warning("Renderer \"causticmap\" needs \"finalgathersamples\": the caustic map is off%s", "");
+        s.caustic_map = false;
+    }
     if (params.FindOneString("photonmap", "grid") == "kdtree") s.params.gather_structure = PM_GATHER_KDTREE;
     /* the light the photon paths start on; -1 (PM_ALL_LIGHTS): every light, picked per path by power */
     s.params.light_source_index = params.FindOneInt("lightsource", s.params.light_source_index);

@@ -391,6 +391,8 @@ void PhotonMappingRenderer::render(CudaRender *r, const std::vector<Light> &, Ca
     /* eye pass -> (photon pass -> photon map -> gather) x passes -> final
      * (photonmappingrenderer.cpp:31-45), NaN / negative / inf -> black */
     rgb.assign((size_t)(3 * n), 0.f);
+    if (settings.final_gather > 0 && settings.caustic_map) /* off is the context's default; a multi-device context has no switch */
+        check(ctx, pm_set_caustic_map(ctx, 1), "pm_set_caustic_map");
     if (settings.final_gather > 0) /* gather rays from every eye hit; what the library refuses (a resampled camera's
                                     * records are not: the render runs its own single eye pass) fails with its message */
         check(ctx, pm_render_final_gather(ctx, &settings.params, settings.final_gather, rgb.data(), &stats), "pm_render_final_gather");

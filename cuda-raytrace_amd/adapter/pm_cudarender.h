@@ -132,6 +132,9 @@ struct RenderSettings {
     /* > 0 (1..PM_FG_MAX): the photon-mapping renderer final-gathers with this many rays per eye hit
      * (pm_render_final_gather; Renderer "cuda" "integer finalgathersamples", --final-gather); 0: pm_render */
     int final_gather = 0;
+    /* with final_gather > 0: the caustic map looked up at the eye hits (pm_set_caustic_map; Renderer "cuda"
+     * "bool causticmap", --caustic-map). Without final gathering it is not honoured: the front ends warn */
+    bool caustic_map = false;
     RenderSettings() { pm_default_params(&params); }
 };
 

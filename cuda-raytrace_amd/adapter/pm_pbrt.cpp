@@ -700,6 +700,8 @@ struct PbrtParser::Impl {
                 opts->settings.final_gather = ps.oneInt("finalgathersamples", 0);
                 if (opts->settings.final_gather < 0 || opts->settings.final_gather > PM_FG_MAX)
                     lx.fail(line, "Renderer \"finalgathersamples\": %d is outside 0..%d", opts->settings.final_gather, PM_FG_MAX);
+                /* honoured only together with finalgathersamples: checked once the command line's overrides are applied (pm_render_cli apply_final_gather_flags) */
+                opts->settings.caustic_map = ps.oneBool("causticmap", false);
                 opts->specular = ps.oneString("specular", "reference");
                 if (opts->specular != "pbrt" && opts->specular != "reference")
                     lx.fail(line, "Renderer \"specular\": \"%s\" is not \"pbrt\" or \"reference\"", opts->specular.c_str());

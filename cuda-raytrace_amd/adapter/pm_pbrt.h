@@ -40,7 +40,10 @@
  *                texture on one of them warns and leaves the default;
  *                "bool resample": PbrtOptions::resample;
  *                "integer finalgathersamples" [N], 0..256: RenderSettings::final_gather,
- *                N gather rays per eye hit through pm_render_final_gather)
+ *                N gather rays per eye hit through pm_render_final_gather;
+ *                "bool causticmap" ["true"]: RenderSettings::caustic_map, the
+ *                caustic map looked up at the eye hits, only together with
+ *                finalgathersamples: pm_render_cli warns otherwise)
  *                Camera "float lensradius" / "float focaldistance" (thin lens),
  *                Sampler "stratified" (xsamples, ysamples, jitter) or
  *                "lowdiscrepancy" | "bestcandidate" | "random" (pixelsamples N,

@@ -21,6 +21,7 @@
  *        [--lightsource K]  (Renderer "cuda" "integer lightsource" [K]; -1: photons from every light)
  *        [--caustic]     (scenes/caustic-fresnel.pbrt: a GlassMaterial sphere and a MirrorMaterial sphere instead of the blocks)
  *        [--specular pbrt|reference]  (Renderer "cuda" "string specular": pbrt = the Fresnel model with the materials' Kr, Kt, index)
+ *        [--caustic-map]  (Renderer "cuda" "bool causticmap" ["true"]: the caustic map at the eye hits; with --final-gather)
  *        [--final-gather N]  (Renderer "cuda" "integer finalgathersamples" [N]: N gather rays per eye hit, pm_render_final_gather)
  *        [--resample]    (Renderer "cuda" "bool resample" ["true"]: a fresh eye sample per pass; --lensradius R --focaldistance F --passes P)
  * The header's third word is the number of light 2D samples per ray
@@ -61,6 +62,7 @@ struct Opts {
     bool resample = false; /* --resample: the ParamSet's "bool resample" (with --lensradius / --focaldistance / --passes) */
     int passes = 1;
     int final_gather = 0; /* --final-gather N: the ParamSet's "integer finalgathersamples" */
+    bool caustic_map = false; /* --caustic-map: the ParamSet's "bool causticmap" */
 };
 
 /* pixel centres in raster order, one sample per pixel; light 2D randoms:
@@ -281,6 +283,7 @@ int run(const Opts &o) {
     }
     if (o.passes != 1) params.AddInt("passes", &o.passes, 1);
     if (o.final_gather) params.AddInt("finalgathersamples", &o.final_gather, 1);
+    if (o.caustic_map) params.AddBool("causticmap", &o.caustic_map, 1);
     CentreSampler *sampler = new CentreSampler(o.W, o.H);
     Renderer *renderer = CreateCudaRenderer(sampler, camera, params, o.renderer == "simple" ? "simple" : "photonmap");
     /* pbrtWorldEnd */
@@ -334,6 +337,7 @@ int main(int argc, char **argv) {
         else if (a == "--resample") o.resample = true;
         else if (a == "--passes") o.passes = std::stoi(val());
         else if (a == "--final-gather") o.final_gather = std::stoi(val());
+        else if (a == "--caustic-map") o.caustic_map = true;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (o.out.empty()) { std::fprintf(stderr, "usage: %s --out f.bin [options]\n", argv[0]); return 2; }

@@ -15,6 +15,8 @@
  *                 [--spp XxY] [--filter name[:xw[:yw[:a[:b]]]]] [--lens R:F] [--no-jitter]   (the device camera + film)
  *                 [--final-gather N]   (N in 1..256 gather rays per eye hit with a kNN estimate at their hits,
  *                 pm_render_final_gather; as Renderer "cuda" "integer finalgathersamples" [N] in the scene file; 0: off)
+ *                 [--caustic-map]   (with final gathering: the caustic map looked up at the eye hits, pm_set_caustic_map;
+ *                 as Renderer "cuda" "bool causticmap" ["true"] in the scene file; warns without final gathering)
  *                 [--resample]   (a fresh jitter and lens sample per pixel every pass, pm_render_resampled: one
  *                 stratum, no film, jitter on; as Renderer "cuda" "bool resample" ["true"] in the scene file)
  *   pm_render_cli --pbrt scene.pbrt --dump   (parse only, no device: the plugin calls as JSON, with the
@@ -344,6 +346,21 @@ void apply_camera_flags(const CameraFlags &f, PbrtOptions &o) {
 std::string g_specular;
 /* --final-gather N: overrides the file's Renderer "integer finalgathersamples" (-1: not given) */
 int g_final_gather = -1;
+/* --caustic-map: as the file's Renderer "bool causticmap" ["true"] */
+bool g_caustic_map = false;
+
+/* the command line's final-gather settings over the file's; the caustic map is honoured only together with
+ * final gathering and warns otherwise */
+void apply_final_gather_flags(PbrtOptions &o) {
+    if (g_final_gather >= 0) o.settings.final_gather = g_final_gather;
+    if (g_caustic_map) o.settings.caustic_map = true;
+    if (o.settings.caustic_map && o.settings.final_gather == 0) {
+        std::fprintf(stderr, "Warning: the caustic map (Renderer \"causticmap\", --caustic-map) needs final gathering "
+                             "(\"finalgathersamples\", --final-gather): it is off\n");
+        o.settings.caustic_map = false;
+        o.warnings++;
+    }
+}
 
 int dump(const std::string &path, const CameraFlags &cflags) {
     DumpSink sink;
@@ -352,7 +369,7 @@ int dump(const std::string &path, const CameraFlags &cflags) {
     PbrtParser parser;
     parser.parseFile(path, sink, o);
     apply_camera_flags(cflags, o);
-    if (g_final_gather >= 0) o.settings.final_gather = g_final_gather;
+    apply_final_gather_flags(o);
     std::string lights;
     for (const Light &L : o.lights) {
         if (!lights.empty()) lights += ",\n";
@@ -436,10 +453,10 @@ int dump(const std::string &path, const CameraFlags &cflags) {
         }
     }
     std::printf("%s},\n\"renderer\": \"%s\", \"paths\": %lld, \"passes\": %d, \"gather\": %d, \"film\": \"%s\", "
-                "\"light_source_index\": %d, \"light_cdf\": %s], \"resample\": %d, \"final_gather\": %d, \"warnings\": %d}\n",
+                "\"light_source_index\": %d, \"light_cdf\": %s], \"resample\": %d, \"final_gather\": %d, \"caustic_map\": %d, \"warnings\": %d}\n",
                 cam.c_str(), o.renderer.c_str(), (long long)p.paths_per_pass, p.passes, p.gather_structure,
                 o.film_filename.c_str(), p.light_source_index, cdf.c_str(), o.resample ? 1 : 0, o.settings.final_gather,
-                o.warnings);
+                o.settings.caustic_map ? 1 : 0, o.warnings);
     return 0;
 }
 
@@ -473,7 +490,7 @@ int render_pbrt(const std::string &path, std::string out, const std::string &ren
     if (!light.empty()) { p.light_source_index = parse_light(light); check_light(p.light_source_index, o.lights.size()); }
     if (out.empty()) out = o.film_filename;
     apply_camera_flags(cflags, o);
-    if (g_final_gather >= 0) o.settings.final_gather = g_final_gather;
+    apply_final_gather_flags(o);
     CudaRender *render = CreateCudaRenderer(o.settings, o.renderer);
     PixelFilm film(o.camera.width, o.camera.height, out); /* the device film writes one value per pixel */
     o.camera.film = &film;
@@ -539,6 +556,7 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+        else if (a == "--caustic-map") g_caustic_map = true;
         else if (a == "--camera") {
             for (float &c : cam) c = std::strtof(next(), nullptr);
             have_cam = true;
@@ -553,8 +571,8 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
-    if (cflags.any() || g_final_gather >= 0) {
-        std::fprintf(stderr, "--spp, --filter, --lens, --no-jitter, --resample and --final-gather need --pbrt scene.pbrt\n");
+    if (cflags.any() || g_final_gather >= 0 || g_caustic_map) {
+        std::fprintf(stderr, "--spp, --filter, --lens, --no-jitter, --resample, --final-gather and --caustic-map need --pbrt scene.pbrt\n");
         return 2;
     }
     if (out.empty()) out = "out.pfm";

@@ -226,7 +226,8 @@ void pm_destroy(void *ptr) {
                       &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times,
                       &c->d_kd, &c->d_out, &c->d_counters, &c->d_hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf, &c->d_film_table, &c->d_img,
                       &c->d_tex_recs, &c->d_texels, &c->d_mat_tex, &c->d_tri_uv, &c->d_rkd, &c->d_mat_spec,
-                      &c->d_fg_pos, &c->d_fg_nrm, &c->d_fg_state, &c->d_fg_n, &c->d_fg_dl, &c->d_fg_li, &c->d_fg_sum};
+                      &c->d_fg_pos, &c->d_fg_nrm, &c->d_fg_state, &c->d_fg_n, &c->d_fg_dl, &c->d_fg_li, &c->d_fg_sum,
+                      &c->d_cg_count, &c->d_cg_cell_start, &c->d_cg_scratch, &c->d_cg_pha, &c->d_cg_phb, &c->d_cg_knnpk, &c->d_cg_knnovf};
     for (DevBuf *b : bufs) b->release();
     c->tiles.release();
     if (c->hist_event) (void)hipEventDestroy(c->hist_event);

@@ -317,7 +317,9 @@ int pm_render_resampled(void *ptr, const pm_render_params *p, float *out_rgb, pm
 
 /* pm_render's loop with pm_final_gather_pass in the place of the primary
  * records' gather, and the resolve in the place of the final. The buckets are
- * built for the kNN estimator, whatever params->estimator says. */
+ * built for the kNN estimator, whatever params->estimator says. Under
+ * pm_set_caustic_map each pass also builds the caustic map and gathers it at
+ * the primary records; the resolve then adds Lc. */
 int pm_render_final_gather(void *ptr, const pm_render_params *p, int n_gather, float *out_rgb, pm_stats *st) {
     if (!p) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_render_final_gather: null params");
     if (n_gather < 1 || n_gather > PM_FG_MAX)
@@ -347,6 +349,11 @@ int pm_render_final_gather(void *ptr, const pm_render_params *p, int n_gather, f
         /* every chunk of the pass; a stage that is not timed (pm_set_stage_timing) adds nothing */
         t_gather += std::max(0.0, timer_ms(c, "fgrays", (size_t)c->fg_chunks)) +
                     std::max(0.0, timer_ms(c, "fgather", (size_t)c->fg_chunks));
+        if (c->caustic_map) { /* the caustic map of this pass's photons, looked up at the eye hits */
+            if ((rc = pm_build_caustic_map(c, s))) return rc;
+            if ((rc = pm_caustic_gather(c, &q, pass, s))) return rc;
+            t_gather += std::max(0.0, timer_ms(c, "caustic", 2)); /* the build and the gather */
+        }
     }
     const double emitted = (double)q.paths_per_pass * q.passes;
     const int64_t nout = c->pinhole ? (int64_t)c->W * c->H : c->nrec;

@@ -46,6 +46,7 @@ int ensure_records(Ctx *c) {
     }
     c->nrec = n;
     c->fg_passes = 0; /* new primary records: the final-gather sums are another record set's */
+    c->cg_passes = 0; /* ... and so are the caustic gather's */
     c->tiles.invalidate();
     c->grid_plan.invalidate();
     return PM_OK;
@@ -248,6 +249,7 @@ int pm_eye_resample(void *ptr, const pm_render_params *p, int pass, void *stream
     timer_end(c, "eye", s);
     ++c->eye_samples;
     c->fg_passes = 0;
+    c->cg_passes = 0;
     c->tiles.invalidate(); /* the flags moved with the hits */
     c->grid_plan.invalidate();
     if (c->view_active && (rc = build_view(c, s))) return rc;
@@ -344,6 +346,14 @@ int pm_trace_photons(void *ptr, const pm_render_params *p, int pass, int64_t pat
     if (path_count < 0 || path_begin < slot_path_base) FAIL(c, PM_ERR_INVALID, "bad path range");
     if ((uint64_t)(path_begin + path_count) * (uint64_t)p->max_photon_count > 0xffffffffull)
         FAIL(c, PM_ERR_INVALID, "photon slot index exceeds 32 bits (reference pm_index is a uint)");
+    if (c->caustic_map) { /* pm_set_caustic_map: what a marked trace refuses */
+        if (p->gather_structure == PM_GATHER_KDTREE)
+            FAIL(c, PM_ERR_INVALID, "pm_trace_photons: the caustic map is on and gather_structure is PM_GATHER_KDTREE; the "
+                                    "kd-tree build owns the photons' bits word (PM_GATHER_GRID)");
+        if (c->albedo())
+            FAIL(c, PM_ERR_INVALID, "pm_trace_photons: the caustic map is on and the scene has a textured or physically "
+                                    "specular material (final gathering takes neither)");
+    }
     const int64_t mpc = p->max_photon_count;
     const int64_t end_slot = (path_begin + path_count - slot_path_base) * mpc;
     hipStream_t s = pick(c, stream);
@@ -371,6 +381,7 @@ int pm_trace_photons(void *ptr, const pm_render_params *p, int pass, int64_t pat
     sh.path_count = path_count; sh.mpc = (int)mpc; sh.slots_aligned = ((uintptr_t)T.slots & 15u) == 0u;
     sh.mode = scene_mode(c->S); sh.wide = c->S.wide; sh.stack_depth = c->S.stack_depth; sh.lds_bytes = c->S.lds_bytes;
     sh.pool_stack = c->pool_stack; sh.trace_pool = c->trace_pool; sh.trace_hold = c->trace_hold;
+    sh.mark = c->caustic_map;
     if (c->S.wide && hipDeviceGetAttribute(&sh.cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) sh.cus = 0;
     const TracePlan plan = plan_trace(sh, trace_waves_per_cu);
     T.hold = plan.hold; T.pool_stack = plan.lstk; T.pool_paths = plan.pool_paths;
@@ -382,6 +393,7 @@ int pm_trace_photons(void *ptr, const pm_render_params *p, int pass, int64_t pat
     T.pass = pass; T.mpc = (int)mpc; T.max_spec = p->max_specular_depth; T.light_index = p->light_source_index;
     T.eps = p->scene_epsilon; T.seed = p->rng_seed;
     T.light_cdf = c->d_light_cdf.as<float>();
+    T.mark = c->caustic_map ? 1 : 0;
     T.counters = c->d_counters.as<unsigned long long>() + 4;
     T.prof = c->d_counters.as<unsigned long long>() + 8;
     if (c->counting) HIPCHK(c, hipMemsetAsync(T.counters, 0, 32, s));
@@ -548,7 +560,8 @@ static int gather_attach_hist(Ctx *c, const pm_render_params *p, GatherParams &G
     return PM_OK;
 }
 
-static int gather_knn_setup(Ctx *c, const pm_render_params *p, GatherParams &G) {
+/* caustic: the scalar stream's pairs and handed-back tiles of the caustic map (G's map is pm_build_caustic_map's) */
+static int gather_knn_setup(Ctx *c, const pm_render_params *p, GatherParams &G, bool caustic = false) {
     G.knn_k = p->knn_lookup;
     G.knn_r2 = p->initial_radius2; /* pbrt's maxDistSquared: the buckets cover it */
     /* every term (kernel <= 3/pi < 1) is <= alpha_max / r_k^2: <= 2^22 of
@@ -559,17 +572,21 @@ static int gather_knn_setup(Ctx *c, const pm_render_params *p, GatherParams &G) 
     G.knn_fx = (float)(std::ldexp(1.0, 24) / std::max(amax, 1e-30));
     G.slots = c->d_slots.as<pm_photon>();
     if (c->knn_ss && !c->counting && c->gather_kernel == PM_GK_TILE) {
-        const int64_t nph = (int64_t)(c->d_pha.bytes / 16), pairs = (nph + 1) / 2 + 16;
+        DevBuf &pk = caustic ? c->d_cg_knnpk : c->d_knnpk, &ovf = caustic ? c->d_cg_knnovf : c->d_knnovf;
+        uint64_t &pack_gen = caustic ? c->cg_pack_gen : c->knn_pack_gen;
+        void *&pack_ptr = caustic ? c->cg_pack_ptr : c->knn_pack_ptr;
+        const uint64_t gen = caustic ? c->cg_gen : c->map_gen;
+        const int64_t nph = (int64_t)((caustic ? c->d_cg_pha : c->d_pha).bytes / 16), pairs = (nph + 1) / 2 + 16;
         const int64_t ntiles = (G.rec_end - G.rec_begin + 63) / 64;
-        HIPCHK(c, c->d_knnpk.ensure((size_t)pairs * 80));
-        HIPCHK(c, c->d_knnovf.ensure((size_t)(ntiles + KNN_OVF_HDR) * 4));
-        G.knn_pk_p = c->d_knnpk.as<float4>();
+        HIPCHK(c, pk.ensure((size_t)pairs * 80));
+        HIPCHK(c, ovf.ensure((size_t)(ntiles + KNN_OVF_HDR) * 4));
+        G.knn_pk_p = pk.as<float4>();
         G.knn_pk_q = G.knn_pk_p + 2 * pairs;
         G.knn_pk_pairs = pairs;
-        G.knn_pack = c->knn_pack_gen != c->map_gen || c->knn_pack_ptr != c->d_knnpk.p;
-        c->knn_pack_gen = c->map_gen;
-        c->knn_pack_ptr = c->d_knnpk.p;
-        G.knn_ovf_n = c->d_knnovf.as<uint32_t>();
+        G.knn_pack = pack_gen != gen || pack_ptr != pk.p;
+        pack_gen = gen;
+        pack_ptr = pk.p;
+        G.knn_ovf_n = ovf.as<uint32_t>();
         G.knn_ovf = G.knn_ovf_n + KNN_OVF_HDR;
     }
     return PM_OK;
@@ -1070,9 +1087,153 @@ int pm_final_gather_resolve(void *ptr, int64_t rec_begin, int64_t rec_count, voi
     R.P = recs(c); R.sum = c->d_fg_sum.as<float4>(); R.materials = c->S.materials;
     R.denom = (float)((int64_t)c->fg_n * c->fg_passes);
     R.rec_begin = rec_begin; R.rec_count = rec_count; R.out = (float *)d_out; R.raster = c->pinhole; R.W = c->W;
+    /* pm_set_caustic_map on and pm_caustic_gather run for every pass: Lc beside the direct light */
+    const bool caustic = c->caustic_map && c->cg_passes > 0;
+    if (caustic && (c->cg_passes != c->fg_passes || c->cg_nrec != c->nrec))
+        FAIL(c, PM_ERR_INVALID, "pm_final_gather_resolve: the caustic map is on and pm_caustic_gather ran for %d of the %d "
+                                "final-gather passes", c->cg_passes, c->fg_passes);
     timer_begin(c, "final", s);
-    HIPCHK(c, launch_fg_resolve(R, s));
+    if (caustic) HIPCHK(c, launch_fg_resolve_caustic(R, (float)c->cg_emitted, s));
+    else HIPCHK(c, launch_fg_resolve(R, s));
     timer_end(c, "final", s);
+    return PM_OK;
+}
+
+/* ------------------------------------------------------- the caustic map */
+int pm_set_caustic_map(void *ptr, int on) {
+    GETCTX(ptr);
+    if (on && c->committed && c->albedo())
+        FAIL(c, PM_ERR_INVALID, "pm_set_caustic_map: the scene has a textured or physically specular material (final "
+                                "gathering takes neither)");
+    c->caustic_map = on != 0;
+    c->cg_built = false;
+    c->cg_passes = 0;
+    return PM_OK;
+}
+
+int pm_build_caustic_map(void *ptr, void *stream) {
+    GETCTX(ptr);
+    if (!c->caustic_map) FAIL(c, PM_ERR_INVALID, "pm_build_caustic_map: the caustic map is off (pm_set_caustic_map)");
+    if (c->map_kind != PM_GATHER_GRID || c->map_slots <= 0)
+        FAIL(c, PM_ERR_INVALID, "pm_build_caustic_map: no photon map built on the buckets (pm_build_photon_map first)");
+    if ((size_t)c->map_slots * sizeof(pm_photon) > c->d_slots.bytes)
+        FAIL(c, PM_ERR_INVALID, "pm_build_caustic_map: the slot buffer no longer holds the map's %lld slots", (long long)c->map_slots);
+    hipStream_t s = pick(c, stream);
+    int rc;
+    if ((rc = materialize_slots(c, s))) return rc; /* the count reads every slot's bits */
+    const GridDesc g = c->grid; /* the full map's grid: the kNN estimator's for the build's initial_radius2 */
+    const size_t n = (size_t)c->map_slots, nc = (size_t)g.ncells + 1;
+    const bool fresh_count = !(c->d_cg_count.p && nc * 4 <= c->d_cg_count.bytes);
+    HIPCHK(c, c->d_cg_count.ensure_slack(nc * 4));
+    HIPCHK(c, c->d_cg_cell_start.ensure_slack(nc * 4));
+    HIPCHK(c, c->d_cg_scratch.ensure_slack(caustic_scratch_words((int64_t)n, g.ncells) * 4));
+    HIPCHK(c, c->d_cg_pha.ensure_slack(n * 16));
+    HIPCHK(c, c->d_cg_phb.ensure_slack(n * 32));
+    /* a new counter buffer starts zeroed; afterwards every build's scan leaves it so */
+    if (fresh_count) HIPCHK(c, hipMemsetAsync(c->d_cg_count.p, 0, c->d_cg_count.bytes, s));
+    timer_begin(c, "caustic", s);
+    HIPCHK(c, launch_caustic_build(c->d_slots.as<pm_photon>(), (int64_t)n, g, c->d_cg_count.as<uint32_t>(),
+                                   c->d_cg_cell_start.as<uint32_t>(), c->d_cg_scratch.as<uint32_t>(),
+                                   c->d_cg_pha.as<float4>(), c->d_cg_phb.as<float4>(), s));
+    timer_end(c, "caustic", s);
+    c->cg_grid = g;
+    c->cg_slots = (int64_t)n;
+    c->cg_built = true;
+    ++c->cg_gen;
+    return PM_OK;
+}
+
+int pm_caustic_gather(void *ptr, const pm_render_params *p, int pass, void *stream) {
+    if (!p) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_caustic_gather: null params");
+    if (pass < 0) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_caustic_gather: pass %d is negative", pass);
+    GETCTX(ptr);
+    int rc;
+    if ((rc = fg_validate(c, p, __func__))) return rc;
+    if (!c->caustic_map) FAIL(c, PM_ERR_INVALID, "pm_caustic_gather: the caustic map is off (pm_set_caustic_map)");
+    if (!c->cg_built) FAIL(c, PM_ERR_INVALID, "pm_caustic_gather: no caustic map built (pm_build_caustic_map)");
+    if (!same_grid(c->cg_grid, pm::make_grid(c->bbox_lo, c->bbox_hi, PM_ESTIMATOR_KNN, c->cell_span, p->initial_radius2)))
+        FAIL(c, PM_ERR_INVALID, "pm_caustic_gather: the caustic map was not built on PM_ESTIMATOR_KNN buckets with this initial_radius2");
+    if (pass > 0 && (c->cg_passes < 1 || c->cg_nrec != c->nrec))
+        FAIL(c, PM_ERR_INVALID, "pm_caustic_gather: pass %d continues no pass 0 over these records", pass);
+    hipStream_t s = pick(c, stream);
+    /* a GatherParams of its own, as pm_final_gather_pass makes for its secondary records: the primary records
+     * against the caustic map, every tile, no view */
+    pm_render_params q = *p;
+    q.estimator = PM_ESTIMATOR_KNN;
+    GatherParams G = gather_params(c, &q);
+    G.view_rank = nullptr; G.view_list = nullptr;
+    G.grid = c->cg_grid;
+    G.cell_start = c->d_cg_cell_start.as<uint32_t>();
+    G.ph_a = c->d_cg_pha.as<float4>(); G.ph_b = c->d_cg_phb.as<float4>();
+    G.rec_begin = 0; G.rec_end = c->nrec;
+    if (pass == 0) { /* pass 0 starts the sums: flux 0, photon_count 0 */
+        G.fresh = 1;
+        G.r2init = p->initial_radius2;
+        c->cg_passes = 0; c->cg_nrec = c->nrec; c->cg_emitted = 0;
+    } else if ((rc = materialize_reset(c, s))) return rc;
+    timer_begin(c, "caustic", s);
+    if ((rc = gather_knn_setup(c, &q, G, true))) return rc;
+    HIPCHK(c, launch_gather_knn(G, 0, s));
+    timer_end(c, "caustic", s);
+    c->rec_fresh = false;
+    c->rec_estimator = PM_ESTIMATOR_KNN; /* the records hold kNN sums */
+    c->grid_plan.invalidate();           /* r_k^2 replaced the radii */
+    ++c->cg_passes;
+    c->cg_emitted += (double)p->paths_per_pass;
+    return PM_OK;
+}
+
+int64_t pm_caustic_map_count(void *ptr) {
+    Ctx *c = (Ctx *)ptr;
+    if (!c || c->group || !c->cg_built) return -1;
+    (void)hipSetDevice(c->device);
+    uint32_t nv = 0;
+    if (hipStreamSynchronize(c->stream) != hipSuccess ||
+        hipMemcpy(&nv, c->d_cg_cell_start.as<uint32_t>() + c->cg_grid.ncells, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    return (int64_t)nv;
+}
+
+int pm_download_caustic_slots(void *ptr, uint32_t *out, int64_t n) {
+    GETCTX(ptr);
+    if (!out) FAIL(c, PM_ERR_INVALID, "pm_download_caustic_slots: null pointer");
+    if (!c->cg_built) FAIL(c, PM_ERR_INVALID, "pm_download_caustic_slots: no caustic map built (pm_build_caustic_map)");
+    const int64_t have = pm_caustic_map_count(c);
+    if (n < 0 || n > have)
+        FAIL(c, PM_ERR_INVALID, "pm_download_caustic_slots: %lld indices asked, %lld held", (long long)n, (long long)have);
+    std::vector<float4> b((size_t)n * 2);
+    HIPCHK(c, hipMemcpy(b.data(), c->d_cg_phb.p, (size_t)n * 32, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) std::memcpy(&out[i], &b[2 * (size_t)i + 1].y, 4);
+    return PM_OK;
+}
+
+int pm_download_caustic_cell_start(void *ptr, uint32_t *out, int64_t n) {
+    GETCTX(ptr);
+    if (!out) FAIL(c, PM_ERR_INVALID, "pm_download_caustic_cell_start: null pointer");
+    if (!c->cg_built) FAIL(c, PM_ERR_INVALID, "pm_download_caustic_cell_start: no caustic map built (pm_build_caustic_map)");
+    if (n < 0 || n > (int64_t)c->cg_grid.ncells + 1)
+        FAIL(c, PM_ERR_INVALID, "pm_download_caustic_cell_start: %lld words asked, %lld held", (long long)n, (long long)c->cg_grid.ncells + 1);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, c->d_cg_cell_start.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PM_OK;
+}
+
+int pm_download_caustic_radiance(void *ptr, float *out_rgb, int64_t n) {
+    GETCTX(ptr);
+    if (!out_rgb) FAIL(c, PM_ERR_INVALID, "pm_download_caustic_radiance: null pointer");
+    if (c->cg_passes < 1 || n < 0 || n > c->cg_nrec || c->cg_nrec != c->nrec)
+        FAIL(c, PM_ERR_INVALID, "pm_download_caustic_radiance: %lld radiances asked, %lld held (pm_caustic_gather)", (long long)n,
+             (long long)(c->cg_passes < 1 ? 0 : c->cg_nrec));
+    if (n == 0) return PM_OK;
+    DevBuf d;
+    HIPCHK(c, d.ensure((size_t)n * 3 * sizeof(float)));
+    FgResolveParams R{};
+    R.P = recs(c); R.materials = c->S.materials; R.rec_begin = 0; R.rec_count = n; R.out = d.as<float>();
+    hipError_t e = launch_caustic_radiance(R, (float)c->cg_emitted, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    d.release();
+    HIPCHK(c, e);
     return PM_OK;
 }
 

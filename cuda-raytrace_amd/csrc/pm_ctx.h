@@ -226,6 +226,21 @@ struct Ctx {
     int64_t fg_nrec = 0, fg_chunk = (int64_t)1 << 22;
     int fg_n = 0, fg_passes = 0;
     int64_t fg_chunks = 0; /* chunks (launches per stage timer) of the last pass */
+    /* the caustic map (pm_set_caustic_map): the bucket set pm_build_caustic_map
+     * fills from the marked slots on the grid cg_grid (built: cg_built), the
+     * kNN scalar stream's pairs and handed-back tiles over it (cg_gen bumped by
+     * every build, as map_gen) and the passes pm_caustic_gather has summed into
+     * the cg_nrec primary records */
+    bool caustic_map = false;
+    DevBuf d_cg_count, d_cg_cell_start, d_cg_scratch, d_cg_pha, d_cg_phb, d_cg_knnpk, d_cg_knnovf;
+    GridDesc cg_grid{};
+    bool cg_built = false;
+    int64_t cg_slots = 0;
+    uint64_t cg_gen = 0, cg_pack_gen = ~0ull;
+    void *cg_pack_ptr = nullptr;
+    int cg_passes = 0;
+    int64_t cg_nrec = 0;
+    double cg_emitted = 0; /* paths_per_pass of the gathers, times cg_passes: the emitted paths of Lc */
     int kd_stack = KD_STACK;       /* kd gather stack entries (env PM_KD_STACK, tests only) */
     bool trace_pool = true;         /* 4-wide scenes: the pooled trace kernel (env PM_TRACE_POOL=0: one path per lane) */
     bool trace_hold = true;         /* deposits written once per path where it costs no waves (env PM_TRACE_HOLD=0: per deposit) */

@@ -187,6 +187,11 @@ struct TraceParams {
      * scene's traversal mode and costs no LDS. Selects the ALL instantiations
      * of the trace kernels (launch_trace); the fixed-light ones never read it */
     const float *light_cdf;
+    /* pm_set_caustic_map: != 0 selects the MARK instantiations (launch_trace),
+     * which set bit 1 of pm_photon::bits on a deposit whose earlier hits were
+     * all specular; never with held deposits, a textured material or one of
+     * the physical specular model. The other kernels never read it */
+    int mark;
 };
 
 struct GatherParams {
@@ -362,6 +367,19 @@ size_t bucket_scratch_words(int64_t n_slots, uint32_t ncells);
 hipError_t launch_bucket_build(const pm_photon *slots, int64_t n, GridDesc g, uint32_t *count, uint32_t *cell_start,
                                uint32_t *scratch, float4 *ph_a, float4 *ph_b, bool counted, hipStream_t s,
                                int64_t key_np = 0, int mpc = 1);
+/* the caustic bucket map (pm_caustic.hip): launch_bucket_build over the slots
+ * with bit 1 of pm_photon::bits set alone, into a count / cell_start / ph_a /
+ * ph_b set of its own on grid g (ph_b keeps the slot index). count arrives
+ * zeroed and leaves zeroed; scratch holds caustic_scratch_words() uint32 */
+size_t caustic_scratch_words(int64_t n_slots, uint32_t ncells);
+hipError_t launch_caustic_build(const pm_photon *slots, int64_t n, GridDesc g, uint32_t *count, uint32_t *cell_start,
+                                uint32_t *scratch, float4 *ph_a, float4 *ph_b, hipStream_t s);
+/* launch_exclusive_scan that zeroes `in` as it reads it (the bucket build's scan) */
+hipError_t launch_exclusive_scan_clear(uint32_t *in, int64_t n, uint32_t *out, uint32_t *sums, hipStream_t s);
+/* the caustic radiance Lc of records [rec_begin, rec_begin + rec_count) (pm_api.h pm_caustic_gather), float3 in
+ * record order; and pm_final_gather_resolve with it: out = (dl + Lc) + Kd x (A / denom) */
+hipError_t launch_caustic_radiance(const FgResolveParams &p, float emitted, hipStream_t s);
+hipError_t launch_fg_resolve_caustic(const FgResolveParams &p, float emitted, hipStream_t s);
 /* gather: structure 0 grid, 1 kd; mode 0 fused PPM, 1 partial */
 hipError_t launch_gather(const GatherParams &p, int structure, int partial, int count, hipStream_t s);
 /* kNN estimator (pbrt LPhoton) over the photon buckets, fused record update */

@@ -105,7 +105,7 @@ static TraceFamily lane_family(int mode) {
 TracePlan plan_trace(const TraceShape &sh, const WavesPerCu &waves_per_cu) {
     constexpr int64_t block_waves = TRACE_BLOCK / 64;
     TracePlan pl;
-    pl.hold = sh.trace_hold ? 1 : 0;
+    pl.hold = sh.trace_hold && !sh.mark ? 1 : 0; /* marking stores per deposit: the mark bit is not carried through held_put */
     if (pl.hold && !sh.wide) { /* per-lane kernel: only when the held deposits' LDS costs no resident waves */
         const TraceFamily asked = sh.mode == MODE_INST ? TRACE_LANE_GLOBAL : lane_family(sh.mode);
         if (waves_per_cu(asked, true, lane_lds(sh, true)) < waves_per_cu(asked, false, lane_lds(sh, false))) pl.hold = 0;

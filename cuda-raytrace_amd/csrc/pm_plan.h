@@ -115,6 +115,7 @@ struct TraceShape {
     int pool_stack = 31;       /* the context's settings (env PM_POOL_STACK, PM_TRACE_POOL, PM_TRACE_HOLD) */
     bool trace_pool = true, trace_hold = true;
     int cus = 0;               /* compute units of the device; <= 0: unknown, taken as 256 */
+    bool mark = false;         /* pm_set_caustic_map: the launch marks caustic photons (the MARK instantiations) */
 };
 
 /* resident waves per CU of `family`'s HOLD (hold) or plain instantiation at
@@ -150,7 +151,10 @@ struct TracePlan {
  *    (hold_launch): the fused keys are then slot-major and not lazily zeroed, as for a held launch;
  *  - a per-lane MODE_INST launch asks the occupancy of TRACE_LANE_GLOBAL;
  *  - a wide scene launched per lane (MODE_INST, or trace_pool off) still gets the pooled geometry's spill_stride,
- *    which is not its grid's thread count: the per-lane kernel has no spill. */
+ *    which is not its grid's thread count: the per-lane kernel has no spill.
+ * Marking (TraceShape::mark): the MARK instantiations store per deposit, so hold and hold_launch are 0 whatever
+ * trace_hold says and no HOLD occupancy is asked; the pooled round is sized by the unmarked kernel's waves (the
+ * occupancy attribute pins both to the same count). Everything else is the plan of trace_hold = 0. */
 TracePlan plan_trace(const TraceShape &sh, const WavesPerCu &waves_per_cu);
 
 } // namespace pm

@@ -37,6 +37,15 @@ PMD void store_photon(pm_photon *dst, v3 p, v3 a, v3 wi) {
     q[3] = make_float2(a.z, wi.x);
     q[4] = make_float2(wi.y, wi.z);
 }
+/* the MARK kernels' store: bits = valid | caustic << 1 (pm_api.h pm_set_caustic_map) */
+PMD void store_photon_marked(pm_photon *dst, uint32_t bits, v3 p, v3 a, v3 wi) {
+    float2 *q = reinterpret_cast<float2 *>(dst);
+    q[0] = make_float2(__uint_as_float(bits), p.x);
+    q[1] = make_float2(p.y, p.z);
+    q[2] = make_float2(a.x, a.y);
+    q[3] = make_float2(a.z, wi.x);
+    q[4] = make_float2(wi.y, wi.z);
+}
 
 /* Photon paths (photontracing.cu:80-185) split into ray steps so a block can
  * compact its live paths between steps. Per-path state (12 words) lives in
@@ -53,6 +62,7 @@ struct PathState {
      * atomic right after issuing it */
     uint32_t pslot;  /* slot of the pending rank, PSLOT_NONE if none */
     uint32_t prank;
+    uint32_t diff;   /* MARK kernels only: a diffuse hit has happened (spec > 0 && nI == 1 also holds for L D S D) */
 };
 constexpr uint32_t PSLOT_NONE = 0xffffffffu;
 /* where the fused bucket count keeps deposit k of path pid: plane-major
@@ -211,17 +221,17 @@ PMD bool emit_path(const TraceParams &P, const SceneDev &S, const uint32_t *perm
 
 /* one ray of a path: trace, then specular continuation or diffuse deposit +
  * Lambert bounce (photontracing.cu:119-183); false when the path ends */
-template <int HOLD, bool INST = false, bool TEX = false, bool SPEC = false>
+template <int HOLD, bool INST = false, bool TEX = false, bool SPEC = false, bool MARK = false>
 PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, const Hit &h, TProf &prof, Held &held);
 
-template <int MODE, int HOLD, bool TEX, bool SPEC, class C>
+template <int MODE, int HOLD, bool TEX, bool SPEC, bool MARK, class C>
 PMD bool path_step(const TraceParams &P, const SceneDev &S, int *stack, PathState &st, C &cen, TProf &prof,
                    Held &held) {
     Hit h;
     const bool hit = traverse<false, MODE>(S, st.ray, h, stack, TRACE_BLOCK, cen);
     prof.mark(1);
     if (!hit) return false;
-    return path_shade<HOLD, MODE == MODE_INST, TEX, SPEC>(P, S, st, h, prof, held);
+    return path_shade<HOLD, MODE == MODE_INST, TEX, SPEC, MARK>(P, S, st, h, prof, held);
 }
 
 /* the hit of a path's ray: specular continuation, or diffuse deposit +
@@ -232,9 +242,15 @@ PMD bool path_step(const TraceParams &P, const SceneDev &S, int *stack, PathStat
  * SPEC (a scene with a material of the physical specular model, always with
  * TEX): such a material's step picks its lobe with a Philox draw of the
  * bounce stream's key at word 2 = the path's specular count (>= 1; the
- * Lambert bounce has 0 there) and scales alpha by the lobe's weight */
-template <int HOLD, bool INST, bool TEX, bool SPEC>
+ * Lambert bounce has 0 there) and scales alpha by the lobe's weight.
+ * MARK (pm_set_caustic_map; never with HOLD, TEX or SPEC): a deposit made
+ * before the path's first diffuse hit — at least one hit before it (nI >= 1)
+ * and every one of them specular — is a caustic photon and gets bit 1 of its
+ * bits word; st.diff carries "a diffuse hit has happened". Everything else
+ * the kernel writes is the unmarked kernel's */
+template <int HOLD, bool INST, bool TEX, bool SPEC, bool MARK>
 PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, const Hit &h, TProf &prof, Held &held) {
+    static_assert(!MARK || (!HOLD && !TEX && !SPEC), "the MARK instantiations store per deposit in plain scenes");
     const uint32_t mpc = (uint32_t)P.mpc;
     Geo g = shade<INST>(S, st.ray, h);
     v3 hit_point = st.ray.o + h.t * st.ray.d;
@@ -275,7 +291,8 @@ PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, cons
     v3 wo = -st.ray.d;
     if (st.nI >= 1) {
         const size_t slot = (size_t)(st.pid - (uint64_t)P.slot_path_base) * mpc + (st.nI - 1);
-        if (!HOLD) store_photon(P.slots + slot, hit_point, st.alpha, wo);
+        if (MARK) store_photon_marked(P.slots + slot, st.diff ? 1u : 3u, hit_point, st.alpha, wo);
+        else if (!HOLD) store_photon(P.slots + slot, hit_point, st.alpha, wo);
         st.stored = st.nI;
         uint32_t key = 0xffffffffu, rank = 0u;
         if (P.bucket) { /* fused counting pass of the bucket build (pm_bucket.hip k_bucket_count) */
@@ -295,6 +312,7 @@ PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, cons
         /* HOLD: the returned rank is first read at the path's end */
         if (HOLD) held_put(held, P, slot, st.nI - 1, hit_point, st.alpha, wo, key, rank);
     }
+    if (MARK) st.diff = 1u;
     prof.mark(4);
     if (st.nI >= mpc) return false;
     const uint32_t pm_index = st.pid * mpc;
@@ -342,7 +360,7 @@ PMD void finish_path(const TraceParams &P, PathState &st, const Held *held = nul
  * §5) and removed. HOLD: deposits held in LDS and written per path.
  * COUNT: census [rays traced, BVH nodes entered, primitive tests, photons
  * deposited], one atomic per wave (counting launches only, never timed). */
-template <int COUNT, int MODE, int HOLD, int ALL, bool TEX, bool SPEC>
+template <int COUNT, int MODE, int HOLD, int ALL, bool TEX, bool SPEC, bool MARK = false>
 PMD void trace_lane_body(const TraceParams &P) {
     extern __shared__ __attribute__((aligned(16))) int stk[];
     __shared__ uint32_t perm[28];
@@ -364,10 +382,11 @@ PMD void trace_lane_body(const TraceParams &P) {
     if (path < P.path_count) {
         if (HOLD) held_clear(held);
         bool alive = emit_path<ALL>(P, S, perm, (uint32_t)(P.path_begin + path), st);
+        if (MARK) st.diff = 0u;
         prof.mark(0);
         while (alive) {
             ++rays;
-            alive = path_step<MODE, HOLD, TEX, SPEC>(P, S, stack, st, cen, prof, held);
+            alive = path_step<MODE, HOLD, TEX, SPEC, MARK>(P, S, stack, st, cen, prof, held);
             prof.mark(2);
         }
         if (COUNT) deposits += st.stored;
@@ -385,6 +404,9 @@ template <int COUNT, int MODE, int HOLD, int ALL = 0, bool TEX = false>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane(TraceParams P) { trace_lane_body<COUNT, MODE, HOLD, ALL, TEX, false>(P); }
 template <int COUNT, int MODE, int HOLD, int ALL>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane_spec(TraceParams P) { trace_lane_body<COUNT, MODE, HOLD, ALL, true, true>(P); }
+/* pm_set_caustic_map: k_trace_lane<COUNT, MODE, 0, ALL> that marks caustic photons */
+template <int COUNT, int MODE, int ALL>
+__global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane_mark(TraceParams P) { trace_lane_body<COUNT, MODE, 0, ALL, false, false, true>(P); }
 
 /* Pooled photon tracer for scenes traversed from HBM with the 4-wide BVH
  * (C3). A ray's traversal lives across iterations of the wave's loop
@@ -405,8 +427,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane_spec(TraceParams P) 
 constexpr int POOL_STEPS = PM_POOL_STEPS, POOL_SHADE_MIN = PM_POOL_SHADE_MIN;
 enum { PHASE_DEAD = 0, PHASE_TRAV = 1, PHASE_SHADE = 2 };
 
-/* W8: the 8-wide tree (S.wide == 3, TravState8); ALL: emit_path's; TEX, SPEC: path_shade's */
-template <int COUNT, int HOLD, int W8, int ALL, bool TEX, bool SPEC>
+/* W8: the 8-wide tree (S.wide == 3, TravState8); ALL: emit_path's; TEX, SPEC, MARK: path_shade's */
+template <int COUNT, int HOLD, int W8, int ALL, bool TEX, bool SPEC, bool MARK = false>
 /* 5 waves/SIMD: 96 VGPRs (102 unconstrained -> 4 waves), no scratch; with
  * the LDS stacks capped at 31 entries (PM_POOL_STACK, the rest spilled) five
  * 256-thread blocks fit a CU. C3 trace (same box): 4.59-4.61 ms at 4 waves,
@@ -459,7 +481,7 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
         if (travm == 0ull || waiting >= POOL_SHADE_MIN) {
             if (phase == PHASE_SHADE) {
                 ++rays;
-                const bool alive = tr.best.ref != 0xffffffffu && path_shade<HOLD, false, TEX, SPEC>(P, S, st, tr.best, prof, held);
+                const bool alive = tr.best.ref != 0xffffffffu && path_shade<HOLD, false, TEX, SPEC, MARK>(P, S, st, tr.best, prof, held);
                 if (alive) {
                     trav_begin(st.ray, tr);
                     phase = PHASE_TRAV;
@@ -474,7 +496,9 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
                 const int64_t mine = cursor + __popcll(dm & ((1ull << lane) - 1ull));
                 if (phase == PHASE_DEAD && mine < wend) {
                     if (HOLD) held_clear(held);
-                    if (emit_path<ALL>(P, S, perm, (uint32_t)(P.path_begin + mine), st)) {
+                    const bool emitted = emit_path<ALL>(P, S, perm, (uint32_t)(P.path_begin + mine), st);
+                    if (MARK) st.diff = 0u;
+                    if (emitted) {
                         trav_begin(st.ray, tr);
                         phase = PHASE_TRAV;
                     } else {
@@ -506,6 +530,12 @@ void k_trace_pool8(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, TEX, fa
 template <int COUNT, int HOLD, int ALL>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
 void k_trace_pool8_spec(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, true, true>(P); }
+/* pm_set_caustic_map: k_trace_pool<COUNT, 0, ALL> / k_trace_pool8<COUNT, 0, ALL> that mark caustic photons */
+template <int COUNT, int ALL>
+__global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool_mark(TraceParams P) { trace_pool_body<COUNT, 0, 0, ALL, false, false, true>(P); }
+template <int COUNT, int ALL>
+__global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
+void k_trace_pool8_mark(TraceParams P) { trace_pool_body<COUNT, 0, 1, ALL, false, false, true>(P); }
 
 /* resident waves per CU of a trace kernel family at `lds` bytes of dynamic
  * LDS (0 if unknown): the occupancy plan_trace (pm_plan.h) asks for. The
@@ -533,19 +563,24 @@ int trace_waves_per_cu(TraceFamily family, bool hold, size_t lds) {
 }
 
 /* MAT: which instantiations a scene runs: 0 = the plain ones, 1 = TEX (a
- * textured material), 2 = SPEC (a material of the physical specular model) */
+ * textured material), 2 = SPEC (a material of the physical specular model),
+ * 3 = MARK (a plain scene under pm_set_caustic_map; HOLD is 0 by the plan,
+ * so the HOLD = 1 arms below name the same kernel and never launch) */
 template <int COUNT, int MODE, int HOLD, int ALL, int MAT>
 static auto lane_kernel() {
-    if constexpr (MAT == 2) return &k_trace_lane_spec<COUNT, MODE, HOLD, ALL>;
+    if constexpr (MAT == 3) return &k_trace_lane_mark<COUNT, MODE, ALL>;
+    else if constexpr (MAT == 2) return &k_trace_lane_spec<COUNT, MODE, HOLD, ALL>;
     else return &k_trace_lane<COUNT, MODE, HOLD, ALL, MAT == 1>;
 }
 template <int COUNT, int HOLD, int W8, int ALL, int MAT>
 static auto pool_kernel() {
     if constexpr (W8 != 0) {
-        if constexpr (MAT == 2) return &k_trace_pool8_spec<COUNT, HOLD, ALL>;
+        if constexpr (MAT == 3) return &k_trace_pool8_mark<COUNT, ALL>;
+        else if constexpr (MAT == 2) return &k_trace_pool8_spec<COUNT, HOLD, ALL>;
         else return &k_trace_pool8<COUNT, HOLD, ALL, MAT == 1>;
     } else {
-        if constexpr (MAT == 2) return &k_trace_pool_spec<COUNT, HOLD, ALL>;
+        if constexpr (MAT == 3) return &k_trace_pool_mark<COUNT, ALL>;
+        else if constexpr (MAT == 2) return &k_trace_pool_spec<COUNT, HOLD, ALL>;
         else return &k_trace_pool<COUNT, HOLD, ALL, MAT == 1>;
     }
 }
@@ -617,6 +652,8 @@ static hipError_t launch_trace_mat(const TraceParams &p, const TracePlan &pl, in
  * before either existed */
 hipError_t launch_trace(const TraceParams &p, const TracePlan &pl, int count, hipStream_t s) {
     if (p.path_count <= 0) return hipSuccess;
+    if (p.mark) /* the MARK instantiations: plain scenes, deposits stored one by one (plan_trace under TraceShape::mark) */
+        return p.S.mat_spec || p.S.tex_recs || pl.hold_launch || p.hold ? hipErrorInvalidValue : launch_trace_mat<3>(p, pl, count, s);
     if (p.S.mat_spec) return p.S.mat_tex ? launch_trace_mat<2>(p, pl, count, s) : hipErrorInvalidValue;
     return p.S.tex_recs ? launch_trace_mat<1>(p, pl, count, s) : launch_trace_mat<0>(p, pl, count, s);
 }

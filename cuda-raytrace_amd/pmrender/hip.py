@@ -75,6 +75,13 @@ def load_library(path=None):
         "pm_render_final_gather": (c_int, [vp, ctypes.POINTER(RenderParams), c_int, P_f, ctypes.POINTER(Stats)]),
         "pm_final_gather_rays": (c_int, [vp, ctypes.POINTER(RenderParams), c_int, c_int, i64, i64, P_f]),
         "pm_download_gather_sum": (c_int, [vp, P_f, i64]),
+        "pm_set_caustic_map": (c_int, [vp, c_int]),
+        "pm_build_caustic_map": (c_int, [vp, vp]),
+        "pm_caustic_gather": (c_int, [vp, ctypes.POINTER(RenderParams), c_int, vp]),
+        "pm_caustic_map_count": (i64, [vp]),
+        "pm_download_caustic_slots": (c_int, [vp, ctypes.POINTER(ctypes.c_uint32), i64]),
+        "pm_download_caustic_cell_start": (c_int, [vp, ctypes.POINTER(ctypes.c_uint32), i64]),
+        "pm_download_caustic_radiance": (c_int, [vp, P_f, i64]),
         "pm_film_filter_table": (c_int, [ctypes.POINTER(Filter), P_f]),
         "pm_commit": (c_int, [vp]),
         "pm_render": (c_int, [vp, ctypes.POINTER(RenderParams), P_f, ctypes.POINTER(Stats)]),
@@ -524,6 +531,45 @@ class Context:
         n = self.num_records() if n is None else int(n)
         out = np.zeros((n, 3), np.float32)
         self._chk(self.lib.pm_download_gather_sum(self.h, fptr(out), n))
+        return out
+
+    # ---- the caustic map of final gathering (pm_api.h pm_set_caustic_map) ----
+    def set_caustic_map(self, on=True):
+        """pm_set_caustic_map: trace_photons marks caustic photons (bit 1 of a slot's bits), and
+        render_final_gather looks a map of them up at the eye hits. Off by default."""
+        self._chk(self.lib.pm_set_caustic_map(self.h, int(bool(on))))
+
+    def build_caustic_map(self, stream=None):
+        """pm_build_caustic_map: the marked slots into a bucket set of their own (after build_photon_map)."""
+        self._chk(self.lib.pm_build_caustic_map(self.h, stream))
+
+    def caustic_gather(self, params, pass_=0, stream=None):
+        """pm_caustic_gather: the kNN gather over the primary records against the caustic map."""
+        self._chk(self.lib.pm_caustic_gather(self.h, ctypes.byref(params), int(pass_), stream))
+
+    def caustic_map_count(self):
+        n = int(self.lib.pm_caustic_map_count(self.h))
+        if n < 0:
+            raise PMError(1, "pm_caustic_map_count: no caustic map built")
+        return n
+
+    def caustic_slots(self):
+        """The slot indices of the caustic map's photons in map order (pm_download_caustic_slots)."""
+        out = np.zeros(self.caustic_map_count(), np.uint32)
+        self._chk(self.lib.pm_download_caustic_slots(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(out)))
+        return out
+
+    def caustic_cell_start(self):
+        """cell_start of the caustic map: cells + 1 words, the last one its photon count."""
+        out = np.zeros(self.map_info()["cells"] + 1, np.uint32)
+        self._chk(self.lib.pm_download_caustic_cell_start(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(out)))
+        return out
+
+    def caustic_radiance(self, n=None):
+        """Lc of the first n primary records, (n, 3) (pm_download_caustic_radiance)."""
+        n = self.num_records() if n is None else int(n)
+        out = np.zeros((n, 3), np.float32)
+        self._chk(self.lib.pm_download_caustic_radiance(self.h, fptr(out), n))
         return out
 
     def final_image(self, emitted):

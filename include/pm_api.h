@@ -535,7 +535,8 @@ int pm_render_resampled(void *ctx, const pm_render_params *params, float *out_rg
  * tiles, at most 2^22 of them at a time (env PM_FG_CHUNK, for tests); the
  * result does not depend on the chunk. The primary records, the tile list,
  * the record view and the estimator the records are read under stay as they
- * were.
+ * were (pm_caustic_gather, below, is the one final-gather call that writes the
+ * primary records).
  * PM_ERR_INVALID, with the reason in the message: null params, n_gather
  * outside 1..256, pass < 0 (these before the context is checked); a
  * multi-device context; gather_structure != PM_GATHER_GRID; no eye pass yet;
@@ -559,6 +560,68 @@ int pm_render_final_gather(void *ctx, const pm_render_params *params, int n_gath
 int pm_final_gather_rays(void *ctx, const pm_render_params *params, int n_gather, int pass, int64_t first,
                          int64_t count, float *rays6);
 int pm_download_gather_sum(void *ctx, float *out_rgb, int64_t n);
+
+/* ---- final gathering: the caustic map, looked up directly at the eye hit
+ * The gather rays leave the emitted term out, so light -> specular chain ->
+ * diffuse eye hit (L S+ D E) is in no term of dl + Kd x mean(Li). pbrt-v2's
+ * photon integrator adds it from a map of its own: a kNN estimate at the eye
+ * hit over the caustic photons.
+ *
+ * A deposit is a caustic photon when its path had at least one hit before it
+ * and every earlier hit was specular (pbrt-v2's specularPath &&
+ * nIntersections > 1). The slot index does not tell: slot k * mpc + 0 also
+ * holds the second diffuse hit of an L D D path. Only the trace knows.
+ *
+ * pm_set_caustic_map(on != 0): off is the default and leaves every call as it
+ * is without this section. On:
+ *   trace    pm_trace_photons sets bit 1 of pm_photon::bits on each caustic
+ *            photon; bit 0 stays the valid bit. Every other word it writes —
+ *            slots, fused keys, ranks up to their order inside a cell, bucket
+ *            counts — is the unmarked trace's, bit for bit.
+ *   map      pm_build_caustic_map, after pm_build_photon_map on the buckets:
+ *            a bucket set of its own over the slots with bit 1 set, on the
+ *            built map's grid, each entry keeping its slot index.
+ *   lookup   pm_caustic_gather(pass): the kNN gather of PM_ESTIMATOR_KNN
+ *            (knn_lookup, initial_radius2) over the primary records against
+ *            the caustic map. The records' flux, radius2 and photon_count are
+ *            written as that estimator writes them, flux summed over the
+ *            passes; pass == 0 starts from flux 0 and the pass count C from 0,
+ *            every call adds 1 to C. This changes what final gathering leaves
+ *            alone: with the switch off the primary records' flux, radius2 and
+ *            photon_count stay as they were; with it on they are the caustic
+ *            gather's, and the records read as PM_ESTIMATOR_KNN's afterwards.
+ *   radiance Lc_r = pm_final's kNN form less dl_r with emitted =
+ *            (float)(C x paths_per_pass): (flux_r * (1 / emitted)) * (Kd_r *
+ *            (1 / pi)) per channel in fp32, the reciprocal correctly rounded,
+ *            Kd_r as in the resolve; 0 for an inactive record; not sanitised
+ *            on its own.
+ *   resolve  with C == P > 0 pm_final_gather_resolve writes out_r = (dl_r +
+ *            Lc_r) + Kd_r x (A_r / (float)(N P)), fp32 in the order written,
+ *            one IEEE division per channel, sanitised as before. C == 0 writes
+ *            the line above without Lc_r; any other C is refused.
+ *   render   pm_render_final_gather runs pm_build_caustic_map and
+ *            pm_caustic_gather after each pass's bucket build (stage
+ *            "caustic", added to ms_gather).
+ * Secondary hits keep the full map: L S+ D D E is indirect light.
+ * PM_ERR_INVALID, with the reason in the message: a multi-device context;
+ * pm_trace_photons under the switch with PM_GATHER_KDTREE (the kd-tree build
+ * owns the bits word) or in a scene with a textured material or one of
+ * pm_add_material_specular; pm_build_caustic_map with the switch off or no
+ * bucket map built; pm_caustic_gather with null params or pass < 0 (before the
+ * context is checked), the switch off, no caustic map, a map built for another
+ * estimator or initial_radius2, what pm_final_gather_pass refuses of the
+ * records and the scene, or pass > 0 that continues no pass 0. */
+int pm_set_caustic_map(void *ctx, int on);
+int pm_build_caustic_map(void *ctx, void *stream);
+int pm_caustic_gather(void *ctx, const pm_render_params *params, int pass, void *stream);
+/* Test hooks: the photons in the caustic map (-1: none built); the slot indices
+ * of its first n entries in map order; the first n words of its cell_start
+ * (cells + 1 words, the last one the count); Lc (rgb) of the first n primary
+ * records. */
+int64_t pm_caustic_map_count(void *ctx);
+int pm_download_caustic_slots(void *ctx, uint32_t *out, int64_t n);
+int pm_download_caustic_cell_start(void *ctx, uint32_t *out, int64_t n);
+int pm_download_caustic_radiance(void *ctx, float *out_rgb, int64_t n);
 
 /* ---- simple renderer (SimpleRenderer::render, simple_render/simplerender.cpp:18-103)
  * Direct light only: closest hit of each eye sample, one shadow-tested sample
