@@ -4,8 +4,9 @@
  * (and the g_stage the launches read), counters, scene / map info and the
  * diagnostic calls, pm_default_params and the small pure exports. The scene
  * calls and pm_commit are in pm_api_scene.cpp, the stages in
- * pm_api_stage.cpp, the whole renders in pm_api_render.cpp; pm_ctx.h holds
- * what the four share. Host code only; the kernels live in the .hip files
+ * pm_api_records.cpp, pm_api_photons.cpp, pm_api_gather.cpp and
+ * pm_api_fgather.cpp, the whole renders in pm_api_render.cpp; pm_ctx.h holds
+ * what they share. Host code only; the kernels live in the .hip files
  * (launchers in pm_kernels.h). No CPU fallback: every compute entry point
  * launches HIP kernels and fails with PM_ERR_HIP when the device is unusable.
  */
@@ -221,14 +222,14 @@ void pm_destroy(void *ptr) {
             (void)hipEventDestroy(t.a);
             (void)hipEventDestroy(t.b);
         }
-    DevBuf *bufs[] = {&c->d_scene, &c->d_rays, &c->d_rand2d, &c->d_pos, &c->d_nrm, &c->d_state, &c->d_n,
-                      &c->d_dl, &c->d_slots, &c->d_count, &c->d_scratch, &c->d_vflags, &c->d_vrank, &c->d_vlist, &c->d_vsums,
-                      &c->d_cell_start, &c->d_pha, &c->d_phb, &c->d_knnpk, &c->d_knnovf, &c->d_tile_times,
-                      &c->d_kd, &c->d_out, &c->d_counters, &c->d_hist, &c->d_spill, &c->d_light_tris, &c->d_light_cdf, &c->d_film_table, &c->d_img,
-                      &c->d_tex_recs, &c->d_texels, &c->d_mat_tex, &c->d_tri_uv, &c->d_rkd, &c->d_mat_spec,
-                      &c->d_fg_pos, &c->d_fg_nrm, &c->d_fg_state, &c->d_fg_n, &c->d_fg_dl, &c->d_fg_li, &c->d_fg_sum,
-                      &c->d_cg_count, &c->d_cg_cell_start, &c->d_cg_scratch, &c->d_cg_pha, &c->d_cg_phb, &c->d_cg_knnpk, &c->d_cg_knnovf};
+    /* the record sets, bucket maps and tile list release their own; these belong to no struct */
+    DevBuf *bufs[] = {&c->d_scene, &c->d_rays, &c->d_rand2d, &c->d_slots, &c->d_vflags, &c->d_vrank, &c->d_vlist, &c->d_vsums,
+                      &c->d_tile_times, &c->d_kd, &c->d_out, &c->d_counters, &c->d_hist, &c->d_spill, &c->d_light_tris,
+                      &c->d_light_cdf, &c->d_film_table, &c->d_img, &c->d_tex_recs, &c->d_texels, &c->d_mat_tex, &c->d_tri_uv,
+                      &c->d_rkd, &c->d_mat_spec, &c->d_fg_li, &c->d_fg_sum};
     for (DevBuf *b : bufs) b->release();
+    c->rec.release(); c->fg_rec.release();
+    c->map.release(); c->cmap.release();
     c->tiles.release();
     if (c->hist_event) (void)hipEventDestroy(c->hist_event);
     if (c->dirty_event) (void)hipEventDestroy(c->dirty_event);
@@ -307,15 +308,15 @@ int pm_trace_counters(void *ptr, int64_t out[4]) {
 int pm_map_info(void *ptr, int64_t out[4]) {
     GETCTX(ptr);
     if (!out) FAIL(c, PM_ERR_INVALID, "null output");
-    out[0] = c->map_kind; out[1] = 0; out[2] = c->map_slots; out[3] = 0;
+    out[0] = c->map_kind; out[1] = 0; out[2] = c->map.slots; out[3] = 0;
     if (c->map_kind == PM_GATHER_KDTREE) {
         out[1] = c->kd_count;
     } else if (c->map_kind == PM_GATHER_GRID) {
         uint32_t nv = 0;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(&nv, c->d_cell_start.as<uint32_t>() + c->grid.ncells, 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, c->map.valid_photons(&nv));
         out[1] = nv;
-        out[3] = c->grid.ncells;
+        out[3] = c->map.grid.ncells;
     }
     return PM_OK;
 }

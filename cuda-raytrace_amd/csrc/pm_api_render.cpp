@@ -41,7 +41,7 @@ static int valid_photons(Ctx *ec, Ctx *c, const pm_render_params *p, int64_t &nv
     nvalid = c->kd_count;
     if (p->gather_structure == PM_GATHER_GRID) {
         uint32_t nv = 0;
-        HIPCHK(ec, hipMemcpyAsync(&nv, c->d_cell_start.as<uint32_t>() + c->grid.ncells, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(ec, c->map.valid_photons(&nv, c->stream));
         HIPCHK(ec, hipStreamSynchronize(c->stream));
         nvalid = nv;
     }
@@ -70,7 +70,7 @@ static int render_stats(Ctx *ec, Ctx *c, double emitted, int64_t nvalid, pm_stat
     st->paths_emitted = (int64_t)emitted;
     st->photons_valid = nvalid;
     std::vector<float4> pos(c->nrec);
-    HIPCHK(ec, hipMemcpy(pos.data(), c->d_pos.p, c->nrec * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(ec, hipMemcpy(pos.data(), c->rec.pos.p, c->nrec * sizeof(float4), hipMemcpyDeviceToHost));
     for (auto &q : pos) st->gather_points += (fbits_h(q.w) & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID)) == 0;
     return PM_OK;
 }

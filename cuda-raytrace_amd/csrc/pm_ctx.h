@@ -1,10 +1,11 @@
 /*
- * pm_ctx.h — what the units of the C-ABI (pm_api.cpp, pm_api_scene.cpp,
- * pm_api_stage.cpp, pm_api_render.cpp) share and nothing else includes: the
- * context (DevBuf, TileList, Ctx, Group), the error and context macros
- * (FAIL / HIPCHK / GETCTX / GROUP_FWD) and the few helpers more than one unit
- * calls. Everything here is hidden: the library exports the pm_* entry points
- * of include/pm_api.h alone.
+ * pm_ctx.h — what the units of the C-ABI (pm_api.cpp, pm_api_scene.cpp, the
+ * stage units pm_api_records.cpp, pm_api_photons.cpp, pm_api_gather.cpp and
+ * pm_api_fgather.cpp, pm_api_render.cpp) share and nothing else includes: the
+ * context (DevBuf, RecordBufs, BucketMap, TileList, Ctx, Group), the error and
+ * context macros (FAIL / HIPCHK / GETCTX / GROUP_FWD) and the few helpers more
+ * than one unit calls. Everything here is hidden: the library exports the
+ * pm_* entry points of include/pm_api.h alone.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -55,6 +56,52 @@ struct DevBuf {
     bool external = false; /* caller-owned memory: never freed or grown here */
     void release() { if (p && !external) (void)hipFree(p); p = nullptr; bytes = 0; external = false; }
     template <class T> T *as() const { return (T *)p; }
+};
+
+/* One record set (RecordsDev) in device memory: Ctx::rec holds the primary
+ * records, Ctx::fg_rec the secondary records of a final-gather chunk. */
+struct RecordBufs {
+    DevBuf pos, nrm, state, n, dl;
+    hipError_t ensure(int64_t cnt) {
+        hipError_t e = hipSuccess;
+        for (DevBuf *b : {&pos, &nrm, &state, &n, &dl})
+            if ((e = b->ensure((size_t)cnt * (b == &n ? sizeof(float) : sizeof(float4)))) != hipSuccess) break;
+        return e;
+    }
+    RecordsDev dev(int64_t cnt) const {
+        return {pos.as<float4>(), nrm.as<float4>(), state.as<float4>(), n.as<float>(), dl.as<float4>(), cnt};
+    }
+    void release() { for (DevBuf *b : {&pos, &nrm, &state, &n, &dl}) b->release(); }
+    /* blocking copies of the first cnt records to / from the C-ABI's layout (pm_api_records.cpp) */
+    hipError_t download(pm_record *out, int64_t cnt) const;
+    hipError_t upload(const pm_record *in, int64_t cnt);
+};
+
+/* One bucket map: the cell-sorted photons of a build on `grid`, and the kNN
+ * scalar stream's buffers over them. Ctx::map is pm_build_photon_map's (its
+ * count and scratch are also what a fused trace writes and materialize_slots
+ * reads), Ctx::cmap pm_build_caustic_map's. */
+struct BucketMap {
+    DevBuf count, cell_start, scratch, ph_a, ph_b;
+    DevBuf knn_pk, knn_ovf;    /* kNN scalar stream: photon pairs, handed-back tiles (+ count) */
+    GridDesc grid{};
+    int64_t slots = 0;         /* the slots of the last build */
+    uint64_t gen = 0;          /* bumped by every build */
+    uint64_t pack_gen = ~0ull; /* the build knn_pk's pairs were packed from */
+    void *pack_ptr = nullptr;  /* ... and the pair buffer they were written to */
+
+    void attach(GatherParams &G) const {
+        G.grid = grid;
+        G.cell_start = cell_start.as<uint32_t>();
+        G.ph_a = ph_a.as<float4>(); G.ph_b = ph_b.as<float4>();
+    }
+    /* the valid photons of the last build, cell_start[ncells]: copied on s,
+     * which the caller waits for, or (no s) by a blocking copy */
+    hipError_t valid_photons(uint32_t *nv, hipStream_t s = nullptr) const {
+        const uint32_t *last = cell_start.as<uint32_t>() + grid.ncells;
+        return s ? hipMemcpyAsync(nv, last, 4, hipMemcpyDeviceToHost, s) : hipMemcpy(nv, last, 4, hipMemcpyDeviceToHost);
+    }
+    void release() { for (DevBuf *b : {&count, &cell_start, &scratch, &ph_a, &ph_b, &knn_pk, &knn_ovf}) b->release(); }
 };
 
 /* The tiles (64 records) that hold an active record, in record order:
@@ -142,7 +189,7 @@ struct Ctx {
     DevBuf d_scene, d_rays, d_rand2d; /* d_scene: the scene blob (SceneDev) */
     DevBuf d_light_tris;              /* SceneDev::light_tris (kept out of the blob: never LDS-resident) */
     /* the committed scene's layout, and its light summary: emission / albedo
-     * bounds for the fixed-point flux scale (emission_bound chooses the
+     * bounds for the fixed-point flux scale (flux_bound chooses the
      * emission bound per call) and the PM_ALL_LIGHTS selection table, whose
      * device copy is d_light_cdf (TraceParams::light_cdf: a buffer of its own
      * like d_light_tris) */
@@ -165,7 +212,7 @@ struct Ctx {
     bool slots_nonneg = true;  /* the slot buffer holds no negative flux (uploaded slots are checked) */
     int bvh_depth = 0;
     /* records */
-    DevBuf d_pos, d_nrm, d_state, d_n, d_dl;
+    RecordBufs rec;
     int64_t nrec = 0;
     /* eye samples summed in the records' dl: 0 none yet (pm_set_camera,
      * pm_set_pinhole, pm_set_eye_rays), 1 after pm_eye_pass, +1 per
@@ -176,7 +223,7 @@ struct Ctx {
     DevBuf d_slots;
     int64_t slots_used = 0;
     /* lazy zero fill (TraceParams::lazy_zero): slots [0, slots_dirty) may hold
-     * stale data where their fused-count key (d_scratch, dirty_key_np /
+     * stale data where their fused-count key (map.scratch, dirty_key_np /
      * dirty_mpc) is invalid; materialize_slots zeroes them before any reader
      * but the bucket fill (env PM_LAZY_ZERO=1; by default the trace zeroes them
      * itself: same-box A/B in profiles/r05/trace_writes) */
@@ -184,22 +231,16 @@ struct Ctx {
     int dirty_mpc = 0;
     hipEvent_t dirty_event = nullptr;
     bool lazy_zero = false, slots_exposed = false;
-    /* photon buckets */
-    DevBuf d_count, d_cell_start, d_scratch, d_pha, d_phb;
-    DevBuf d_knnpk, d_knnovf; /* kNN scalar stream: photon pairs, handed-back tiles (+ count) */
+    /* photon buckets (pm_build_photon_map); map.slots also counts a kd-tree build's slots */
+    BucketMap map;
     DevBuf d_tile_times;      /* PM_TILE_TIMES diagnostic builds */
-    uint64_t map_gen = 0;      /* bumped by every bucket build */
-    uint64_t knn_pack_gen = ~0ull; /* the map d_knnpk's pairs were packed from */
-    void *knn_pack_ptr = nullptr;  /* ... and the pair buffer they were written to */
     bool knn_ss = true;       /* kNN: k_gather_knn_ss first (PM_KNN_SS=0: k_gather_knn_tile alone) */
     bool fuse_ok = true;      /* trace may fuse the bucket counting (off for the sub-contexts of a multi-device group) */
     struct { bool valid = false; int64_t n = 0; GridDesc grid{}; float r2 = 0.f; int64_t key_np = 0; int mpc = 1; } fused; /* counts made by the last trace (keys plane-major when key_np > 0) */
-    GridDesc grid{};
-    float grid_r2 = 0.f; /* radius^2 the photon map's grid is designed for */
+    float grid_r2 = 0.f; /* radius^2 the photon map's grid (map.grid) is designed for */
     int64_t bvh4_nodes = 0; /* 4-wide BVH of an HBM scene (0: binary traversal) */
     int bvh4_depth = 0;
     int map_kind = -1;
-    int64_t map_slots = 0;
     /* kd-tree */
     DevBuf d_kd;
     int64_t kd_count = 0;
@@ -222,22 +263,17 @@ struct Ctx {
      * primary record, valid for fg_nrec records of fg_n rays over fg_passes
      * passes; any new primary records drop them) and the chunk cap in
      * secondary records (env PM_FG_CHUNK, tests only) */
-    DevBuf d_fg_pos, d_fg_nrm, d_fg_state, d_fg_n, d_fg_dl, d_fg_li, d_fg_sum;
+    RecordBufs fg_rec;
+    DevBuf d_fg_li, d_fg_sum;
     int64_t fg_nrec = 0, fg_chunk = (int64_t)1 << 22;
     int fg_n = 0, fg_passes = 0;
     int64_t fg_chunks = 0; /* chunks (launches per stage timer) of the last pass */
-    /* the caustic map (pm_set_caustic_map): the bucket set pm_build_caustic_map
-     * fills from the marked slots on the grid cg_grid (built: cg_built), the
-     * kNN scalar stream's pairs and handed-back tiles over it (cg_gen bumped by
-     * every build, as map_gen) and the passes pm_caustic_gather has summed into
-     * the cg_nrec primary records */
+    /* the caustic map (pm_set_caustic_map): the bucket map pm_build_caustic_map
+     * fills from the marked slots on the full map's grid (built: cg_built) and
+     * the passes pm_caustic_gather has summed into the cg_nrec primary records */
     bool caustic_map = false;
-    DevBuf d_cg_count, d_cg_cell_start, d_cg_scratch, d_cg_pha, d_cg_phb, d_cg_knnpk, d_cg_knnovf;
-    GridDesc cg_grid{};
+    BucketMap cmap;
     bool cg_built = false;
-    int64_t cg_slots = 0;
-    uint64_t cg_gen = 0, cg_pack_gen = ~0ull;
-    void *cg_pack_ptr = nullptr;
     int cg_passes = 0;
     int64_t cg_nrec = 0;
     double cg_emitted = 0; /* paths_per_pass of the gathers, times cg_passes: the emitted paths of Lc */
@@ -256,8 +292,8 @@ struct Ctx {
     DevBuf d_hist;
     uint32_t *h_hist = nullptr, *h_hist_dev = nullptr;
     hipEvent_t hist_event = nullptr;
-    /* leading words of d_count known to be zero (the bucket scan clears the
-     * counters it reads); valid while d_count.p == count_zero_ptr */
+    /* leading words of map.count known to be zero (the bucket scan clears the
+     * counters it reads); valid while map.count.p == count_zero_ptr */
     size_t count_zero_words = 0;
     void *count_zero_ptr = nullptr;
     /* stages that get event pairs: "all", "" (none) or a comma list
@@ -267,6 +303,9 @@ struct Ctx {
     StageEvents stage;             /* the stage being timed (g_stage points here) */
     bool stage_marker = false;
     std::map<std::string, TimerPool> timers;
+    /* new or moved primary records: the final-gather and caustic sums are another
+     * record set's, and so are the tile list and the radii the grid plan binned */
+    void records_replaced() { fg_passes = 0; cg_passes = 0; tiles.invalidate(); grid_plan.invalidate(); }
 };
 
 #define FAIL(c, code, ...)                                                     \
@@ -335,6 +374,14 @@ inline bool real_filter(const pm_filter &f) { return f.type != PM_FILTER_NONE; }
 
 inline bool has_film(const Ctx *c) { return c->camera && real_filter(c->cam.filter); }
 
+inline RecordsDev recs(const Ctx *c) { return c->rec.dev(c->nrec); }
+
+/* number of records the range-based record calls address, and their list */
+inline int64_t view_size(const Ctx *c) { return c->view_active ? c->n_view : c->nrec; }
+inline const uint32_t *view_list(const Ctx *c) { return c->view_active ? c->d_vlist.as<uint32_t>() : nullptr; }
+
+inline bool same_grid(const GridDesc &a, const GridDesc &b) { return std::memcmp(&a, &b, sizeof(GridDesc)) == 0; }
+
 /* the helpers more than one unit calls, by the unit that defines them.
  * pm_api.cpp: the stage timers (an event pair per launch of a stage) and the Halton table of a pass */
 int timer_begin(Ctx *c, const char *name, hipStream_t s, bool marker = false);
@@ -343,8 +390,15 @@ double timer_ms(Ctx *c, const char *name, size_t k = 1);
 void halton_perm(uint32_t seed, uint32_t out[28]);
 /* pm_api_scene.cpp */
 void eye_camera(const Ctx *c, EyeParams &E);
-/* pm_api_stage.cpp */
-FinalParams final_params(Ctx *c, double emitted, int64_t begin, int64_t count, float *out);int materialize_reset(Ctx *c, hipStream_t s);
+/* pm_api_records.cpp */
 int check_params(Ctx *c, const pm_render_params *p);
+FinalParams final_params(Ctx *c, double emitted, int64_t begin, int64_t count, float *out);
+int materialize_reset(Ctx *c, hipStream_t s);
+int download_rgb(Ctx *c, const DevBuf &d, float *out_rgb, int64_t n);
+/* pm_api_photons.cpp */
+int materialize_slots(Ctx *c, hipStream_t s);
+/* pm_api_gather.cpp */
+GatherParams gather_params(Ctx *c, const pm_render_params *p);
+int gather_knn_setup(Ctx *c, const pm_render_params *p, GatherParams &G, BucketMap &m);
 
 #pragma GCC visibility pop

@@ -20,7 +20,7 @@
 namespace pm {
 /* Exact, order-independent flux sums for the bucket gather: each photon's
  * contribution is rounded once to a 64-bit fixed-point integer (scale 2^S
- * chosen per scene so that 2^23 maximal contributions fit, pm_api_stage.cpp
+ * chosen per scene so that 2^23 maximal contributions fit, pm_api_gather.cpp
  * fx_scale) and integers add associatively. The bucket order (atomic
  * arrival order in pm_bucket.hip) and the number of GPUs that hold the
  * photons therefore never change a bit of the result. */

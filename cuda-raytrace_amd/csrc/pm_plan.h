@@ -2,8 +2,8 @@
  * pm_plan.h — pass planning: which photon grid a pass gets (the grid of a
  * radius, the adaptive radius and its state machine), which record bands
  * a device of a group gathers, and the trace launch's geometry (TracePlan).
- * Host code only, no HIP: pm_api_stage.cpp performs the HIP call each answer
- * asks for, and tests/native drives the same code on a CPU
+ * Host code only, no HIP: pm_api_photons.cpp and pm_api_gather.cpp perform the
+ * HIP call each answer asks for, and tests/native drives the same code on a CPU
  * (tests/test_pass_plan.py, tests/test_trace_plan.py).
  */
 #pragma once
@@ -93,7 +93,7 @@ std::vector<std::vector<std::pair<int64_t, int64_t>>> device_bands(int64_t n, in
 
 /* ---- the trace launch ------------------------------------------------------
  * One trace call's launch geometry, decided once: pm_trace_photons
- * (pm_api_stage.cpp) fills TraceParams and sizes the spill buffer from it,
+ * (pm_api_photons.cpp) fills TraceParams and sizes the spill buffer from it,
  * launch_trace (pm_trace.hip) takes its kernel, grid and LDS bytes from it.
  * The kernels index what it sizes: trace_lane_body / trace_pool_body
  * (pm_trace.hip) derive the same lstk from TraceParams::pool_stack and

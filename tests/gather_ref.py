@@ -34,7 +34,7 @@ GROUP_MIN = 4           # PM_GROUP_MIN: lanes a leader group needs
 GROUP_MIN_SPARSE = 12   # PM_GROUP_MIN_SPARSE: the same for a sparse map
 SPARSE_CELLS = 20       # SPARSE_CELLS: sparse = under one photon per 20 cells
 GROUP_R = 3             # PM_GROUP_R: a leader group's reach in cells (span 2)
-COOP_STEPS = 8          # GatherParams::coop_steps of a scene traversed from LDS (pm_api_stage.cpp gather_params)
+COOP_STEPS = 8          # GatherParams::coop_steps of a scene traversed from LDS (pm_api_gather.cpp gather_params)
 
 WHITE = 0               # material ids of _scene(): scenes.cornell_box's white matte ...
 
@@ -154,7 +154,7 @@ def flux_bound(A, M, S, kd_tree=False):
 
 
 def fx_shift(scene, params):
-    """S of the gathers' fixed point 2^S (pm_api_stage.cpp gather_params)."""
+    """S of the gathers' fixed point 2^S (pm_api_gather.cpp gather_params)."""
     em = 0.0
     for L in scene.lights:
         if L[0] == "point":

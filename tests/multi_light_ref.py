@@ -216,7 +216,7 @@ def emission_bounds(scene, cdf=None):
 
 
 def ppm_fixed_unit(scene, cdf, max_photon_count=4):
-    """one unit of the PPM gather's fixed point under PM_ALL_LIGHTS (pm_api_stage.cpp
+    """one unit of the PPM gather's fixed point under PM_ALL_LIGHTS (pm_api_gather.cpp
     gather_params): 2^-S, S = floor(log2(2^40 / cmax)), cmax = emission bound *
     kd_max^mpc * kd_max / pi * 4"""
     kd = 1.0

@@ -67,7 +67,7 @@ def knn_reference(recs, photons, K, maxd2):
 def knn_fixed_unit(scene, r2, max_photon_count=4):
     """The kNN gathers' fixed-point unit per record (1 / sc): sc = the power of
     two below knn_fx * r_k^2 (pm_gather_knn.hip knn_scale), knn_fx = 2^24 / amax,
-    amax = 4 emit_max kd_max^mpc (pm_api_stage.cpp gather_knn_setup; emit_max over the
+    amax = 4 emit_max kd_max^mpc (pm_api_gather.cpp gather_knn_setup; emit_max over the
     lights: Le * area * 2 pi for a disk, I * 4 pi for a point; kd_max >= 1
     over the matte materials). Every term is rounded to this unit."""
     from pmrender.abi import PM_MATTE

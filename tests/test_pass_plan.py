@@ -122,7 +122,7 @@ def test_device_bands_equal_dist_bands(run):
 # ---- the state machine ---------------------------------------------------------
 # A step is (command, answer, flags[, field checks]); flags are the plan's
 # wanted accum dirty pending valid after the event. The commands of a pass
-# come in the order pm_api_stage.cpp's grid_radius2 delivers them: active, landed
+# come in the order pm_api_photons.cpp's grid_radius2 delivers them: active, landed
 # (the pending reduce's event has fired), due, issued (the reduce was
 # launched), began, radius; a binning gather (one that finds `wanted`) is
 # bin, binned. Streams: 1 = A, 2 = B. INIT: answer `radius` with the initial
