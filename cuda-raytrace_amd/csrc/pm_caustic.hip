@@ -13,7 +13,10 @@
  *                          map's own ph_a / ph_b, ph_b keeping the slot index
  *                          in the slot buffer (the kNN tie-break reads it)
  *   k_caustic_radiance     Lc_r of the primary records after pm_caustic_gather
- *   k_fg_resolve_caustic   k_fg_resolve with Lc_r: (dl + Lc) + Kd x (A / (N P))
+ *   k_fg_resolve<CAUSTIC>  final gathering's resolve (the accumulation is
+ *                          pm_fgather.hip's): out_r = dl_r + Kd_r x A_r / (N P),
+ *                          sanitised as k_final does; CAUSTIC: with Lc_r,
+ *                          (dl + Lc) + Kd x (A / (N P))
  *
  * The kNN gather over the map is pm_gather_knn*.hip's, as it is.
  */
@@ -25,7 +28,6 @@
 
 namespace pm {
 
-constexpr uint32_t REC_INACTIVE = PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID;
 constexpr uint32_t PHOTON_VALID = 1u, PHOTON_CAUSTIC = 2u;
 
 __global__ __launch_bounds__(256) void k_caustic_count(const pm_photon *slots, int64_t n, GridDesc g, uint32_t *count,
@@ -91,9 +93,7 @@ __global__ __launch_bounds__(256) void k_caustic_radiance(FgResolveParams P, flo
     const uint32_t flags = (uint32_t)__float_as_int(P.P.pos[r].w);
     v3 lc = mk(0.f, 0.f, 0.f);
     if (!(flags & REC_INACTIVE)) lc = caustic_radiance(P.P, P.materials, emitted, r);
-    P.out[3 * i + 0] = lc.x;
-    P.out[3 * i + 1] = lc.y;
-    P.out[3 * i + 2] = lc.z;
+    store_rgb(P.out, i, lc);
 }
 
 hipError_t launch_caustic_radiance(const FgResolveParams &p, float emitted, hipStream_t s) {
@@ -102,37 +102,39 @@ hipError_t launch_caustic_radiance(const FgResolveParams &p, float emitted, hipS
     return hipGetLastError();
 }
 
-/* k_fg_resolve (pm_fgather.hip) with the caustic radiance beside the direct light */
-__global__ __launch_bounds__(256) void k_fg_resolve_caustic(FgResolveParams P, float emitted) {
+/* pm_final_gather_resolve: k_final's layout and sanitising with the
+ * final-gathered indirect term, out = dl + Kd x (A / denom); CAUSTIC: with the
+ * caustic radiance beside the direct light, (dl + Lc) + Kd x (A / denom)
+ * (`emitted` is read by that instantiation alone) */
+template <bool CAUSTIC>
+__global__ __launch_bounds__(256) void k_fg_resolve(FgResolveParams P, float emitted) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= P.rec_count) return;
     const int64_t r = P.rec_begin + i;
     const uint32_t flags = (uint32_t)__float_as_int(P.P.pos[r].w);
-    int64_t o = i;
-    if (P.raster) {
-        int px, py;
-        rec_to_pixel(r, P.W, &px, &py);
-        if (flags & PM_REC_INVALID) return;
-        o = (int64_t)py * P.W + px;
-    }
+    int64_t o;
+    if (!out_index(r, i, P.raster, P.W, flags, &o)) return;
     v3 out = mk(0.f, 0.f, 0.f);
     if (!(flags & REC_INACTIVE)) {
         const float4 dl = P.P.dl[r], a = P.sum[r];
         const float4 m = P.materials[__float_as_int(P.P.nrm[r].w)];
         const v3 kd = __float_as_int(m.w) == PM_MATTE ? xyz(m) : mk(0.f, 0.f, 0.f);
-        const v3 lc = caustic_radiance(P.P, P.materials, emitted, r);
-        out = (xyz(dl) + lc) + kd * mk(a.x / P.denom, a.y / P.denom, a.z / P.denom); /* one IEEE division per channel */
-        const float y = 0.212671f * out.x + 0.715160f * out.y + 0.072169f * out.z;
-        if (isnan(out.x) || isnan(out.y) || isnan(out.z) || y < -1e-5f || isinf(y)) out = mk(0.f, 0.f, 0.f);
+        v3 direct = xyz(dl);
+        if (CAUSTIC) direct = direct + caustic_radiance(P.P, P.materials, emitted, r);
+        out = sanitise_radiance(direct + kd * mk(a.x / P.denom, a.y / P.denom, a.z / P.denom)); /* one IEEE division per channel */
     }
-    P.out[3 * o + 0] = out.x;
-    P.out[3 * o + 1] = out.y;
-    P.out[3 * o + 2] = out.z;
+    store_rgb(P.out, o, out);
+}
+
+hipError_t launch_fg_resolve(const FgResolveParams &p, hipStream_t s) {
+    if (p.rec_count <= 0) return hipSuccess;
+    pm_launch(k_fg_resolve<false>, dim3((unsigned)((p.rec_count + 255) / 256)), dim3(256), 0, s, p, 0.f);
+    return hipGetLastError();
 }
 
 hipError_t launch_fg_resolve_caustic(const FgResolveParams &p, float emitted, hipStream_t s) {
     if (p.rec_count <= 0) return hipSuccess;
-    pm_launch(k_fg_resolve_caustic, dim3((unsigned)((p.rec_count + 255) / 256)), dim3(256), 0, s, p, emitted);
+    pm_launch(k_fg_resolve<true>, dim3((unsigned)((p.rec_count + 255) / 256)), dim3(256), 0, s, p, emitted);
     return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
  * (SceneDev) and the block's view of it (scene_view), Ray and Hit, the
  * record-to-pixel map and the census helpers (wave_sum, count4). Included by
  * pm_kernels.h, so by every kernel unit and the API units. The units that
- * trace or shade (pm_trace.hip, pm_eye.hip) add pm_traverse.h and pm_shade.h;
+ * trace or shade (pm_trace.hip; pm_eye.hip and pm_fgather.hip through
+ * pm_eye_dev.h) add pm_traverse.h and pm_shade.h;
  * the vector math is pm_math.h.
  */
 #pragma once

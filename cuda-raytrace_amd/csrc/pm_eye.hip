@@ -9,62 +9,49 @@
  *                  (simple_render/simplerender.cu)
  *   k_camera_rays  pm_camera_rays: the rays of pm_set_camera's samples
  * (photon pass: pm_trace.hip)
+ *
+ * The rays, the specular chain and the direct-light loop are pm_eye_dev.h's,
+ * which final gathering (pm_fgather.hip) shares.
  */
 #include <hip/hip_runtime.h>
 
-#include "pm_kernels.h"
-#include "pm_sample.h"
-#include "pm_shade.h"
-#include "pm_traverse.h"
+#include "pm_eye_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace pm {
 
-/* The camera ray of sample (ix, iy) of the WS x HS raster, in the order of
- * operations pm_api.h pins (its jitter and film position, camera_randoms and
- * camera_film_xy of pm_kernels.h, are the film kernel's too): shared by k_eye,
- * k_simple and k_camera_rays. pass: the eye pass of a resampled render
- * (pm_eye_resample), the constant 0 anywhere else. */
-PMD void camera_ray(const CameraDev &C, float4 eye4, float4 fwd4, float4 right4, float4 up4, int WS, int HS, int ix,
-                    int iy, uint32_t pass, v3 *o, v3 *d, float *fx, float *fy) {
-    float ju, jv, lu, lv;
-    camera_randoms(C, (int64_t)iy * WS + ix, pass, &ju, &jv, &lu, &lv);
-    camera_film_xy(C, ix, iy, ju, jv, fx, fy);
-    const v3 eye = xyz(eye4), fwd = xyz(fwd4), right = xyz(right4), up = xyz(up4);
-    const float sx = (2.0f * ((float)ix + ju)) / (float)WS - 1.0f;
-    const float sy = 1.0f - (2.0f * ((float)iy + jv)) / (float)HS;
-    const v3 d0 = fwd + sx * right + sy * up;
-    if (C.lens_radius > 0.0f) {
-        float cx, cy;
-        concentric_sample_disk(lu, lv, &cx, &cy);
-        const v3 ol = eye + C.lens_radius * (cx * normalize(right) + cy * normalize(up));
-        const float ft = C.focal / sqrtf(dot(fwd, fwd));
-        const v3 pf = eye + d0 * ft;
-        *o = ol;
-        *d = normalize(pf - ol);
-    } else {
-        *o = eye;
-        *d = normalize(d0);
+/* the light samples of the eye pass and the simple renderer for sample index
+ * `pixel`: a Philox draw keyed (pixel, slot) with the eye pass as counter word
+ * 3 (pinhole and camera rays), else the host's rand2d table (host rays) */
+struct EyeLightSampler {
+    const EyeParams &P;
+    int64_t pixel;
+    uint32_t pass;
+    PMD void operator()(int slot, float *u1, float *u2) const {
+        if (P.pinhole) {
+            uint32_t o4[4];
+            pmdm_philox4x32_10((uint32_t)pixel, (uint32_t)slot, 0u, pass, P.light_seed, 0u, o4);
+            *u1 = pmdm_u01(o4[0]); *u2 = pmdm_u01(o4[1]);
+        } else {
+            const float *q = P.rand2d + ((size_t)pixel * P.n2d + slot) * 2;
+            *u1 = q[0]; *u2 = q[1];
+        }
     }
-}
+};
 
 /* ====================================================================== */
 /* eye pass                                                               */
 /* ====================================================================== */
-/* CAM: the rays of pm_set_camera (camera_ray above) over the sample
- * raster P.W x P.H; uniform per launch, so the pinhole / host-ray
- * instantiations (CAM = false) carry none of it */
+/* CAM: the rays of pm_set_camera (primary_ray<true>) */
 /* TEX: the committed scene has a textured material (SceneDev::tex_recs): the
  * direct light's f takes Kd from the texture at the hit, and the record's
  * albedo factor goes to P.kd (pm_kernels.h EyeParams::kd). The other
  * instantiations hold none of it. */
 /* SPEC: the committed scene has a material of the physical specular model
- * (SceneDev::mat_spec; always with TEX): the chain follows one branch per
- * sample, picked with a Philox draw keyed like the light samples (word 2 = 2,
- * word 3 = the depth), and carries an rgb throughput T that multiplies what
- * the record contributes: dl = T L, P.kd = T x (the texel, or 1). A material
- * of the reference's model in such a scene steps as it always did. */
+ * (SceneDev::mat_spec; always with TEX): specular_chain<MODE, true> carries an
+ * rgb throughput T that multiplies what the record contributes: dl = T L,
+ * P.kd = T x (the texel, or 1). */
 /* RESAMPLE (with CAM, without TEX and SPEC): eye pass P.pass > 0 of
  * pm_eye_resample. The record keeps its statistics (state, n) and moves under
  * them: the camera randoms and the light samples take P.pass as counter word
@@ -73,6 +60,7 @@ PMD void camera_ray(const CameraDev &C, float4 eye4, float4 fwd4, float4 right4,
  * other instantiations hold none of it: their pass is the constant 0. */
 template <int MODE, bool CAM, bool TEX, bool SPEC, bool RESAMPLE = false>
 PMD void eye_body(const EyeParams &P) {
+    static_assert(!RESAMPLE || CAM, "the resampled eye pass moves its records along pm_set_camera's rays");
     extern __shared__ __attribute__((aligned(16))) int stk[]; /* [stack_depth x EYE_BLOCK][scene blob (LDS)] */
     int *stack = stk + threadIdx.x;
     const SceneDev S = scene_view<mode_lds(MODE)>(P.S, reinterpret_cast<uint4 *>(stk + P.S.stack_depth * EYE_BLOCK),
@@ -82,95 +70,21 @@ PMD void eye_body(const EyeParams &P) {
     if (r >= P.R.count) return;
 
     Ray ray;
-    int64_t pixel;
-    float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    int64_t pixel; /* the sample index q: keys the light samples below */
     const uint32_t pass = RESAMPLE ? P.pass : 0u;
-    if (CAM) {
-        int px, py;
-        rec_to_pixel(r, P.W, &px, &py);
-        if (px >= P.W || py >= P.H) {
-            if (RESAMPLE) return;
-            P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float(PM_REC_INVALID));
-            P.R.nrm[r] = zero4; P.R.state[r] = zero4; P.R.n[r] = 0.f; P.R.dl[r] = zero4;
-            if (TEX) P.kd[r] = zero4;
-            return;
-        }
-        pixel = (int64_t)py * P.W + px; /* the sample index q: keys the light samples below */
-        float fx, fy;
-        camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, px, py, pass, &ray.o, &ray.d, &fx, &fy);
-    } else if (P.pinhole) {
-        int px, py;
-        rec_to_pixel(r, P.W, &px, &py);
-        if (px >= P.W || py >= P.H) {
-            P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float(PM_REC_INVALID));
-            P.R.nrm[r] = zero4; P.R.state[r] = zero4; P.R.n[r] = 0.f; P.R.dl[r] = zero4;
-            if (TEX) P.kd[r] = zero4;
-            return;
-        }
-        pixel = (int64_t)py * P.W + px;
-        float sx = (2.0f * ((float)px + 0.5f)) / (float)P.W - 1.0f;
-        float sy = 1.0f - (2.0f * ((float)py + 0.5f)) / (float)P.H;
-        v3 d = xyz(P.fwd) + sx * xyz(P.right) + sy * xyz(P.up);
-        ray.o = xyz(P.eye);
-        ray.d = normalize(d);
-    } else {
-        pixel = r;
-        const float *q = P.rays + 6 * r;
-        ray.o = mk(q[0], q[1], q[2]);
-        ray.d = mk(q[3], q[4], q[5]);
+    if (!primary_ray<CAM>(P, r, pass, &ray, &pixel)) {
+        if (!RESAMPLE) store_inactive<TEX>(P.R, P.kd, r, PM_REC_INVALID);
+        return;
     }
-    ray.tmin = P.eps;
-    ray.tmax = RT_DEFAULT_MAX;
-
-    int depth = 0;
     Hit h;
     Geo g;
-    uint32_t flags = 0;
     v3 T = mk(1.f, 1.f, 1.f); /* SPEC: the chain's throughput */
-    while (true) {
-        if (!traverse<false, MODE>(S, ray, h, stack, EYE_BLOCK)) { flags = PM_REC_MISS; break; }
-        g = shade<MODE == MODE_INST>(S, ray, h);
-        const v3 point = ray.o + ray.d * h.t;
-        int mtype = fbits(S.materials[g.material].w);
-        if (is_specular(mtype)) {
-            v3 wi;
-            bool ok;
-            float4 sa, sb;
-            bool pbrt = false;
-            if (SPEC) {
-                sa = S.mat_spec[2 * g.material]; sb = S.mat_spec[2 * g.material + 1];
-                pbrt = fbits(sb.w) != 0;
-            }
-            if (SPEC && pbrt) {
-                float u = 0.f;
-                if (mtype == PM_GLASS) {
-                    uint32_t o4[4];
-                    pmdm_philox4x32_10((uint32_t)((uint64_t)pixel & 0xffffffffu), (uint32_t)((uint64_t)pixel >> 32), 2u,
-                                       (uint32_t)(depth + 1), P.light_seed, 0u, o4);
-                    u = pmdm_u01(o4[0]);
-                }
-                v3 w; float eta2;
-                ok = material_specular_pbrt(mtype, sa, sb, g, -ray.d, u, &wi, &w, &eta2);
-                if (ok) T = (T * w) * eta2; /* radiance: a transmitted step scales by (ei / et)^2 */
-            } else {
-                ok = material_specular(mtype, g, -ray.d, &wi);
-            }
-            depth++;
-            if (depth > P.max_spec || !ok) { flags = PM_REC_EXCEPTION; break; }
-            ray.o = point; ray.d = wi; ray.tmin = P.eps; ray.tmax = RT_DEFAULT_MAX;
-            continue;
-        }
-        ray.o = point; /* keep the hit point; ray.d stays the incident direction */
-        break;
-    }
+    const uint32_t flags = specular_chain<MODE, SPEC>(S, stack, ray, h, g, P.eps, P.max_spec, pixel, P.light_seed, &T);
     if (flags) {
-        P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float((int)flags));
         if (RESAMPLE) { /* this sample adds no light (dl + 0 is dl: a sum from +0 is never -0); the statistics stay */
-            P.R.nrm[r] = zero4;
-            return;
-        }
-        P.R.nrm[r] = zero4; P.R.state[r] = zero4; P.R.n[r] = 0.f; P.R.dl[r] = zero4;
-        if (TEX) P.kd[r] = zero4;
+            P.R.pos[r] = make_float4(0.f, 0.f, 0.f, __int_as_float((int)flags));
+            P.R.nrm[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else store_inactive<TEX>(P.R, P.kd, r, flags);
         return;
     }
     const v3 point = ray.o, ns = g.ns, dir = ray.d;
@@ -185,40 +99,13 @@ PMD void eye_body(const EyeParams &P) {
 
     /* directLight (raytracing.cu:49-84) */
     v3 L = mk(0.f, 0.f, 0.f);
-    const int total = S.n_lights;
-    if (g.light < total) {
+    if (g.light < S.n_lights) {
         if (g.light >= 0) L = L + light_le(S.lights[g.light], -dir, g.ng);
         float4 m = S.materials[g.material];
         v3 kd = xyz(m);
         if (TEX && textured) kd = kdf;
         v3 fv = fbits(m.w) == PM_MATTE ? kd * INV_PI : mk(0.f, 0.f, 0.f);
-        for (int i = 0; i < total; ++i) {
-            const LightDev Lt = S.lights[i];
-            const int nS = fbits(Lt.p1_ns.w);
-            const int ltype = fbits(Lt.o_type.w);
-            for (int s = 0; s < nS; ++s) {
-                float u1 = 0.f, u2 = 0.f;
-                if (ltype == PM_LIGHT_AREA_DISK || ltype == PM_LIGHT_AREA_MESH) {
-                    int slot = fbits(Lt.p2_r2d.w) + s;
-                    if (P.pinhole) {
-                        uint32_t o4[4];
-                        pmdm_philox4x32_10((uint32_t)pixel, (uint32_t)slot, 0u, pass, P.light_seed, 0u, o4);
-                        u1 = pmdm_u01(o4[0]); u2 = pmdm_u01(o4[1]);
-                    } else {
-                        const float *q = P.rand2d + ((size_t)pixel * P.n2d + slot) * 2;
-                        u1 = q[0]; u2 = q[1];
-                    }
-                }
-                v3 uwi; float pdf;
-                v3 li = sample_l_shading(Lt, S.light_tris, point, u1, u2, &uwi, &pdf);
-                Ray sr;
-                sr.o = point; sr.d = uwi; sr.tmin = 0.001f; sr.tmax = 1.0f - 0.001f;
-                Hit sh;
-                float atten = traverse<true, MODE>(S, sr, sh, stack, EYE_BLOCK) ? 0.0f : 1.0f;
-                v3 wi = normalize(uwi);
-                L = L + (atten * fabsf(dot(ns, wi))) * fv * li / (pdf * nS);
-            }
-        }
+        L = direct_light<MODE>(S, stack, point, ns, fv, L, EyeLightSampler{P, pixel, pass});
     }
     /* Faceforward(nn, wo) side, for the kNN estimator (the reference keeps
      * record.direction itself, raytracing.cu:117) */
@@ -244,54 +131,34 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_eye_spec(EyeParams P) { eye_body<
 template <int MODE>
 __global__ __launch_bounds__(EYE_BLOCK) void k_eye_resample(EyeParams P) { eye_body<MODE, true, false, false, true>(P); }
 
-template <bool CAM, bool TEX>
-static void launch_eye_mode(const EyeParams &p, unsigned grid, size_t lds, hipStream_t s) {
-    switch (scene_mode(p.S)) {
-    case MODE_BRUTE: pm_launch((k_eye<MODE_BRUTE, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_LDS: pm_launch((k_eye<MODE_LDS, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_INST: pm_launch((k_eye<MODE_INST, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    default: pm_launch((k_eye<MODE_GLOBAL, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    }
-}
-
-template <bool CAM>
-static void launch_eye_spec(const EyeParams &p, unsigned grid, size_t lds, hipStream_t s) {
-    switch (scene_mode(p.S)) {
-    case MODE_BRUTE: pm_launch((k_eye_spec<MODE_BRUTE, CAM>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_LDS: pm_launch((k_eye_spec<MODE_LDS, CAM>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_INST: pm_launch((k_eye_spec<MODE_INST, CAM>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    default: pm_launch((k_eye_spec<MODE_GLOBAL, CAM>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    }
-}
-
 hipError_t launch_eye(const EyeParams &p, hipStream_t s) {
     if (p.R.count <= 0) return hipSuccess;
-    unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
-    const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
-    if (p.S.mat_spec) { /* a material of the physical specular model: the SPEC instantiations */
-        if (!p.kd || !p.S.mat_tex) return hipErrorInvalidValue;
-        if (p.camera) launch_eye_spec<true>(p, grid, lds, s);
-        else launch_eye_spec<false>(p, grid, lds, s);
-    } else if (p.S.tex_recs) { /* a textured scene: the TEX instantiations, which write the records' albedo */
-        if (!p.kd) return hipErrorInvalidValue;
-        if (p.camera) launch_eye_mode<true, true>(p, grid, lds, s);
-        else launch_eye_mode<false, true>(p, grid, lds, s);
-    } else if (p.camera) launch_eye_mode<true, false>(p, grid, lds, s);
-    else launch_eye_mode<false, false>(p, grid, lds, s);
+    /* a material of the physical specular model selects the SPEC instantiations, else a textured one the TEX
+     * instantiations; both write the records' albedo */
+    if ((p.S.mat_spec && !p.S.mat_tex) || ((p.S.mat_spec || p.S.tex_recs) && !p.kd)) return hipErrorInvalidValue;
+    unsigned grid;
+    size_t lds;
+    eye_launch_geometry(p.S, p.R.count, &grid, &lds);
+    dispatch_mode(scene_mode(p.S), [&](auto M) {
+        constexpr int MODE = decltype(M)::value;
+        void (*k)(EyeParams);
+        if (p.S.mat_spec) k = p.camera ? k_eye_spec<MODE, true> : k_eye_spec<MODE, false>;
+        else if (p.S.tex_recs) k = p.camera ? k_eye<MODE, true, true> : k_eye<MODE, false, true>;
+        else k = p.camera ? k_eye<MODE, true, false> : k_eye<MODE, false, false>;
+        pm_launch(k, dim3(grid), dim3(EYE_BLOCK), lds, s, p);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_eye_resample(const EyeParams &p, hipStream_t s) {
     if (p.R.count <= 0) return hipSuccess;
     if (!p.camera || p.pass == 0u || p.S.mat_spec || p.S.tex_recs) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
-    const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
-    switch (scene_mode(p.S)) {
-    case MODE_BRUTE: pm_launch((k_eye_resample<MODE_BRUTE>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_LDS: pm_launch((k_eye_resample<MODE_LDS>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_INST: pm_launch((k_eye_resample<MODE_INST>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    default: pm_launch((k_eye_resample<MODE_GLOBAL>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    }
+    unsigned grid;
+    size_t lds;
+    eye_launch_geometry(p.S, p.R.count, &grid, &lds);
+    dispatch_mode(scene_mode(p.S), [&](auto M) {
+        pm_launch((k_eye_resample<decltype(M)::value>), dim3(grid), dim3(EYE_BLOCK), lds, s, p);
+    });
     return hipGetLastError();
 }
 
@@ -300,10 +167,10 @@ hipError_t launch_eye_resample(const EyeParams &p, hipStream_t s) {
 /* ====================================================================== */
 /* One lane per eye sample: closest hit of the camera ray (no specular
  * chain), then for every light one shadow-tested sample (iSample 0, no pdf
- * division, no emitted term): L += att·|ns·wi|·f·li (simplerender.cu:40-72);
- * a miss is black (:75-79). The host's NaN / negative / infinite check
- * (simplerender.cpp:70-87) is fused into the store. Output: raster order
- * (pinhole) or sample order (host rays), float3 per sample. */
+ * division, no emitted term): direct_light's FIRST_ONLY form; a miss is black
+ * (:75-79). The host's NaN / negative / infinite check (simplerender.cpp:70-87)
+ * is fused into the store. Output: raster order (pinhole) or sample order
+ * (host rays), float3 per sample. */
 template <int MODE, bool CAM = false, bool TEX = false>
 __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
     extern __shared__ __attribute__((aligned(16))) int stk[];
@@ -316,31 +183,7 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
 
     Ray ray;
     int64_t pixel;
-    if (CAM) {
-        int px, py;
-        rec_to_pixel(r, P.W, &px, &py);
-        if (px >= P.W || py >= P.H) return;
-        pixel = (int64_t)py * P.W + px;
-        float fx, fy;
-        camera_ray(P.cam, P.eye, P.fwd, P.right, P.up, P.W, P.H, px, py, 0u, &ray.o, &ray.d, &fx, &fy);
-    } else if (P.pinhole) {
-        int px, py;
-        rec_to_pixel(r, P.W, &px, &py);
-        if (px >= P.W || py >= P.H) return;
-        pixel = (int64_t)py * P.W + px;
-        float sx = (2.0f * ((float)px + 0.5f)) / (float)P.W - 1.0f;
-        float sy = 1.0f - (2.0f * ((float)py + 0.5f)) / (float)P.H;
-        v3 d = xyz(P.fwd) + sx * xyz(P.right) + sy * xyz(P.up);
-        ray.o = xyz(P.eye);
-        ray.d = normalize(d);
-    } else {
-        pixel = r;
-        const float *q = P.rays + 6 * r;
-        ray.o = mk(q[0], q[1], q[2]);
-        ray.d = mk(q[3], q[4], q[5]);
-    }
-    ray.tmin = P.eps;
-    ray.tmax = RT_DEFAULT_MAX;
+    if (!primary_ray<CAM>(P, r, 0u, &ray, &pixel)) return;
 
     v3 L = mk(0.f, 0.f, 0.f);
     Hit h;
@@ -351,56 +194,23 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_simple(EyeParams P, float *out) {
         v3 kd = xyz(m);
         if (TEX && fbits(m.w) == PM_MATTE) kd = hit_kd<MODE == MODE_INST>(S, h, point, g.material, kd);
         const v3 fv = fbits(m.w) == PM_MATTE ? kd * INV_PI : mk(0.f, 0.f, 0.f); /* f(wo, wi) */
-        for (int i = 0; i < S.n_lights; ++i) {
-            const LightDev Lt = S.lights[i];
-            float u1 = 0.f, u2 = 0.f;
-            if (fbits(Lt.o_type.w) == PM_LIGHT_AREA_DISK || fbits(Lt.o_type.w) == PM_LIGHT_AREA_MESH) {
-                const int slot = fbits(Lt.p2_r2d.w); /* random2DStart + iSample 0 */
-                if (P.pinhole) {
-                    uint32_t o4[4];
-                    pmdm_philox4x32_10((uint32_t)pixel, (uint32_t)slot, 0u, 0u, P.light_seed, 0u, o4);
-                    u1 = pmdm_u01(o4[0]); u2 = pmdm_u01(o4[1]);
-                } else {
-                    const float *q = P.rand2d + ((size_t)pixel * P.n2d + slot) * 2;
-                    u1 = q[0]; u2 = q[1];
-                }
-            }
-            v3 uwi; float pdf;
-            const v3 li = sample_l_shading(Lt, S.light_tris, point, u1, u2, &uwi, &pdf);
-            Ray sr;
-            sr.o = point; sr.d = uwi; sr.tmin = 0.001f; sr.tmax = 1.0f - 0.001f;
-            Hit sh;
-            const float atten = traverse<true, MODE>(S, sr, sh, stack, EYE_BLOCK) ? 0.0f : 1.0f;
-            const v3 wi = normalize(uwi);
-            L = L + (atten * fabsf(dot(g.ns, wi))) * fv * li;
-        }
+        L = direct_light<MODE, true>(S, stack, point, g.ns, fv, L, EyeLightSampler{P, pixel, 0u});
     }
-    const float y = 0.212671f * L.x + 0.715160f * L.y + 0.072169f * L.z; /* pbrt RGBSpectrum::y */
-    if (isnan(L.x) || isnan(L.y) || isnan(L.z) || y < -1e-5f || isinf(y)) L = mk(0.f, 0.f, 0.f);
-    out[3 * pixel + 0] = L.x;
-    out[3 * pixel + 1] = L.y;
-    out[3 * pixel + 2] = L.z;
-}
-
-template <bool CAM, bool TEX>
-static void launch_simple_mode(const EyeParams &p, float *out, unsigned grid, size_t lds, hipStream_t s) {
-    switch (scene_mode(p.S)) {
-    case MODE_BRUTE: pm_launch((k_simple<MODE_BRUTE, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-    case MODE_LDS: pm_launch((k_simple<MODE_LDS, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-    case MODE_INST: pm_launch((k_simple<MODE_INST, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-    default: pm_launch((k_simple<MODE_GLOBAL, CAM, TEX>), dim3(grid), dim3(EYE_BLOCK), lds, s, p, out); break;
-    }
+    store_rgb(out, pixel, sanitise_radiance(L));
 }
 
 hipError_t launch_simple(const EyeParams &p, float *out, hipStream_t s) {
     if (p.R.count <= 0) return hipSuccess;
-    unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
-    const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
-    if (p.S.tex_recs) {
-        if (p.camera) launch_simple_mode<true, true>(p, out, grid, lds, s);
-        else launch_simple_mode<false, true>(p, out, grid, lds, s);
-    } else if (p.camera) launch_simple_mode<true, false>(p, out, grid, lds, s);
-    else launch_simple_mode<false, false>(p, out, grid, lds, s);
+    unsigned grid;
+    size_t lds;
+    eye_launch_geometry(p.S, p.R.count, &grid, &lds);
+    dispatch_mode(scene_mode(p.S), [&](auto M) {
+        constexpr int MODE = decltype(M)::value;
+        void (*k)(EyeParams, float *);
+        if (p.S.tex_recs) k = p.camera ? k_simple<MODE, true, true> : k_simple<MODE, false, true>;
+        else k = p.camera ? k_simple<MODE, true, false> : k_simple<MODE, false, false>;
+        pm_launch(k, dim3(grid), dim3(EYE_BLOCK), lds, s, p, out);
+    });
     return hipGetLastError();
 }
 

@@ -8,24 +8,20 @@
  *                   record + direct light with shadow rays, no emitted term
  *   k_fg_ray_dump   pm_final_gather_rays: the same rays, nothing traced
  *   k_fg_accumulate A_r += Li_j over a primary record's rays, ascending j
- *   k_fg_resolve    out_r = dl_r + Kd_r x A_r / (N P), sanitised as k_final does
  *
  * Between k_fg_rays and k_fg_accumulate the host runs the kNN gather
  * (pm_gather_knn*.hip) and k_final (pm_records.hip) over the secondary records
- * as they are.
+ * as they are. The resolve (k_fg_resolve) is pm_caustic.hip's, beside the
+ * caustic radiance it may add. The specular chain and the direct-light loop
+ * are pm_eye_dev.h's, which the eye pass (pm_eye.hip) shares.
  */
 #include <hip/hip_runtime.h>
 
-#include "pm_kernels.h"
-#include "pm_sample.h"
-#include "pm_shade.h"
-#include "pm_traverse.h"
+#include "pm_eye_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace pm {
-
-constexpr uint32_t REC_INACTIVE = PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID;
 
 /* pbrt's CoordinateSystem(v1, &v2, &v3) in fp32 */
 PMD void coordinate_system(v3 n, v3 *v1, v3 *v2) {
@@ -67,11 +63,24 @@ PMD bool fg_ray(const FgParams &P, int64_t r, int j, v3 *o, v3 *d) {
     return true;
 }
 
-/* One lane per secondary record. From the ray on this is k_eye's host-ray
- * path (pm_eye.hip eye_body without TEX / SPEC, which pm_final_gather_pass
- * refuses) through the same device functions in the same order, with two
- * differences: the light samples are keyed by the secondary record's index,
- * and the emitted term of a hit on a light is left out. */
+/* the light samples of secondary record s: a Philox draw keyed by s, with the
+ * slot in the seed's second word */
+struct FgLightSampler {
+    int64_t s;
+    uint32_t pass, light_seed;
+    PMD void operator()(int slot, float *u1, float *u2) const {
+        uint32_t o4[4];
+        pmdm_philox4x32_10((uint32_t)((uint64_t)s & 0xffffffffu), (uint32_t)((uint64_t)s >> 32), 0u, pass, light_seed,
+                           (uint32_t)slot, o4);
+        *u1 = pmdm_u01(o4[0]); *u2 = pmdm_u01(o4[1]);
+    }
+};
+
+/* One lane per secondary record. From the ray on it calls what k_eye calls
+ * (pm_eye.hip eye_body without TEX / SPEC, which pm_final_gather_pass
+ * refuses): pm_eye_dev.h's specular_chain, store_inactive and direct_light.
+ * Two things differ: the light samples are keyed by the secondary record's
+ * index, and the emitted term of a hit on a light is left out. */
 template <int MODE>
 __global__ __launch_bounds__(EYE_BLOCK) void k_fg_rays(FgParams P) {
     extern __shared__ __attribute__((aligned(16))) int stk[]; /* [stack_depth x EYE_BLOCK][scene blob (LDS)] */
@@ -84,69 +93,27 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_fg_rays(FgParams P) {
     const int64_t s = P.sec_begin + i;
     const int64_t r = s / P.n_gather;
     const int j = (int)(s - r * P.n_gather);
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
 
     Ray ray;
     uint32_t flags = 0;
     if (r >= P.P.count || !fg_ray(P, r, j, &ray.o, &ray.d)) flags = PM_REC_MISS; /* not traced: contributes 0 */
     ray.tmin = P.eps;
     ray.tmax = RT_DEFAULT_MAX;
-
-    int depth = 0;
     Hit h;
     Geo g;
-    while (!flags) {
-        if (!traverse<false, MODE>(S, ray, h, stack, EYE_BLOCK)) { flags = PM_REC_MISS; break; }
-        g = shade<MODE == MODE_INST>(S, ray, h);
-        const v3 point = ray.o + ray.d * h.t;
-        const int mtype = fbits(S.materials[g.material].w);
-        if (is_specular(mtype)) {
-            v3 wi;
-            const bool ok = material_specular(mtype, g, -ray.d, &wi);
-            depth++;
-            if (depth > P.max_spec || !ok) { flags = PM_REC_EXCEPTION; break; }
-            ray.o = point; ray.d = wi; ray.tmin = P.eps; ray.tmax = RT_DEFAULT_MAX;
-            continue;
-        }
-        ray.o = point; /* keep the hit point; ray.d stays the incident direction */
-        break;
-    }
+    if (!flags) flags = specular_chain<MODE, false>(S, stack, ray, h, g, P.eps, P.max_spec, 0, 0u, nullptr);
     if (flags) {
-        P.R.pos[i] = make_float4(0.f, 0.f, 0.f, __int_as_float((int)flags));
-        P.R.nrm[i] = zero4; P.R.state[i] = zero4; P.R.n[i] = 0.f; P.R.dl[i] = zero4;
+        store_inactive<false>(P.R, nullptr, i, flags);
         return;
     }
     const v3 point = ray.o, ns = g.ns, dir = ray.d;
 
     /* directLight (raytracing.cu:49-84) without the emitted term */
     v3 L = mk(0.f, 0.f, 0.f);
-    const int total = S.n_lights;
-    if (g.light < total) {
+    if (g.light < S.n_lights) {
         const float4 m = S.materials[g.material];
         const v3 fv = fbits(m.w) == PM_MATTE ? xyz(m) * INV_PI : mk(0.f, 0.f, 0.f);
-        for (int li_ = 0; li_ < total; ++li_) {
-            const LightDev Lt = S.lights[li_];
-            const int nS = fbits(Lt.p1_ns.w);
-            const int ltype = fbits(Lt.o_type.w);
-            for (int k = 0; k < nS; ++k) {
-                float u1 = 0.f, u2 = 0.f;
-                if (ltype == PM_LIGHT_AREA_DISK || ltype == PM_LIGHT_AREA_MESH) {
-                    const int slot = fbits(Lt.p2_r2d.w) + k;
-                    uint32_t o4[4];
-                    pmdm_philox4x32_10((uint32_t)((uint64_t)s & 0xffffffffu), (uint32_t)((uint64_t)s >> 32), 0u, P.pass,
-                                       P.light_seed, (uint32_t)slot, o4);
-                    u1 = pmdm_u01(o4[0]); u2 = pmdm_u01(o4[1]);
-                }
-                v3 uwi; float pdf;
-                const v3 li = sample_l_shading(Lt, S.light_tris, point, u1, u2, &uwi, &pdf);
-                Ray sr;
-                sr.o = point; sr.d = uwi; sr.tmin = 0.001f; sr.tmax = 1.0f - 0.001f;
-                Hit sh;
-                const float atten = traverse<true, MODE>(S, sr, sh, stack, EYE_BLOCK) ? 0.0f : 1.0f;
-                const v3 wi = normalize(uwi);
-                L = L + (atten * fabsf(dot(ns, wi))) * fv * li / (pdf * nS);
-            }
-        }
+        L = direct_light<MODE>(S, stack, point, ns, fv, L, FgLightSampler{s, P.pass, P.light_seed});
     }
     const uint32_t side = dot(ns, -dir) < 0.f ? PM_REC_BACKFACE : 0u;
     P.R.pos[i] = make_float4(point.x, point.y, point.z, __uint_as_float(side));
@@ -159,14 +126,12 @@ __global__ __launch_bounds__(EYE_BLOCK) void k_fg_rays(FgParams P) {
 hipError_t launch_fg_rays(const FgParams &p, hipStream_t s) {
     if (p.R.count <= 0) return hipSuccess;
     if (p.n_gather < 1 || p.S.tex_recs || p.S.mat_spec) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)((p.R.count + EYE_BLOCK - 1) / EYE_BLOCK);
-    const size_t lds = (size_t)p.S.stack_depth * EYE_BLOCK * 4 + p.S.lds_bytes;
-    switch (scene_mode(p.S)) {
-    case MODE_BRUTE: pm_launch((k_fg_rays<MODE_BRUTE>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_LDS: pm_launch((k_fg_rays<MODE_LDS>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    case MODE_INST: pm_launch((k_fg_rays<MODE_INST>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    default: pm_launch((k_fg_rays<MODE_GLOBAL>), dim3(grid), dim3(EYE_BLOCK), lds, s, p); break;
-    }
+    unsigned grid;
+    size_t lds;
+    eye_launch_geometry(p.S, p.R.count, &grid, &lds);
+    dispatch_mode(scene_mode(p.S), [&](auto M) {
+        pm_launch((k_fg_rays<decltype(M)::value>), dim3(grid), dim3(EYE_BLOCK), lds, s, p);
+    });
     return hipGetLastError();
 }
 
@@ -210,39 +175,6 @@ __global__ __launch_bounds__(256) void k_fg_accumulate(FgSumParams P) {
 hipError_t launch_fg_accumulate(const FgSumParams &p, hipStream_t s) {
     if (p.rec_count <= 0) return hipSuccess;
     pm_launch(k_fg_accumulate, dim3((unsigned)((p.rec_count + 255) / 256)), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
-/* k_final's layout and sanitising with the final-gathered indirect term */
-__global__ __launch_bounds__(256) void k_fg_resolve(FgResolveParams P) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= P.rec_count) return;
-    const int64_t r = P.rec_begin + i;
-    const uint32_t flags = (uint32_t)__float_as_int(P.P.pos[r].w);
-    int64_t o = i;
-    if (P.raster) {
-        int px, py;
-        rec_to_pixel(r, P.W, &px, &py);
-        if (flags & PM_REC_INVALID) return;
-        o = (int64_t)py * P.W + px;
-    }
-    v3 out = mk(0.f, 0.f, 0.f);
-    if (!(flags & REC_INACTIVE)) {
-        const float4 dl = P.P.dl[r], a = P.sum[r];
-        const float4 m = P.materials[__float_as_int(P.P.nrm[r].w)];
-        const v3 kd = __float_as_int(m.w) == PM_MATTE ? xyz(m) : mk(0.f, 0.f, 0.f);
-        out = xyz(dl) + kd * mk(a.x / P.denom, a.y / P.denom, a.z / P.denom); /* one IEEE division per channel */
-        const float y = 0.212671f * out.x + 0.715160f * out.y + 0.072169f * out.z;
-        if (isnan(out.x) || isnan(out.y) || isnan(out.z) || y < -1e-5f || isinf(y)) out = mk(0.f, 0.f, 0.f);
-    }
-    P.out[3 * o + 0] = out.x;
-    P.out[3 * o + 1] = out.y;
-    P.out[3 * o + 2] = out.z;
-}
-
-hipError_t launch_fg_resolve(const FgResolveParams &p, hipStream_t s) {
-    if (p.rec_count <= 0) return hipSuccess;
-    pm_launch(k_fg_resolve, dim3((unsigned)((p.rec_count + 255) / 256)), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

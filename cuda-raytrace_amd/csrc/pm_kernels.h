@@ -1,12 +1,16 @@
 /*
  * pm_kernels.h — kernel parameter blocks and launcher declarations shared by
  * the host orchestration (pm_api*.cpp around pm_ctx.h) and the HIP kernels (pm_trace.hip, pm_eye.hip, pm_bucket.hip,
- * pm_gather.hip, pm_gather_knn.hip, pm_records.hip, pm_bvh_gpu.hip, pm_film.hip, pm_fgather.hip).
+ * pm_gather.hip, pm_gather_knn.hip, pm_records.hip, pm_bvh_gpu.hip, pm_film.hip, pm_fgather.hip, pm_caustic.hip),
+ * with the few device and host helpers several of them use (REC_INACTIVE, the
+ * output tail, dispatch_mode, eye_launch_geometry).
  */
 #pragma once
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "pm_device.h"
 #include "pm_plan_pod.h"
@@ -55,6 +59,10 @@ enum { PM_GK_TILE = 0, PM_GK_LANE = 1 };
 enum { PM_GATHER_ERR_STACK = 1u, PM_GATHER_ERR_TREE = 2u };
 constexpr int KD_STACK = 32;       /* >= pbrt median kd-tree depth for < 2^31 photons */
 constexpr int KNN_BLOCK = 64;      /* k_gather_knn: one wave per block, LDS heaps [K][64] */
+
+/* a record that gathers nothing and shows black: its ray missed the scene, its
+ * specular chain failed, or it lies outside the raster */
+constexpr uint32_t REC_INACTIVE = PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID;
 
 /* device SoA record arrays */
 struct RecordsDev {
@@ -330,9 +338,54 @@ struct FgResolveParams {
     int raster, W;     /* as FinalParams */
 };
 
+/* the output tail of the kernels that write radiance (k_final, k_final_resampled,
+ * k_simple, k_fg_resolve): the host's check of photonmappingrenderer.cpp:251-268
+ * and simplerender.cpp:70-87 (a NaN, or a negative or infinite luminance, pbrt
+ * RGBSpectrum::y, shows black), the float3 store, and the place of record r,
+ * number i of its launch, in `out`: i, or with `raster` its pixel (false for a
+ * record outside the raster, which has none) */
+PMD v3 sanitise_radiance(v3 v) {
+    const float y = 0.212671f * v.x + 0.715160f * v.y + 0.072169f * v.z;
+    if (isnan(v.x) || isnan(v.y) || isnan(v.z) || y < -1e-5f || isinf(y)) v = mk(0.f, 0.f, 0.f);
+    return v;
+}
+PMD void store_rgb(float *out, int64_t o, v3 v) {
+    out[3 * o + 0] = v.x;
+    out[3 * o + 1] = v.y;
+    out[3 * o + 2] = v.z;
+}
+PMD bool out_index(int64_t r, int64_t i, int raster, int W, uint32_t flags, int64_t *o) {
+    *o = i;
+    if (raster) {
+        int px, py;
+        rec_to_pixel(r, W, &px, &py);
+        if (flags & PM_REC_INVALID) return false;
+        *o = (int64_t)py * W + px;
+    }
+    return true;
+}
+
 /* traversal mode of a scene: LDS-resident blob (brute force when tiny) or HBM */
 inline int scene_mode(const SceneDev &S) {
     return S.n_inst > 0 ? MODE_INST : S.lds_bytes ? (S.brute ? MODE_BRUTE : MODE_LDS) : MODE_GLOBAL;
+}
+/* f(std::integral_constant<int, MODE>) for the traversal mode `mode`: the one
+ * switch from a scene's mode to the kernels instantiated per mode */
+template <class F>
+inline void dispatch_mode(int mode, F &&f) {
+    switch (mode) {
+    case MODE_BRUTE: f(std::integral_constant<int, MODE_BRUTE>{}); break;
+    case MODE_LDS: f(std::integral_constant<int, MODE_LDS>{}); break;
+    case MODE_INST: f(std::integral_constant<int, MODE_INST>{}); break;
+    default: f(std::integral_constant<int, MODE_GLOBAL>{}); break;
+    }
+}
+/* a launch of the eye-side traversal kernels over `count` lanes: blocks of
+ * EYE_BLOCK, and as dynamic LDS a stack column per lane, then the scene blob
+ * of the LDS modes */
+inline void eye_launch_geometry(const SceneDev &S, int64_t count, unsigned *grid, size_t *lds) {
+    *grid = (unsigned)((count + EYE_BLOCK - 1) / EYE_BLOCK);
+    *lds = (size_t)S.stack_depth * EYE_BLOCK * 4 + S.lds_bytes;
 }
 
 hipError_t launch_eye(const EyeParams &p, hipStream_t s);

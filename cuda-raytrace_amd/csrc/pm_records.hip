@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void k_ppm_update(RecordsDev R, const long lon
     if (i >= rec_count) return;
     const int64_t r = view ? (int64_t)view[rec_begin + i] : rec_begin + i;
     uint32_t flags = (uint32_t)__float_as_int(R.pos[r].w);
-    if (flags & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID)) return;
+    if (flags & REC_INACTIVE) return;
     const longlong2 *q = reinterpret_cast<const longlong2 *>(partial + 4 * i);
     const longlong2 a = q[0], b = q[1];
     const int M = (int)a.x;
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void k_ppm_update_split(RecordsDev R, const in
     if (i >= n_view) return;
     const int64_t r = view ? (int64_t)view[i] : i;
     const uint32_t flags = (uint32_t)__float_as_int(R.pos[r].w);
-    if (flags & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID)) return;
+    if (flags & REC_INACTIVE) return;
     const int M = count[i];
     if (M <= 0 && !fresh) return;
     float4 st = fresh ? make_float4(0.f, 0.f, 0.f, r2init) : R.state[r];
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void k_ppm_update_radius(RecordsDev R, const i
     const int64_t r = view ? (int64_t)view[i] : i;
     ratio_out[i] = -1.f;
     const uint32_t flags = (uint32_t)__float_as_int(R.pos[r].w);
-    if (flags & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID)) return;
+    if (flags & REC_INACTIVE) return;
     const int M = count[i];
     if (M <= 0 && !fresh) return;
     float4 st = fresh ? make_float4(0.f, 0.f, 0.f, r2init) : R.state[r];
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void k_view_flags(RecordsDev R, uint32_t *flag
     if (r > R.count) return;
     if (r == R.count) { flags[r] = 0u; return; } /* scanned tail -> total */
     const uint32_t f = (uint32_t)__float_as_int(R.pos[r].w);
-    flags[r] = (f & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID)) ? 0u : 1u;
+    flags[r] = (f & REC_INACTIVE) ? 0u : 1u;
 }
 
 __global__ __launch_bounds__(256) void k_view_list(RecordsDev R, const uint32_t *flags, uint32_t *rank,
@@ -192,18 +192,11 @@ __global__ __launch_bounds__(256) void k_final(FinalParams P) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= P.rec_count) return;
     const int64_t r = P.view ? (int64_t)P.view[P.rec_begin + i] : P.rec_begin + i;
-    int64_t o = i;
-    if (P.raster) {
-        int px, py;
-        rec_to_pixel(r, P.W, &px, &py);
-        uint32_t fl = (uint32_t)__float_as_int(P.R.pos[r].w);
-        if (fl & PM_REC_INVALID) return;
-        o = (int64_t)py * P.W + px;
-    }
-    float4 pos = P.R.pos[r];
-    uint32_t flags = (uint32_t)__float_as_int(pos.w);
+    const uint32_t flags = (uint32_t)__float_as_int(P.R.pos[r].w);
+    int64_t o;
+    if (!out_index(r, i, P.raster, P.W, flags, &o)) return;
     v3 out = mk(0.f, 0.f, 0.f);
-    if (!(flags & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID))) {
+    if (!(flags & REC_INACTIVE)) {
         float4 dl = P.R.dl[r], st = P.R.state[r];
         float N = P.R.n[r];
         v3 IDL = mk(0.f, 0.f, 0.f);
@@ -216,13 +209,9 @@ __global__ __launch_bounds__(256) void k_final(FinalParams P) {
             if (P.kd) IDL = (xyz(P.kd[r]) * xyz(st)) * INV_PI / (st.w * P.emitted);
             else IDL = xyz(st) * INV_PI / (st.w * P.emitted);
         }
-        out = xyz(dl) + IDL;
-        float y = 0.212671f * out.x + 0.715160f * out.y + 0.072169f * out.z;
-        if (isnan(out.x) || isnan(out.y) || isnan(out.z) || y < -1e-5f || isinf(y)) out = mk(0.f, 0.f, 0.f);
+        out = sanitise_radiance(xyz(dl) + IDL);
     }
-    P.out[3 * o + 0] = out.x;
-    P.out[3 * o + 1] = out.y;
-    P.out[3 * o + 2] = out.z;
+    store_rgb(P.out, o, out);
 }
 
 /* k_final over the records of a resampled render (FinalParams::resampled,
@@ -235,13 +224,8 @@ __global__ __launch_bounds__(256) void k_final_resampled(FinalParams P) {
     if (i >= P.rec_count) return;
     const int64_t r = P.view ? (int64_t)P.view[P.rec_begin + i] : P.rec_begin + i;
     const uint32_t flags = (uint32_t)__float_as_int(P.R.pos[r].w);
-    int64_t o = i;
-    if (P.raster) {
-        int px, py;
-        rec_to_pixel(r, P.W, &px, &py);
-        if (flags & PM_REC_INVALID) return;
-        o = (int64_t)py * P.W + px;
-    }
+    int64_t o;
+    if (!out_index(r, i, P.raster, P.W, flags, &o)) return;
     v3 out = mk(0.f, 0.f, 0.f);
     if (!(flags & PM_REC_INVALID)) {
         const float4 dl = P.R.dl[r], st = P.R.state[r];
@@ -249,19 +233,15 @@ __global__ __launch_bounds__(256) void k_final_resampled(FinalParams P) {
         v3 IDL = mk(0.f, 0.f, 0.f);
         if (N != 0) IDL = xyz(st) * INV_PI / (st.w * P.emitted);
         const float ne = (float)P.n_eye; /* one IEEE division per channel (v3 / float would multiply by 1 / ne) */
-        out = mk(dl.x / ne, dl.y / ne, dl.z / ne) + IDL;
-        float y = 0.212671f * out.x + 0.715160f * out.y + 0.072169f * out.z;
-        if (isnan(out.x) || isnan(out.y) || isnan(out.z) || y < -1e-5f || isinf(y)) out = mk(0.f, 0.f, 0.f);
+        out = sanitise_radiance(mk(dl.x / ne, dl.y / ne, dl.z / ne) + IDL);
     }
-    P.out[3 * o + 0] = out.x;
-    P.out[3 * o + 1] = out.y;
-    P.out[3 * o + 2] = out.z;
+    store_rgb(P.out, o, out);
 }
 
 __global__ __launch_bounds__(256) void k_tile_flags(RecordsDev R, uint8_t *flags) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     bool act = false;
-    if (r < R.count) act = !((uint32_t)__float_as_int(R.pos[r].w) & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID));
+    if (r < R.count) act = !((uint32_t)__float_as_int(R.pos[r].w) & REC_INACTIVE);
     const unsigned long long m = __ballot(act);
     if ((threadIdx.x & 63) == 0 && r < R.count) flags[r >> 6] = m != 0ull ? 1 : 0;
 }
@@ -360,7 +340,7 @@ __global__ __launch_bounds__(256) void k_reset_records(RecordsDev R, float r2ini
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= R.count) return;
     uint32_t flags = (uint32_t)__float_as_int(R.pos[r].w);
-    if (flags & (PM_REC_MISS | PM_REC_EXCEPTION | PM_REC_INVALID)) return;
+    if (flags & REC_INACTIVE) return;
     R.state[r] = make_float4(0.f, 0.f, 0.f, r2init);
     R.n[r] = 0.f;
 }
