@@ -288,6 +288,61 @@ int pm_upload_slots(void *ptr, const pm_photon *in, int64_t n) {
     return PM_OK;
 }
 
+/* ---- test hooks: the bucket map of the last pm_build_photon_map, read only.
+ * What needs no context is checked before the context is. */
+#define MAP_HOOK(fn, null_arg)                                                                    \
+    if (null_arg) FAIL((Ctx *)ptr, PM_ERR_INVALID, fn ": null pointer");                          \
+    if (!ptr) FAIL((Ctx *)nullptr, PM_ERR_INVALID, fn ": null context");                          \
+    GETCTX(ptr);                                                                                  \
+    if (c->map_kind != PM_GATHER_GRID || !c->map.cell_start.p)                                    \
+        FAIL(c, PM_ERR_INVALID, fn ": no photon map built on the buckets (pm_build_photon_map)"); \
+    HIPCHK(c, hipStreamSynchronize(c->stream))
+
+int pm_map_grid(void *ptr, int32_t dims[3], float origin[3], uint32_t *inv_cs_bits) {
+    MAP_HOOK("pm_map_grid", !dims || !origin || !inv_cs_bits);
+    const GridDesc &g = c->map.grid;
+    dims[0] = g.dx; dims[1] = g.dy; dims[2] = g.dz;
+    origin[0] = g.gx; origin[1] = g.gy; origin[2] = g.gz;
+    std::memcpy(inv_cs_bits, &g.inv_cs, 4);
+    return PM_OK;
+}
+
+int pm_download_map_cell_start(void *ptr, uint32_t *out, int64_t n) {
+    if (n < 0) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_download_map_cell_start: negative size %lld", (long long)n);
+    MAP_HOOK("pm_download_map_cell_start", !out);
+    const int64_t have = (int64_t)c->map.grid.ncells + 1;
+    if (n > have || (size_t)n * 4 > c->map.cell_start.bytes)
+        FAIL(c, PM_ERR_INVALID, "pm_download_map_cell_start: %lld words asked, %lld held", (long long)n, (long long)have);
+    HIPCHK(c, hipMemcpy(out, c->map.cell_start.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PM_OK;
+}
+
+int pm_download_map_counters(void *ptr, uint32_t *out, int64_t n) {
+    if (n < 0) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_download_map_counters: negative size %lld", (long long)n);
+    MAP_HOOK("pm_download_map_counters", !out);
+    const int64_t have = (int64_t)c->map.grid.ncells + 1;
+    if (n > have || !c->map.count.p || (size_t)n * 4 > c->map.count.bytes)
+        FAIL(c, PM_ERR_INVALID, "pm_download_map_counters: %lld words asked, %lld held", (long long)n, (long long)have);
+    HIPCHK(c, hipMemcpy(out, c->map.count.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PM_OK;
+}
+
+int pm_download_map_photons(void *ptr, float *ph_a, float *ph_b, int64_t n) {
+    if (n < 0) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_download_map_photons: negative size %lld", (long long)n);
+    MAP_HOOK("pm_download_map_photons", !ph_a || !ph_b);
+    uint32_t nv = 0;
+    HIPCHK(c, c->map.valid_photons(&nv));
+    /* the photons the scan counted, and never more than the build sized the arrays for */
+    const int64_t have = std::min<int64_t>((int64_t)nv, c->map.slots);
+    if (n > have || (size_t)n * 16 > c->map.ph_a.bytes || (size_t)n * 32 > c->map.ph_b.bytes)
+        FAIL(c, PM_ERR_INVALID, "pm_download_map_photons: %lld photons asked, %lld held", (long long)n, (long long)have);
+    if (n == 0) return PM_OK;
+    HIPCHK(c, hipMemcpy(ph_a, c->map.ph_a.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(ph_b, c->map.ph_b.p, (size_t)n * 32, hipMemcpyDeviceToHost));
+    return PM_OK;
+}
+#undef MAP_HOOK
+
 int pm_download_kdtree(void *ptr, pm_photon *out, int64_t n) {
     GETCTX(ptr);
     if (!out || n < 0 || n > c->kd_count) FAIL(c, PM_ERR_INVALID, "bad kd range");

@@ -220,6 +220,38 @@ int pm_record_view_list(void *ptr, void *d_out, void *stream) {
     return PM_OK;
 }
 
+int pm_record_view_size(void *ptr, int64_t *n_view) {
+    if (!n_view) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_record_view_size: null pointer");
+    if (!ptr) FAIL((Ctx *)nullptr, PM_ERR_INVALID, "pm_record_view_size: null context");
+    GETCTX(ptr);
+    if (!c->view_active) FAIL(c, PM_ERR_INVALID, "pm_record_view_size: no active-record view (pm_set_record_view)");
+    *n_view = c->n_view;
+    return PM_OK;
+}
+
+int pm_download_tile_list(void *ptr, uint32_t *out, int64_t max_n, int64_t *n, int *sorted) {
+    if (!n || !sorted) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_download_tile_list: null pointer");
+    if (max_n < 0) FAIL((Ctx *)ptr, PM_ERR_INVALID, "pm_download_tile_list: negative size %lld", (long long)max_n);
+    if (!ptr) FAIL((Ctx *)nullptr, PM_ERR_INVALID, "pm_download_tile_list: null context");
+    GETCTX(ptr);
+    if (c->nrec <= 0) FAIL(c, PM_ERR_INVALID, "pm_download_tile_list: no records (run pm_eye_pass first)");
+    TileList &t = c->tiles;
+    HIPCHK(c, t.ensure(recs(c), c->stream));
+    HIPCHK(c, hipDeviceSynchronize()); /* the list may have been built or sorted on a caller's stream */
+    uint32_t cnt = 0;
+    HIPCHK(c, hipMemcpy(&cnt, t.d_count.p, 4, hipMemcpyDeviceToHost));
+    const int64_t tiles = (c->nrec + 63) / 64;
+    if ((int64_t)cnt > tiles || (size_t)cnt * 4 > t.d_list.bytes)
+        FAIL(c, PM_ERR_INVALID, "pm_download_tile_list: the list claims %u of %lld tiles", cnt, (long long)tiles);
+    *n = (int64_t)cnt;
+    *sorted = t.sorted ? 1 : 0;
+    if (!out) return PM_OK;
+    if (max_n < (int64_t)cnt)
+        FAIL(c, PM_ERR_INVALID, "pm_download_tile_list: room for %lld entries, %u held", (long long)max_n, cnt);
+    if (cnt) HIPCHK(c, hipMemcpy(out, t.d_list.p, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    return PM_OK;
+}
+
 int pm_set_record_view(void *ptr, int active_only, int64_t *n_view) {
     GETCTX(ptr);
     if (active_only) {

@@ -112,6 +112,12 @@ def load_library(path=None):
         "pm_scene_info": (c_int, [vp, ctypes.POINTER(i64)]),
         "pm_scene_section": (c_int, [vp, c_int, vp, i64, ctypes.POINTER(i64)]),
         "pm_map_info": (c_int, [vp, ctypes.POINTER(i64)]),
+        "pm_map_grid": (c_int, [vp, ctypes.POINTER(ctypes.c_int32), P_f, ctypes.POINTER(ctypes.c_uint32)]),
+        "pm_download_map_cell_start": (c_int, [vp, ctypes.POINTER(ctypes.c_uint32), i64]),
+        "pm_download_map_counters": (c_int, [vp, ctypes.POINTER(ctypes.c_uint32), i64]),
+        "pm_download_map_photons": (c_int, [vp, P_f, P_f, i64]),
+        "pm_download_tile_list": (c_int, [vp, ctypes.POINTER(ctypes.c_uint32), i64, ctypes.POINTER(i64), P_i]),
+        "pm_record_view_size": (c_int, [vp, ctypes.POINTER(i64)]),
         "pm_trace_profile": (c_int, [vp, ctypes.POINTER(i64), c_int]),
         "pm_set_counting": (c_int, [vp, c_int]),
         "pm_set_stage_timing": (c_int, [vp, ctypes.c_char_p]),
@@ -707,6 +713,45 @@ class Context:
         self._chk(self.lib.pm_map_info(self.h, out))
         v = [int(x) for x in out]
         return {"structure": v[0], "valid": v[1], "slots": v[2], "cells": v[3]}
+
+    # ---- test hooks of the photon buckets, the tile list and the record view (read only) ----
+    def map_grid(self):
+        """dict: dims (dx, dy, dz), origin (float32 x 3) and inv_cs_bits of the built buckets' grid (pm_map_grid)."""
+        dims, org, ib = (ctypes.c_int32 * 3)(), np.zeros(3, np.float32), ctypes.c_uint32()
+        self._chk(self.lib.pm_map_grid(self.h, dims, fptr(org), ctypes.byref(ib)))
+        return {"dims": tuple(int(d) for d in dims), "origin": org, "inv_cs_bits": int(ib.value)}
+
+    def _map_words(self, fn):
+        out = np.zeros(self.map_info()["cells"] + 1, np.uint32)
+        self._chk(fn(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(out)))
+        return out
+
+    def map_counters(self):
+        """The cells + 1 bucket counters (pm_download_map_counters): all zero after a build."""
+        return self._map_words(self.lib.pm_download_map_counters)
+
+    def photon_map(self):
+        """(cell_start [cells + 1] uint32, ph_a [n, 4] float32, ph_b [n, 2, 4] float32) of the built buckets, n =
+        cell_start[-1] photons in map order (pm_download_map_cell_start, pm_download_map_photons)."""
+        cs = self._map_words(self.lib.pm_download_map_cell_start)
+        n = min(int(cs[-1]), self.map_info()["slots"])  # never beyond what the build sized the arrays for
+        a, b = np.zeros((n, 4), np.float32), np.zeros((n, 2, 4), np.float32)
+        self._chk(self.lib.pm_download_map_photons(self.h, fptr(a), fptr(b), n))
+        return cs, a, b
+
+    def tile_list(self):
+        """(the tile list, uint32; whether a gather's costs have reordered it) (pm_download_tile_list)."""
+        n, srt = ctypes.c_int64(), ctypes.c_int()
+        self._chk(self.lib.pm_download_tile_list(self.h, None, 0, ctypes.byref(n), ctypes.byref(srt)))
+        out = np.zeros(max(int(n.value), 1), np.uint32)
+        self._chk(self.lib.pm_download_tile_list(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(out),
+                                                 ctypes.byref(n), ctypes.byref(srt)))
+        return out[:int(n.value)], bool(srt.value)
+
+    def record_view_size(self):
+        n = ctypes.c_int64()
+        self._chk(self.lib.pm_record_view_size(self.h, ctypes.byref(n)))
+        return int(n.value)
 
     def trace_profile(self, reset=False):
         """k_trace phase cycles (profiling builds, lib/libpmhip_prof.so): dict of summed cycles."""

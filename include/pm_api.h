@@ -695,6 +695,8 @@ int pm_set_record_view(void *ctx, int active_only, int64_t *n_view);
  * record indices (uint32 x n_view) — records outside the view are black. */
 int pm_final_view(void *ctx, double emitted, int64_t v_begin, int64_t v_count, void *d_out, void *stream);
 int pm_record_view_list(void *ctx, void *d_out, void *stream);
+/* the size of the active view as it stands (pm_set_record_view rebuilds it) */
+int pm_record_view_size(void *ctx, int64_t *n_view);
 /* PPM update of records [rec_begin, rec_begin+rec_count) from summed partials
  * (d_partial points at the partial of rec_begin). */
 int pm_ppm_update(void *ctx, const pm_render_params *params, const void *d_partial,
@@ -791,6 +793,37 @@ int pm_scene_section(void *ctx, int section, void *out, int64_t max_bytes, int64
  * (PM_GATHER_GRID / PM_GATHER_KDTREE, -1 none), [1] valid photons in it,
  * [2] slots it was built from, [3] grid cells (0 for the kd-tree) */
 int pm_map_info(void *ctx, int64_t out[4]);
+/* Test hooks: the photon buckets of the last pm_build_photon_map, read only.
+ * Each waits for the context's stream first and returns PM_ERR_INVALID, with
+ * a message that names the call, for a null context or pointer, a size that
+ * is negative or beyond what is held, and while no map is built on the buckets
+ * (PM_GATHER_GRID). With cells = dims[0] dims[1] dims[2] (pm_map_info [3]):
+ *  pm_map_grid                 the grid: cells per axis, the origin (the scene
+ *                              box's low corner) and the bits of the float32
+ *                              1 / cell edge. A photon at p lies in cell
+ *                              (cz dims[1] + cy) dims[0] + cx, c = floor((p -
+ *                              origin) inv_cs) in float32, clamped to the grid.
+ *  pm_download_map_cell_start  the first n <= cells + 1 words of cell_start:
+ *                              cell k holds photons [cell_start[k],
+ *                              cell_start[k + 1]); cell_start[cells] = valid
+ *                              photons.
+ *  pm_download_map_counters    the first n <= cells + 1 bucket counters; every
+ *                              build's scan leaves them zero.
+ *  pm_download_map_photons     the first n <= valid photons in map order:
+ *                              ph_a 4 floats each (p.xyz, wi.x), ph_b 8 floats
+ *                              each (alpha.rgb, wi.y | wi.z, the photon's slot
+ *                              index as uint32 bits, 0, 0). */
+int pm_map_grid(void *ctx, int32_t dims[3], float origin[3], uint32_t *inv_cs_bits);
+int pm_download_map_cell_start(void *ctx, uint32_t *out, int64_t n);
+int pm_download_map_counters(void *ctx, uint32_t *out, int64_t n);
+int pm_download_map_photons(void *ctx, float *ph_a, float *ph_b, int64_t n);
+/* Test hook: the tile list of the full-range tile gathers, built first if the
+ * records changed since the last one (so it exists after pm_upload_records):
+ * *n = its length, *sorted = 1 once a gather's measured costs reordered it, and
+ * with out != NULL (room for max_n >= *n entries) the ids of the 64-record
+ * tiles that hold an active record, ascending until sorted. Waits for the
+ * device. PM_ERR_INVALID as above, and without records. */
+int pm_download_tile_list(void *ctx, uint32_t *out, int64_t max_n, int64_t *n, int *sorted);
 /* Phase profile of the trace kernel, summed over waves and launches since the
  * last reset: shader-clock cycles in [0] emission, [1] BVH traversal,
  * [2] shading + bounce + deposit, [3] compaction barrier, [4] state exchange,

@@ -25,7 +25,9 @@ def declared_functions():
 def test_header_declares_entry_points():
     names = declared_functions()
     for must in ("pm_create", "pm_destroy", "pm_render", "pm_add_trimesh", "pm_add_sphere", "pm_add_disk",
-                 "pm_add_light_disk", "pm_trace_photons", "pm_build_photon_map", "pm_gather", "pm_final"):
+                 "pm_add_light_disk", "pm_trace_photons", "pm_build_photon_map", "pm_gather", "pm_final",
+                 "pm_map_grid", "pm_download_map_cell_start", "pm_download_map_counters", "pm_download_map_photons",
+                 "pm_download_tile_list", "pm_record_view_size"):
         assert must in names
     assert len(names) >= 40
 
