@@ -147,7 +147,8 @@ int pm_trace_photons(void *ptr, const pm_render_params *p, int pass, int64_t pat
     sh.mode = scene_mode(c->S); sh.wide = c->S.wide; sh.stack_depth = c->S.stack_depth; sh.lds_bytes = c->S.lds_bytes;
     sh.pool_stack = c->pool_stack; sh.trace_pool = c->trace_pool; sh.trace_hold = c->trace_hold;
     sh.mark = c->caustic_map;
-    if (c->S.wide && hipDeviceGetAttribute(&sh.cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) sh.cus = 0;
+    if (c->trace_cus > 0) sh.cus = c->trace_cus; /* env PM_TRACE_CUS: pools, grid and spill stride follow together */
+    else if (c->S.wide && hipDeviceGetAttribute(&sh.cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) sh.cus = 0;
     const TracePlan plan = plan_trace(sh, trace_waves_per_cu);
     T.hold = plan.hold; T.pool_stack = plan.lstk; T.pool_paths = plan.pool_paths;
     if (plan.spill_entries > 0) {

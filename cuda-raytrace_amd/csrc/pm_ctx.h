@@ -281,6 +281,8 @@ struct Ctx {
     bool trace_pool = true;         /* 4-wide scenes: the pooled trace kernel (env PM_TRACE_POOL=0: one path per lane) */
     bool trace_hold = true;         /* deposits written once per path where it costs no waves (env PM_TRACE_HOLD=0: per deposit) */
     int pool_stack = 31;            /* pooled kernel: LDS stack entries per lane (env PM_POOL_STACK; 0 = the exact bound): 31 lets five blocks share a CU's LDS */
+    int trace_cus = 0;              /* > 0: the compute units plan_trace sizes a wave's pool for, in place of the device's
+                                     * (env PM_TRACE_CUS: tests and diagnosis; small traces then refill their lanes) */
     DevBuf d_spill;                 /* pooled kernel: stack entries beyond pool_stack */
     int gather_kernel = PM_GK_TILE; /* bucket gather kernel (env PM_GATHER_KERNEL=tile|lane) */
     int cell_span = 2;              /* PPM grid: cells per axis of a query box (env PM_CELL_SPAN 2..5) */

@@ -114,7 +114,7 @@ struct TraceShape {
     uint32_t lds_bytes = 0;    /* S.lds_bytes */
     int pool_stack = 31;       /* the context's settings (env PM_POOL_STACK, PM_TRACE_POOL, PM_TRACE_HOLD) */
     bool trace_pool = true, trace_hold = true;
-    int cus = 0;               /* compute units of the device; <= 0: unknown, taken as 256 */
+    int cus = 0;               /* compute units of the device (the context's env PM_TRACE_CUS in their place); <= 0: unknown, taken as 256 */
     bool mark = false;         /* pm_set_caustic_map: the launch marks caustic photons (the MARK instantiations) */
 };
 

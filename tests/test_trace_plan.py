@@ -218,6 +218,36 @@ def test_path_counts_around_a_wave_a_block_and_an_occupancy_round(run):
     assert [p["grid"] for p in lanes[:8]] == [0, 1, 1, 1, 1, 1, 1, 2]
 
 
+def test_one_compute_unit_gives_small_traces_long_pools(run):
+    """PM_TRACE_CUS=1 (the context's planning input, TraceShape::cus): one CU's 20 pooled waves share the trace, so a
+    few thousand paths make pools of more than a wave's 64 lanes, whose lanes take second and third paths. Pool,
+    grid and spill stride move together. Occupancy comes in whole blocks, so above 19 paths per wave every wave of
+    the round has a pool and the last block is full; below, the last block can hold waves without one."""
+    round_waves = 20  # REGS and 160 KB of LDS at 31 stack entries: five blocks
+    counts = [3001, 2934, 1281, 70, 37, 1]
+    for hold, cap in ((0, LDS_CU), (1, ROOMY)):
+        cases = [case(paths=n, cus=1, depth=40, trace_hold=hold, cap=cap) for n in counts]
+        for n, c, p in zip(counts, cases, check(run, cases)):
+            want, _ = expected(c)
+            assert (p["grid"], p["spill_stride"], p["lds_hold"], p["pool_paths"]) == \
+                (want["grid"], want["spill_stride"], want["lds_hold"], want["pool_paths"])
+            assert p["pooled"] and p["hold"] == hold and p["pool_paths"] == -(-n // round_waves)
+            assert p["spill_entries"] == 9 and p["spill_stride"] == p["grid"] * TB
+            waves, last, idle = ref.pool_layout(p, n)
+            assert (waves - 1) * p["pool_paths"] < n <= waves * p["pool_paths"] and 0 <= idle < 4
+            if n > 64 * round_waves:
+                assert p["pool_paths"] > 64 and (waves, p["grid"], idle) == (round_waves, 5, 0)
+        by = {n: (p, ref.pool_layout(p, n)) for n, p in zip(counts, check(run, cases))}
+        assert [by[n][0]["pool_paths"] for n in counts] == [151, 147, 65, 4, 2, 1]
+        assert by[3001][1] == (20, 132, 0) and by[2934][1] == (20, 141, 0) and by[1281][1] == (20, 46, 0)
+        # the last pool partial and the last block not full: 70 paths in pools of 4 are 18 waves, the last of 2
+        # paths, in five blocks whose last two waves find their pool empty
+        assert by[70][1] == (18, 2, 2) and by[70][0]["grid"] == 5
+        assert by[37][1] == (19, 1, 1) and by[1][1] == (1, 1, 3) and by[1][0]["grid"] == 1
+    # the same traces on the whole device: pools of one path, no lane takes a second
+    assert all(p["pool_paths"] == 1 for p in check(run, [case(paths=n, cus=256, depth=40) for n in counts]))
+
+
 def test_trace_pool_off_and_the_eight_wide_tree(run):
     off4, off8, on8 = check(run, [case(trace_pool=0, wide=2, depth=40), case(trace_pool=0, wide=3, depth=70),
                                   case(trace_pool=1, wide=3, depth=70)])

@@ -82,3 +82,11 @@ def plan(paths, mpc, aligned, mode, wide, depth, blob, pool_stack, trace_pool, t
     p["hold"] = int(want_hold)
     p["hold_launch"] = int(want_hold and mpc == HOLD_MPC and bool(aligned))
     return p, asked
+
+
+def pool_layout(p, paths):
+    """how a pooled plan's waves share `paths` (trace_pool_body: wave w takes [w * pool_paths, (w + 1) * pool_paths)
+    clipped by paths): (waves with a pool, paths of the last pool, waves of the last block whose pool is empty)"""
+    assert p["pooled"] and p["pool_paths"] > 0
+    waves = ceil_div(paths, p["pool_paths"])
+    return waves, paths - (waves - 1) * p["pool_paths"], p["grid"] * WAVES_PER_BLOCK - waves
