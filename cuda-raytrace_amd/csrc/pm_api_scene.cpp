@@ -435,7 +435,7 @@ int pm_set_eye_rays(void *ptr, const float *rays, int64_t nrays, const float *ra
     GROUP_FWD(ptr, pm_set_eye_rays(sub, rays, nrays, rand2d, n2d));
     GETCTX(ptr);
     if (!rays || nrays <= 0) FAIL(c, PM_ERR_INVALID, "no rays");
-    /* the traversal modes agree bit for bit for finite rays with |o| <= 2^20 (pm_traverse.h box_near) */
+    /* the traversal modes agree bit for bit for finite rays with |o| <= 2^20 (pm_slab.h box_near) */
     for (int64_t i = 0; i < nrays; ++i)
         for (int a = 0; a < 3; ++a)
             if (!(fabsf(rays[6 * i + a]) <= PM_MAX_RAY_ORIGIN) || !std::isfinite(rays[6 * i + 3 + a]))

@@ -405,7 +405,7 @@ void bvh4_bfs_order(std::vector<float> &nodes) {
     nodes.swap(out);
 }
 
-/* the device's decode of a quantized bound (traverse4 / trav_step): o + q * 2^e,
+/* the device's decode of a quantized bound (pm_slab.h qslab): o + q * 2^e,
  * the power of two s = 2^e passed exactly */
 static float qdecode(float o, uint32_t q, float s) { return o + (float)q * s; }
 

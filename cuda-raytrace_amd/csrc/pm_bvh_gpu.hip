@@ -206,7 +206,7 @@ __global__ __launch_bounds__(BB) void k_bvh4_expand(Tree T, const int *fr, int n
     nint[f] = k;
 }
 
-/* the encoder's decode (pm_build.cpp qdecode; traverse4's FMA rounds the same) */
+/* the encoder's decode (pm_build.cpp qdecode; pm_slab.h qslab's FMA rounds the same) */
 __device__ __forceinline__ float qdecode(float o, uint32_t q, float s) { return o + (float)q * s; }
 
 /* writes 4-wide node level_base + f, quantized (pm_build.cpp quantize_nodes),

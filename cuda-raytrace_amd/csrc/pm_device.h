@@ -4,7 +4,8 @@
  * record-to-pixel map and the census helpers (wave_sum, count4). Included by
  * pm_kernels.h, so by every kernel unit and the API units. The units that
  * trace or shade (pm_trace.hip; pm_eye.hip and pm_fgather.hip through
- * pm_eye_dev.h) add pm_traverse.h and pm_shade.h;
+ * pm_eye_dev.h) add pm_traverse.h (boxes: pm_slab.h, primitives: pm_leaf.h;
+ * pm_trace.hip alone the resumable walk, pm_trav_step.h) and pm_shade.h;
  * the vector math is pm_math.h.
  */
 #pragma once

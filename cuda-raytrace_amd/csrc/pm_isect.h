@@ -2,8 +2,8 @@
  * pm_isect.h — the primitive intersectors (triangle, disk, sphere), the
  * sphere's ray and normal transforms, and the world-space triangle of an
  * instance's object slot (inst_point, inst_tri), which the instance walk
- * intersects and shade() rebuilds its frame from. Included by pm_traverse.h
- * and pm_shade.h.
+ * intersects and shade() rebuilds its frame from. Included by pm_leaf.h
+ * (so by pm_traverse.h) and pm_shade.h.
  */
 #pragma once
 #include "pm_device.h"

@@ -3,7 +3,7 @@
  * the host orchestration (pm_api*.cpp around pm_ctx.h) and the HIP kernels (pm_trace.hip, pm_eye.hip, pm_bucket.hip,
  * pm_gather.hip, pm_gather_knn.hip, pm_records.hip, pm_bvh_gpu.hip, pm_film.hip, pm_fgather.hip, pm_caustic.hip),
  * with the few device and host helpers several of them use (REC_INACTIVE, the
- * output tail, dispatch_mode, eye_launch_geometry).
+ * output tail, dispatch_mode, dispatch_flag, eye_launch_geometry).
  */
 #pragma once
 #include <hip/hip_ext.h>
@@ -379,6 +379,14 @@ inline void dispatch_mode(int mode, F &&f) {
     case MODE_INST: f(std::integral_constant<int, MODE_INST>{}); break;
     default: f(std::integral_constant<int, MODE_GLOBAL>{}); break;
     }
+}
+/* f(std::integral_constant<int, 1>) or <int, 0>: a launch's yes / no property
+ * to the template argument of the kernels instantiated for both (pm_trace.hip
+ * adds dispatch_mat for its four material classes) */
+template <class F>
+inline void dispatch_flag(bool flag, F &&f) {
+    if (flag) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
 }
 /* a launch of the eye-side traversal kernels over `count` lanes: blocks of
  * EYE_BLOCK, and as dynamic LDS a stack column per lane, then the scene blob

@@ -329,7 +329,7 @@ int commit_objects(const HostScene &hs, InstLayout &IL, std::string &err) {
             IL.insts.push_back(f4(in.minv[4 * r], in.minv[4 * r + 1], in.minv[4 * r + 2], in.minv[4 * r + 3]));
         const int nt = (int)(hs.objs[in.obj].idx.size() / 3);
         IL.insts.push_back(f4(ibits((int)root[in.obj]), ibits((int)slot0[in.obj]), ibits((int)in.gid_base), ibits(nt)));
-        /* blas_isect's box pad, 1e-5 (a (2 |o| + W) + k B): a = |w2o|, W
+        /* blas_isect's (pm_traverse.h) box pad, 1e-5 (a (2 |o| + W) + k B): a = |w2o|, W
          * bounds the world extent by |o2w| B + |translation|, k = |o2w| |w2o|
          * (infinity norms of the linear parts), B the object's extent */
         double B = 0.0, nm = 0.0, ni_ = 0.0, tr = 0.0;
@@ -370,7 +370,7 @@ int assemble_scene(const HostScene &hs, std::vector<BuildPrim> &prims, const Bui
     if (bvh.depth >= BVH_STACK) return fail(err, "BVH too deep (%d)", bvh.depth);
 
     /* tiny LDS scenes skip the BVH (MODE_BRUTE). Their triangles are stored
-     * in global-id order (brute_isect's tie-break relies on it), others in
+     * in global-id order (pm_leaf.h brute_isect's tie-break relies on it), others in
      * leaf order. */
     const bool id_order = ni == 0 && (int64_t)bvh.refs.size() <= BRUTE_MAX_PRIMS;
     std::vector<uint32_t> tri_order; /* triangle ids in storage order */

@@ -19,7 +19,7 @@
 #include "pm_plan.h"
 #include "pm_sample.h"
 #include "pm_shade.h"
-#include "pm_traverse.h"
+#include "pm_trav_step.h"
 
 #pragma clang fp contract(off)
 
@@ -28,17 +28,9 @@ namespace pm {
 /* ====================================================================== */
 /* photon pass                                                            */
 /* ====================================================================== */
-PMD void store_photon(pm_photon *dst, v3 p, v3 a, v3 wi) {
+/* bits = valid | caustic << 1 (pm_api.h pm_set_caustic_map): 1 from every kernel but the MARK ones */
+PMD void store_photon(pm_photon *dst, uint32_t bits, v3 p, v3 a, v3 wi) {
     /* 40-B slot, 8-B aligned: five 8-byte stores */
-    float2 *q = reinterpret_cast<float2 *>(dst);
-    q[0] = make_float2(__int_as_float(1), p.x);
-    q[1] = make_float2(p.y, p.z);
-    q[2] = make_float2(a.x, a.y);
-    q[3] = make_float2(a.z, wi.x);
-    q[4] = make_float2(wi.y, wi.z);
-}
-/* the MARK kernels' store: bits = valid | caustic << 1 (pm_api.h pm_set_caustic_map) */
-PMD void store_photon_marked(pm_photon *dst, uint32_t bits, v3 p, v3 a, v3 wi) {
     float2 *q = reinterpret_cast<float2 *>(dst);
     q[0] = make_float2(__uint_as_float(bits), p.x);
     q[1] = make_float2(p.y, p.z);
@@ -65,12 +57,14 @@ struct PathState {
     uint32_t diff;   /* MARK kernels only: a diffuse hit has happened (spec > 0 && nI == 1 also holds for L D S D) */
 };
 constexpr uint32_t PSLOT_NONE = 0xffffffffu;
+/* path pid's place in the launch's slot buffer, in paths: its slots start at mpc times this */
+PMD size_t path_slot_base(const TraceParams &P, uint32_t pid) { return (size_t)(pid - (uint64_t)P.slot_path_base); }
 /* where the fused bucket count keeps deposit k of path pid: plane-major
  * (k * key_np + path) when key_np > 0, so that the lanes of a wave — paths
  * next to each other — store their keys and ranks into the same lines
  * instead of one 4-B store per 16-B path block; else the slot index */
 PMD size_t key_index(const TraceParams &P, uint32_t pid, uint32_t k) {
-    const size_t path = (size_t)(pid - (uint64_t)P.slot_path_base);
+    const size_t path = path_slot_base(P, pid);
     return P.key_np > 0 ? (size_t)k * (size_t)P.key_np + path : path * (size_t)P.mpc + k;
 }
 PMD void flush_rank(const TraceParams &P, PathState &st) {
@@ -91,9 +85,8 @@ PMD void flush_rank(const TraceParams &P, PathState &st) {
 /* HOLD_MPC, HOLD_WORDS: pm_plan_pod.h */
 struct Held {
     uint32_t *col;    /* this thread's LDS column: word i at col[i * TRACE_BLOCK] */
-    uint4 key, rank;  /* shift registers, .x the newest deposit's */
+    uint4 key, rank;  /* shift registers, .x the newest deposit's; those beyond the path's count are never read */
 };
-PMD void held_clear(Held &h) { (void)h; } /* deposits beyond the path's count are never read */
 PMD void held_put(Held &h, const TraceParams &P, size_t slot, uint32_t k, v3 p, v3 a, v3 wi, uint32_t key,
                   uint32_t rank) {
     if (k < 3u) {
@@ -104,7 +97,7 @@ PMD void held_put(Held &h, const TraceParams &P, size_t slot, uint32_t k, v3 p, 
         c[6 * TRACE_BLOCK] = __float_as_uint(wi.x); c[7 * TRACE_BLOCK] = __float_as_uint(wi.y);
         c[8 * TRACE_BLOCK] = __float_as_uint(wi.z);
     } else {
-        store_photon(P.slots + slot, p, a, wi); /* the last deposit: the block is written right after */
+        store_photon(P.slots + slot, 1u, p, a, wi); /* the last deposit: the block is written right after */
     }
     h.key = make_uint4(key, h.key.x, h.key.y, h.key.z);
     h.rank = make_uint4(rank, h.rank.x, h.rank.y, h.rank.z);
@@ -114,7 +107,7 @@ PMD void held_put(Held &h, const TraceParams &P, size_t slot, uint32_t k, v3 p, 
  * deposits), slot 3 zero unless its deposit was stored; with fused counting
  * the key and rank quads (key 0xffffffff past n) */
 PMD void held_write(const TraceParams &P, uint32_t pid, const Held &h, uint32_t n) {
-    const size_t path = (size_t)(pid - (uint64_t)P.slot_path_base);
+    const size_t path = path_slot_base(P, pid);
     uint32_t w[HOLD_WORDS];
 #pragma unroll
     for (int i = 0; i < HOLD_WORDS; ++i) w[i] = (uint32_t)(i / 9) < n ? h.col[i * TRACE_BLOCK] : 0u;
@@ -290,9 +283,9 @@ PMD bool path_shade(const TraceParams &P, const SceneDev &S, PathState &st, cons
     }
     v3 wo = -st.ray.d;
     if (st.nI >= 1) {
-        const size_t slot = (size_t)(st.pid - (uint64_t)P.slot_path_base) * mpc + (st.nI - 1);
-        if (MARK) store_photon_marked(P.slots + slot, st.diff ? 1u : 3u, hit_point, st.alpha, wo);
-        else if (!HOLD) store_photon(P.slots + slot, hit_point, st.alpha, wo);
+        const size_t slot = path_slot_base(P, st.pid) * mpc + (st.nI - 1);
+        /* MARK is never built with HOLD (the static_assert above), so a MARK kernel always stores here */
+        if (!HOLD) store_photon(P.slots + slot, MARK && !st.diff ? 3u : 1u, hit_point, st.alpha, wo);
         st.stored = st.nI;
         uint32_t key = 0xffffffffu, rank = 0u;
         if (P.bucket) { /* fused counting pass of the bucket build (pm_bucket.hip k_bucket_count) */
@@ -339,7 +332,7 @@ PMD void finish_path(const TraceParams &P, PathState &st, const Held *held = nul
     if (HOLD) { held_write(P, st.pid, *held, st.stored); return; }
     flush_rank(P, st);
     const uint32_t mpc = (uint32_t)P.mpc;
-    pm_photon *slots = P.slots + (size_t)(st.pid - (uint64_t)P.slot_path_base) * mpc;
+    pm_photon *slots = P.slots + path_slot_base(P, st.pid) * mpc;
     const float2 z = make_float2(0.f, 0.f);
     for (uint32_t k = st.stored; k < mpc; ++k) {
         float2 *q = reinterpret_cast<float2 *>(slots + k);
@@ -351,6 +344,12 @@ PMD void finish_path(const TraceParams &P, PathState &st, const Held *held = nul
         if (!P.lazy_zero) { q[0] = z; q[1] = z; q[2] = z; q[3] = z; q[4] = z; }
         if (P.bucket) P.key[key_index(P, st.pid, k)] = 0xffffffffu;
     }
+}
+
+/* the COUNT kernels' last act: the block's census into P.counters */
+PMD void census_tail(const TraceParams &, const NoCensus &, uint32_t, uint32_t) {}
+PMD void census_tail(const TraceParams &P, const Census &cen, uint32_t rays, uint32_t deposits) {
+    count4(P.counters, rays, cen.nodes, cen.prims, deposits);
 }
 
 /* Per-lane photon tracer: one path per lane, no block barriers; a wave lives
@@ -380,7 +379,6 @@ PMD void trace_lane_body(const TraceParams &P) {
         held.col = reinterpret_cast<uint32_t *>(stk + P.S.stack_depth * TRACE_BLOCK + (mode_lds(MODE) ? (int)((P.S.lds_bytes + 15u) / 4u & ~3u) : 0)) + tid;
     prof.begin();
     if (path < P.path_count) {
-        if (HOLD) held_clear(held);
         bool alive = emit_path<ALL>(P, S, perm, (uint32_t)(P.path_begin + path), st);
         if (MARK) st.diff = 0u;
         prof.mark(0);
@@ -393,11 +391,7 @@ PMD void trace_lane_body(const TraceParams &P) {
         finish_path<HOLD>(P, st, &held);
     }
     prof.flush(P.prof);
-    if (COUNT) {
-        uint32_t nodes = 0, prims = 0;
-        if constexpr (COUNT != 0) { nodes = cen.nodes; prims = cen.prims; }
-        count4(P.counters, rays, nodes, prims, deposits);
-    }
+    census_tail(P, cen, rays, deposits);
 }
 
 template <int COUNT, int MODE, int HOLD, int ALL = 0, bool TEX = false>
@@ -418,35 +412,23 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_lane_mark(TraceParams P) 
  * rest of the time every iteration runs POOL_STEPS traversal steps for the
  * traversing lanes. Paths, slots and bucket counts are the per-lane
  * kernel's (owner-writes; the fused bucket ranks' order is immaterial). */
-#ifndef PM_POOL_SHADE_MIN
-#define PM_POOL_SHADE_MIN 16
-#endif
-#ifndef PM_POOL_STEPS
-#define PM_POOL_STEPS 4
-#endif
-constexpr int POOL_STEPS = PM_POOL_STEPS, POOL_SHADE_MIN = PM_POOL_SHADE_MIN;
+constexpr int POOL_SHADE_MIN = 16, POOL_STEPS = 4;
 enum { PHASE_DEAD = 0, PHASE_TRAV = 1, PHASE_SHADE = 2 };
-
-/* W8: the 8-wide tree (S.wide == 3, TravState8); ALL: emit_path's; TEX, SPEC, MARK: path_shade's */
-template <int COUNT, int HOLD, int W8, int ALL, bool TEX, bool SPEC, bool MARK = false>
-/* 5 waves/SIMD: 96 VGPRs (102 unconstrained -> 4 waves), no scratch; with
+/* 5 waves/SIMD: 96 VGPRs with 28 B of scratch (104 B with held deposits;
+ * unconstrained the kernel takes more registers and fits 4 waves); with
  * the LDS stacks capped at 31 entries (PM_POOL_STACK, the rest spilled) five
  * 256-thread blocks fit a CU. C3 trace (same box): 4.59-4.61 ms at 4 waves,
  * 4.41-4.42 ms at 5 (stack 31 or 24); 6 (80 VGPRs, 100 B of scratch) 4.58 */
-#ifndef PM_POOL_EU
-#define PM_POOL_EU 5
-#endif
-#if PM_POOL_EU > 0
-#define POOL_OCC __attribute__((amdgpu_waves_per_eu(PM_POOL_EU, PM_POOL_EU)))
-#else
-#define POOL_OCC
-#endif
-/* the 8-wide walk needs 117 VGPRs unconstrained: 4 waves/SIMD (113, no
- * scratch) by default; 5 spills 88 B */
-#ifndef PM_POOL8_EU
-#define PM_POOL8_EU 4
-#endif
-__device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs without SLP: 4 waves/SIMD */
+constexpr int POOL_EU = 5;
+/* the 8-wide walk: 4 waves/SIMD (102 VGPRs, 115 with held deposits, no
+ * scratch); at 5 it spilled 88 B */
+constexpr int POOL8_EU = 4;
+#define POOL_OCC __attribute__((amdgpu_waves_per_eu(POOL_EU, POOL_EU)))
+#define POOL8_OCC __attribute__((amdgpu_waves_per_eu(POOL8_EU, POOL8_EU)))
+
+/* W8: the 8-wide tree (S.wide == 3, TravState8); ALL: emit_path's; TEX, SPEC, MARK: path_shade's */
+template <int COUNT, int HOLD, int W8, int ALL, bool TEX, bool SPEC, bool MARK = false>
+__device__ __forceinline__ void trace_pool_body(TraceParams P) {
     extern __shared__ __attribute__((aligned(16))) int stk[];
     __shared__ uint32_t perm[28];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -495,7 +477,6 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
             if (cursor < wend) {
                 const int64_t mine = cursor + __popcll(dm & ((1ull << lane) - 1ull));
                 if (phase == PHASE_DEAD && mine < wend) {
-                    if (HOLD) held_clear(held);
                     const bool emitted = emit_path<ALL>(P, S, perm, (uint32_t)(P.path_begin + mine), st);
                     if (MARK) st.diff = 0u;
                     if (emitted) {
@@ -513,11 +494,7 @@ __device__ __forceinline__ void trace_pool_body(TraceParams P) { /* ~102 VGPRs w
         for (int k = 0; k < POOL_STEPS; ++k)
             if (phase == PHASE_TRAV && !trav_step(S, st.ray, tr, sstk, cen)) phase = PHASE_SHADE;
     }
-    if (COUNT) {
-        uint32_t nodes = 0, prims = 0;
-        if constexpr (COUNT != 0) { nodes = cen.nodes; prims = cen.prims; }
-        count4(P.counters, rays, nodes, prims, deposits);
-    }
+    census_tail(P, cen, rays, deposits);
 }
 
 template <int COUNT, int HOLD, int ALL = 0, bool TEX = false>
@@ -525,42 +502,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool(TraceParams
 template <int COUNT, int HOLD, int ALL>
 __global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool_spec(TraceParams P) { trace_pool_body<COUNT, HOLD, 0, ALL, true, true>(P); }
 template <int COUNT, int HOLD, int ALL = 0, bool TEX = false>
-__global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
-void k_trace_pool8(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, TEX, false>(P); }
+__global__ __launch_bounds__(TRACE_BLOCK) POOL8_OCC void k_trace_pool8(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, TEX, false>(P); }
 template <int COUNT, int HOLD, int ALL>
-__global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
-void k_trace_pool8_spec(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, true, true>(P); }
+__global__ __launch_bounds__(TRACE_BLOCK) POOL8_OCC void k_trace_pool8_spec(TraceParams P) { trace_pool_body<COUNT, HOLD, 1, ALL, true, true>(P); }
 /* pm_set_caustic_map: k_trace_pool<COUNT, 0, ALL> / k_trace_pool8<COUNT, 0, ALL> that mark caustic photons */
 template <int COUNT, int ALL>
 __global__ __launch_bounds__(TRACE_BLOCK) POOL_OCC void k_trace_pool_mark(TraceParams P) { trace_pool_body<COUNT, 0, 0, ALL, false, false, true>(P); }
 template <int COUNT, int ALL>
-__global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PM_POOL8_EU, PM_POOL8_EU)))
-void k_trace_pool8_mark(TraceParams P) { trace_pool_body<COUNT, 0, 1, ALL, false, false, true>(P); }
-
-/* resident waves per CU of a trace kernel family at `lds` bytes of dynamic
- * LDS (0 if unknown): the occupancy plan_trace (pm_plan.h) asks for. The
- * bytes are the plan's; this only picks the kernel */
-template <class K>
-static int kernel_waves_per_cu(K kernel, size_t lds) {
-    int blocks = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, TRACE_BLOCK, lds) == hipSuccess ? blocks * (TRACE_BLOCK / 64) : 0;
-}
-int trace_waves_per_cu(TraceFamily family, bool hold, size_t lds) {
-    if (family == TRACE_POOL8) return hold ? kernel_waves_per_cu(k_trace_pool8<0, 1>, lds) : kernel_waves_per_cu(k_trace_pool8<0, 0>, lds);
-    if (family == TRACE_POOL) return hold ? kernel_waves_per_cu(k_trace_pool<0, 1>, lds) : kernel_waves_per_cu(k_trace_pool<0, 0>, lds);
-    if (hold) {
-        switch (family) {
-        case TRACE_LANE_BRUTE: return kernel_waves_per_cu(k_trace_lane<0, MODE_BRUTE, 1>, lds);
-        case TRACE_LANE_LDS: return kernel_waves_per_cu(k_trace_lane<0, MODE_LDS, 1>, lds);
-        default: return kernel_waves_per_cu(k_trace_lane<0, MODE_GLOBAL, 1>, lds);
-        }
-    }
-    switch (family) {
-    case TRACE_LANE_BRUTE: return kernel_waves_per_cu(k_trace_lane<0, MODE_BRUTE, 0>, lds);
-    case TRACE_LANE_LDS: return kernel_waves_per_cu(k_trace_lane<0, MODE_LDS, 0>, lds);
-    default: return kernel_waves_per_cu(k_trace_lane<0, MODE_GLOBAL, 0>, lds); /* the plan asks no other family */
-    }
-}
+__global__ __launch_bounds__(TRACE_BLOCK) POOL8_OCC void k_trace_pool8_mark(TraceParams P) { trace_pool_body<COUNT, 0, 1, ALL, false, false, true>(P); }
 
 /* MAT: which instantiations a scene runs: 0 = the plain ones, 1 = TEX (a
  * textured material), 2 = SPEC (a material of the physical specular model),
@@ -584,78 +533,70 @@ static auto pool_kernel() {
         else return &k_trace_pool<COUNT, HOLD, ALL, MAT == 1>;
     }
 }
-
-template <int HOLD, int ALL, int MAT>
-static void launch_lane(const TraceParams &p, TraceFamily family, dim3 grid, size_t lds, int count, hipStream_t s) {
-    switch (family) {
-    case TRACE_LANE_BRUTE:
-        if (count) pm_launch((lane_kernel<1, MODE_BRUTE, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((lane_kernel<0, MODE_BRUTE, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-        break;
-    case TRACE_LANE_LDS:
-        if (count) pm_launch((lane_kernel<1, MODE_LDS, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((lane_kernel<0, MODE_LDS, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-        break;
-    case TRACE_LANE_INST: /* instances: the per-lane kernel (the pooled one walks only one level) */
-        if (count) pm_launch((lane_kernel<1, MODE_INST, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((lane_kernel<0, MODE_INST, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-        break;
-    default:
-        if (count) pm_launch((lane_kernel<1, MODE_GLOBAL, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-        else pm_launch((lane_kernel<0, MODE_GLOBAL, HOLD, ALL, MAT>()), grid, dim3(TRACE_BLOCK), lds, s, p);
-        break;
+/* f(std::integral_constant<int, MAT>): dispatch_flag (pm_kernels.h) for the four-valued MAT of this unit */
+template <class F>
+static void dispatch_mat(int mat, F &&f) {
+    switch (mat) {
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    default: f(std::integral_constant<int, 0>{}); break;
+    }
+}
+/* f(kernel) for the kernel of a family: the pooled ones by tree width, the
+ * per-lane ones by traversal mode (instances: the per-lane kernel, the pooled
+ * one walks only one level; plan_trace asks trace_waves_per_cu for
+ * TRACE_LANE_GLOBAL's occupancy in their place, never TRACE_LANE_INST's) */
+template <int COUNT, int HOLD, int ALL, int MAT, class F>
+static void dispatch_family(TraceFamily family, F &&f) {
+    if (family == TRACE_POOL || family == TRACE_POOL8) {
+        dispatch_flag(family == TRACE_POOL8, [&](auto W8) { f(pool_kernel<COUNT, HOLD, decltype(W8)::value, ALL, MAT>()); });
+    } else {
+        const int mode = family == TRACE_LANE_BRUTE ? MODE_BRUTE : family == TRACE_LANE_LDS ? MODE_LDS
+                         : family == TRACE_LANE_INST ? MODE_INST : MODE_GLOBAL;
+        dispatch_mode(mode, [&](auto MODE) { f(lane_kernel<COUNT, decltype(MODE)::value, HOLD, ALL, MAT>()); });
     }
 }
 
-/* the pooled kernels (4-wide: k_trace_pool; 8-wide: k_trace_pool8) */
-template <int ALL, int MAT>
-static void launch_pool(const TraceParams &p, const TracePlan &pl, dim3 grid, int count, hipStream_t s) {
-    const bool hold = pl.hold_launch;
-    if (pl.family == TRACE_POOL8) {
-        if (count && hold) pm_launch((pool_kernel<1, 1, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds_hold, s, p);
-        else if (count) pm_launch((pool_kernel<1, 0, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds, s, p);
-        else if (hold) pm_launch((pool_kernel<0, 1, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds_hold, s, p);
-        else pm_launch((pool_kernel<0, 0, 1, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds, s, p);
-    } else if (count && hold) pm_launch((pool_kernel<1, 1, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds_hold, s, p);
-    else if (count) pm_launch((pool_kernel<1, 0, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds, s, p);
-    else if (hold) pm_launch((pool_kernel<0, 1, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds_hold, s, p);
-    else pm_launch((pool_kernel<0, 0, 0, ALL, MAT>()), grid, dim3(TRACE_BLOCK), pl.lds, s, p);
+/* resident waves per CU of a trace kernel family at `lds` bytes of dynamic
+ * LDS (0 if unknown): the occupancy plan_trace (pm_plan.h) asks for. The
+ * bytes are the plan's; this only picks the kernel */
+int trace_waves_per_cu(TraceFamily family, bool hold, size_t lds) {
+    int blocks = 0;
+    dispatch_flag(hold, [&](auto HOLD) {
+        dispatch_family<0, decltype(HOLD)::value, 0, 0>(family, [&](auto kernel) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, TRACE_BLOCK, lds) != hipSuccess) blocks = 0;
+        });
+    });
+    return blocks * (TRACE_BLOCK / 64);
 }
 
 /* kernel, grid and LDS bytes are the plan's (plan_trace, pm_plan.h: the one
  * place they are computed); p carries the same plan's pool_stack, pool_paths,
- * hold and spill_stride to the kernel */
-template <int MAT>
-static hipError_t launch_trace_mat(const TraceParams &p, const TracePlan &pl, int count, hipStream_t s) {
-    /* PM_ALL_LIGHTS: the ALL instantiations; a fixed light is an index into S.lights */
-    const bool all = p.light_index == PM_ALL_LIGHTS;
-    if (all ? !p.light_cdf : p.light_index < 0 || p.light_index >= p.S.n_lights) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)pl.grid_blocks);
-    if (pl.pooled) {
-        if (pl.spill_entries > 0 && !p.spill) return hipErrorInvalidValue;
-        if (all) launch_pool<1, MAT>(p, pl, grid, count, s);
-        else launch_pool<0, MAT>(p, pl, grid, count, s);
-        return hipGetLastError();
-    }
-    /* one path per lane */
-    if (pl.hold_launch) {
-        if (all) launch_lane<1, 1, MAT>(p, pl.family, grid, pl.lds_hold, count, s);
-        else launch_lane<1, 0, MAT>(p, pl.family, grid, pl.lds_hold, count, s);
-    } else if (all) launch_lane<0, 1, MAT>(p, pl.family, grid, pl.lds, count, s);
-    else launch_lane<0, 0, MAT>(p, pl.family, grid, pl.lds, count, s);
-    return hipGetLastError();
-}
-
-/* a scene with a material of the physical specular model (SceneDev::mat_spec)
- * runs the SPEC instantiations, one with a textured material
- * (SceneDev::tex_recs) the TEX ones; every other scene the kernels it ran
- * before either existed */
+ * hold and spill_stride to the kernel. A scene with a material of the
+ * physical specular model (SceneDev::mat_spec) runs the SPEC instantiations,
+ * one with a textured material (SceneDev::tex_recs) the TEX ones, a plain one
+ * under pm_set_caustic_map the MARK ones (deposits stored one by one:
+ * plan_trace under TraceShape::mark); every other scene the kernels it ran
+ * before any of these existed */
 hipError_t launch_trace(const TraceParams &p, const TracePlan &pl, int count, hipStream_t s) {
     if (p.path_count <= 0) return hipSuccess;
-    if (p.mark) /* the MARK instantiations: plain scenes, deposits stored one by one (plan_trace under TraceShape::mark) */
-        return p.S.mat_spec || p.S.tex_recs || pl.hold_launch || p.hold ? hipErrorInvalidValue : launch_trace_mat<3>(p, pl, count, s);
-    if (p.S.mat_spec) return p.S.mat_tex ? launch_trace_mat<2>(p, pl, count, s) : hipErrorInvalidValue;
-    return p.S.tex_recs ? launch_trace_mat<1>(p, pl, count, s) : launch_trace_mat<0>(p, pl, count, s);
+    const int mat = p.mark ? 3 : p.S.mat_spec ? 2 : p.S.tex_recs ? 1 : 0;
+    /* PM_ALL_LIGHTS: the ALL instantiations; a fixed light is an index into S.lights */
+    const bool all = p.light_index == PM_ALL_LIGHTS;
+    if ((p.mark && (p.S.mat_spec || p.S.tex_recs || pl.hold_launch || p.hold)) || (mat == 2 && !p.S.mat_tex) ||
+        (all ? !p.light_cdf : p.light_index < 0 || p.light_index >= p.S.n_lights) ||
+        (pl.pooled && pl.spill_entries > 0 && !p.spill))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)pl.grid_blocks);
+    const size_t lds = pl.hold_launch ? pl.lds_hold : pl.lds;
+    dispatch_flag(count != 0, [&](auto COUNT) { dispatch_flag(pl.hold_launch, [&](auto HOLD) { dispatch_flag(all, [&](auto ALL) {
+        dispatch_mat(mat, [&](auto MAT) {
+            dispatch_family<decltype(COUNT)::value, decltype(HOLD)::value, decltype(ALL)::value, decltype(MAT)::value>(
+                pl.family, [&](auto kernel) { pm_launch(kernel, grid, dim3(TRACE_BLOCK), lds, s, p); });
+        });
+    }); }); });
+    return hipGetLastError();
 }
 
 } // namespace pm

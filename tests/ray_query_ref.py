@@ -3,7 +3,7 @@ a ray against triangles, disks and spheres) and the ray and scene generators of
 tests/test_ray_query.py (CPU) and tests/test_ray_query_gpu.py (GPU).
 
 This is not a restatement of the device's intersectors (pm_isect.h) or walkers
-(pm_traverse.h): triangles are intersected with the
+(pm_slab.h, pm_leaf.h, pm_traverse.h, pm_trav_step.h): triangles are intersected with the
 textbook Moller-Trumbore test on edge vectors taken from the vertices
 (e1 = p1 - p0, e2 = p2 - p0, pvec = d x e2, ...), disks and spheres
 analytically, everything in float64 on the fp32 input values widened. No

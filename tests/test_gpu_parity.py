@@ -987,7 +987,7 @@ def test_kd_gather_reports_stack_overflow(oracle_mod, hip_mod, monkeypatch):
 def test_bvh8_equals_bvh4(n_tris, oracle_mod, hip_mod, monkeypatch):
     """The 8-wide quantized tree (PM_BVH8=1: pm_build.h collapse_bvh8 /
     quantize_bvh8, pm_traverse.h traverse8 and the pooled kernel's
-    k_trace_pool8) against the 4-wide one on the same soup: eye records,
+    k_trace_pool8 with pm_trav_step.h trav_step) against the 4-wide one on the same soup: eye records,
     every photon slot and the grid render bit for bit (closest hits do not
     depend on the tree; ties resolve to the lowest global id), and the slots
     equal the oracle's."""

@@ -1,7 +1,7 @@
 """CPU tests of the float64 ray-query reference and its generators
 (ray_query_ref.py): the decided shares and caps the GPU tests rely on, the
 reference against longdouble and exact rational arithmetic, the generators'
-claims, and the slab-test bound of pm_traverse.h (box_near with the per-ray
+claims, and the slab-test bound of pm_slab.h (box_near with the per-ray
 pad) in emulated fp32 on the far-origin group."""
 from fractions import Fraction
 
@@ -117,7 +117,7 @@ def slab_accepts(lo, hi, o, d, t_hit, ray_pad):
     """box_near in emulated fp32 on the box [lo, hi] padded as pm_commit pads
     it, with an exact reciprocal rounded to fp32 (the hardware's is within an
     ulp of it): does the box's [tn, tf] survive, with tmax = the hit's own t?
-    ray_pad: the per-ray pad 2^-20 max|o| (pm_traverse.h ray_pad2, ray_oinv, ray_oinv_hi) or none."""
+    ray_pad: the per-ray pad 2^-20 max|o| (pm_slab.h ray_pad2, ray_slab, ray_oinv_hi) or none."""
     lo, hi = Q.padded_box(lo, hi)
     dd = np.where(np.abs(d) < f32(1e-20), np.copysign(f32(1e-20), d), d).astype(f32)
     inv = (1.0 / dd.astype(np.float64)).astype(f32)

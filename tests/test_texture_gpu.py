@@ -453,7 +453,7 @@ def test_every_traversal_mode_gives_the_same_records_albedo_and_slots(monkeypatc
 @pytest.mark.parametrize("bvh8", ["0", "1"])
 def test_pool_stack_spill_leaves_the_slots_unchanged(monkeypatch, bvh8):
     """The pooled trace keeps PM_POOL_STACK traversal-stack entries per lane in LDS and spills deeper ones to
-    global memory (pm_traverse.h SpillStack; sized by pm_plan.cpp plan_trace). PM_POOL_STACK=0 reserves the tree's
+    global memory (pm_trav_step.h SpillStack; sized by pm_plan.cpp plan_trace). PM_POOL_STACK=0 reserves the tree's
     exact bound: no spill. PM_POOL_STACK=1 is the smallest cap SpillStack supports by its code (entry i < cap in
     LDS, every other one in the spill area; a cap of 0 means `the exact bound` to plan_trace), and it is below
     every tree's bound: fill_scene_dev sets S.stack_depth = max(2, the wide tree's stack bound + 1), and the
